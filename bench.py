@@ -15,11 +15,14 @@ for it as THE value: `value` = N_from * N_to * steps / wall of those calls.  The
 clock has stopped, on a heap the process has touched before (FrameKeeper: the disposal of a result -- ~0.9 ms of reference counting
 -- and the first touch of fresh pages are not part of a call); `match_wall_ms` is the same call under a per-call clock (median of 7).
 The bench contract's own reading of `value` -- the same work with the list ALREADY RESIDENT IN HBM, nothing crossing PCIe inside
-the timed region (fit + vectorise + index + K3: `TfidfMatchJob.step`) -- is timed in a second region of the same run, same
-protocol, and reported as `device_step` (`--step device` makes it the line); `kernel_ms_per_step` and `roofline` (the dominant
-kernel, K3, timed live with HIP events on the library's stream) are that region's.
+the timed region (fit + vectorise + index + K3: `TfidfMatchJob.step`) -- is timed with --full in a second region of the same
+run, same protocol, and reported as `device_step` (`--step device` makes it the line); `kernel_ms_per_step` and `roofline` (the
+dominant kernel, K3, timed live with HIP events on the library's stream) are that region's.
 
-The same JSON line also carries, measured after the timed regions on rank 0 at N = 1:
+A plain run (no --full) does only what the line's headline figure needs: set up, warm up, time exactly --steps steps, write the
+last step's outputs (--dump-outputs DIR: DIR/<name>.npy; the headline's are to_index and similarity, the frame's To / Similarity
+columns as numbers) and print the line.  With --full the same JSON line also carries, measured after the timed regions on rank 0
+at N = 1:
   match_wall_ms / match_stages_ms    the same call under a median-of-7 protocol with its stage stamps
   latency.top1_single_query_ms       one query string against the fitted 100k list, top-1, re_train=False
   roofline, cpu_baseline (+ cpu_baseline_arms), parity_check (EVERY from-row the all-cores CPU arm computes -- the whole list on a
@@ -101,9 +104,19 @@ def parse(argv=None):
                          "WITHOUT a GPU -- hands the ranks to tests/bench_rehearsal.py (TfidfMatchJob through tests/cpu_engine.py on a "
                          "400-name list); prints a rehearsal record, never a bench line")
     ap.add_argument("--config", choices=("tfidf", "c2", "editdistance", "rapidfuzz", "dense", "tfidf_1m"), default="tfidf",
-                    help="tfidf: the headline (+ every other config as a sub-record at N = 1); the others: that "
+                    help="tfidf: the headline (+ every other config as a sub-record at N = 1 with --full); the others: that "
                          "configuration alone as the line")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the line's own timed steps: the device-resident second region (`device_step`), the "
+                         "per-kernel breakdown, the CPU baselines and parity checks, .match() wall time and latency, the other "
+                         "configurations' sub-records.  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all)")
+    args = ap.parse_args(argv)
+    if not args.full:
+        args.no_cpu_baseline = args.no_match_wall = args.no_configs = True
+    return args
 
 
 # ---- who am I: single process, one process per GPU (torch.distributed), or one thread per rank ------------------
@@ -588,6 +601,46 @@ def contract(metric, value, unit, world, args, steps, warmup, wall, scaling, dty
             "dtype": dtype, "data": data, "config": config}
 
 
+# ---- --dump-outputs: what the timed path returned in its last step ---------------------------------------------------
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def topn_outputs(idx, val):
+    """a device top-n / best-match result: index (-1: no match) and score per row"""
+    val = np.asarray(val)
+    return {"index": np.asarray(idx, np.float64), "score": val.astype(np.float32 if val.dtype == np.float32 else np.float64)}
+
+
+def frame_outputs(frame, names, top_n):
+    """the user-level call's DataFrame as numbers: to_index[:, r] = the position in `names` of the first occurrence of the
+    rank-r To string (-1: None), similarity[:, r] = its Similarity column"""
+    first = {}
+    for i, s in enumerate(names):
+        first.setdefault(s, i)
+    to_index = np.empty((len(frame), top_n), np.float64)
+    similarity = np.empty((len(frame), top_n), np.float64)
+    for r in range(top_n):
+        sfx = "" if r == 0 else f"_{r + 1}"
+        to_index[:, r] = [-1 if t is None else first[t] for t in frame["To" + sfx].tolist()]
+        similarity[:, r] = frame["Similarity" + sfx].to_numpy(np.float64)
+    return {"to_index": to_index, "similarity": similarity}
+
+
+def write_outputs(directory, arrays):
+    """DIR/<name>.npy for every array (rows along the first axis).  Above DUMP_MAX_BYTES in all, a fixed seeded sample of the
+    rows is written instead, its row numbers as rows.npy."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        n = len(next(iter(arrays.values())))
+        keep = max(1, DUMP_MAX_BYTES // (-(-total // n) + 8))
+        rows = np.sort(np.random.default_rng(SEED).choice(n, keep, replace=False))
+        arrays = dict({k: a[rows] for k, a in arrays.items()}, rows=rows.astype(np.float64))
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+
+
 # ---- configuration: the headline (and config 2 / config 4's shard, the same job at other sizes) --------------------
 
 def run_tfidf(world, ctx, args, from_shard=None, to_list=None, top_n=None, steps=None, warmup=None, self_match=True,
@@ -611,10 +664,43 @@ def run_tfidf(world, ctx, args, from_shard=None, to_list=None, top_n=None, steps
         uwall, _ = timed_steps(world, ctx, user_step, steps, warmup)
         k3u = ctx.prof_get("k3_cossim_topn")
         user = {"wall": uwall, "gpu_ms": ctx.event_elapsed_ms(0, 1), "k3_ms": k3u[0] / max(k3u[1], 1) * (k3u[1] / steps), "k3_launches": k3u[1] / steps}
+    metric = ("string-pairs/sec, TF-IDF cosine top-n 100k x 100k (config.timed_step says what a step is: by default the user-level "
+              ".match() call of SURVEY section 8d's metric, `device_step` = the list resident in HBM; latency.top1_single_query_ms = "
+              "top-1 match latency)"
+              if label is None else f"string-pairs/sec, TF-IDF cosine top-{top_n}, {label}")
+    scaling = tfidf_scaling(args, world.size) if (label is None or world.size > 1 and args.scaling) else "weak"
+    data = ("real: reference data/company_names.json (100 000 SEC-EDGAR names, gzipped in polyfuzz_amd/data/)" if kind == "real"
+            else "synthetic: token recombination of the real names (polyfuzz_amd/synth.py, SURVEY section 8d config 4)")
+    config = {"workload": label or (f"TFIDF(min_similarity={MIN_SIM}, top_n={top_n}).match(names): self-match of "
+                                    f"{'the first ' + str(n_to) + ' of the ' if n_to < N_NAMES else 'all '}{N_NAMES} real company names, "
+                                    "char-3-gram TF-IDF cosine (SURVEY.md section 8d headline; reference "
+                                    "docs/tutorial/datasets/datasets.md:36-41)"),
+              "n_from_total": n_from_total, "n_from_this_rank": job.n_from, "n_to": n_to, "top_n": top_n, "from_rows": shard_desc}
+    if user is not None and not args.full:
+        # a plain run: the line is timed region 1 alone (the device-resident region and everything after it: --full)
+        if world.rank != 0:
+            return None, job, None
+        config.update({"transport": world.kind, "device": ctx.info()["name"]})
+        out = contract(metric, float(n_from_total) * float(n_to) * steps / user["wall"], "pairs/s", world, args, steps, warmup,
+                       user["wall"], scaling, "f32", data, config)
+        out["gpu_ms_per_step_rank0"] = user["gpu_ms"] / steps
+        out["k3_ms_per_step_inside_the_call"] = user["k3_ms"]
+        return out, job, None
     # the device-resident step (timed region 2 when there is a user-level step): same protocol, list resident in HBM
     wall, result = timed_steps(world, ctx, job.step, steps, warmup)
     k3_timed = ctx.prof_get("k3_cossim_topn")
     gpu_ms = ctx.event_elapsed_ms(0, 1)
+    if not args.full:
+        # a plain run of the device-resident step: the line and the result of its last step
+        if world.rank != 0:
+            return None, job, None
+        config.update({"step": job.step_description(), "transport": world.kind, "device": ctx.info()["name"]})
+        out = contract(metric, float(n_from_total) * float(n_to) * steps / wall, "pairs/s", world, args, steps, warmup, wall,
+                       scaling, "f32", data, config)
+        out["gpu_ms_per_step_rank0"] = gpu_ms / steps
+        if args.dump_outputs:
+            out["_outputs"] = topn_outputs(*result.download())
+        return out, job, None
     # the per-kernel breakdown of a step: three more steps with every profiled kernel bracketed, outside the timed region
     ctx.prof_enable(True)
     ctx.prof_reset()
@@ -627,26 +713,15 @@ def run_tfidf(world, ctx, args, from_shard=None, to_list=None, top_n=None, steps
     kernel_ms = {name: round(ctx.prof_get(name)[0] / 3, 4) for name in pipeline.PROFILED_KERNELS}
     stats = job.stats()
     traffic, traffic_note = recorded_traffic(traffic_key(args, traffic_label))
-    out = contract(
-        "string-pairs/sec, TF-IDF cosine top-n 100k x 100k (config.timed_step says what a step is: by default the user-level "
-        ".match() call of SURVEY section 8d's metric, `device_step` = the list resident in HBM; latency.top1_single_query_ms = "
-        "top-1 match latency)"
-        if label is None else f"string-pairs/sec, TF-IDF cosine top-{top_n}, {label}",
-        float(n_from_total) * float(n_to) * steps / wall, "pairs/s", world, args, steps, warmup, wall,
-        tfidf_scaling(args, world.size) if (label is None or world.size > 1 and args.scaling) else "weak", "f32",
-        "real: reference data/company_names.json (100 000 SEC-EDGAR names, gzipped in polyfuzz_amd/data/)" if kind == "real"
-        else "synthetic: token recombination of the real names (polyfuzz_amd/synth.py, SURVEY section 8d config 4)",
-        {"workload": label or (f"TFIDF(min_similarity={MIN_SIM}, top_n={top_n}).match(names): self-match of "
-                               f"{'the first ' + str(n_to) + ' of the ' if n_to < N_NAMES else 'all '}{N_NAMES} real company names, "
-                               "char-3-gram TF-IDF cosine (SURVEY.md section 8d headline; reference "
-                               "docs/tutorial/datasets/datasets.md:36-41)"),
-         "n_from_total": n_from_total, "n_from_this_rank": job.n_from, "n_to": n_to, "top_n": top_n, "from_rows": shard_desc,
+    config.update({
          "vocab": stats["vocab"], "nnz_from": stats["nnz_from"], "nnz_to": stats["nnz_to"], "multiply_adds_rank0": stats["madds"],
          "step": job.step_description(),
          "parallelism": (f"from-rows sharded x{world.size}, list replicated" if not job.result_is_full else
                          f"from-rows sharded x{world.size} (rank r: the rows r, r + {world.size}, ...), list replicated, every unordered pair scored once over all ranks"),
          "exchange": exchange if not job.result_is_full else exchange.replace("of the per-shard result blocks", "of the pass-0 thresholds and of the per-row candidate lists"),
          "transport": world.kind, "device": ctx.info()["name"]})
+    out = contract(metric, float(n_from_total) * float(n_to) * steps / wall, "pairs/s", world, args, steps, warmup, wall,
+                   scaling, "f32", data, config)
     out["gpu_ms_per_step_rank0"] = gpu_ms / steps
     out["kernel_ms_per_step"] = kernel_ms
     out["roofline"] = k3_roofline(job, stats, k3_timed[0], k3_timed[1], top_n, traffic, traffic_note)
@@ -670,6 +745,8 @@ def run_tfidf(world, ctx, args, from_shard=None, to_list=None, top_n=None, steps
             out["cpu_baseline"], out["cpu_baseline_arms"], out["parity_check"] = k3_cpu_and_parity(
                 job, res[0], res[1], args.cpu_seconds if cpu_seconds is None else cpu_seconds, all_cores=all_cores_arm,
                 min_rows=min_parity_rows, lists=(from_shard, to_list), all_cores_seconds=all_cores_seconds)
+    if args.dump_outputs and user is None:
+        out["_outputs"] = topn_outputs(*(res if res is not None else result.download()))
     return out, job, res
 
 
@@ -788,7 +865,9 @@ def headline(world, ctx, args):
         out["value_definition"] = ("SURVEY section 8d's metric: N_from x N_to x steps / wall of the timed steps, a step = the user-level call "
                                    "(host list to DataFrame: host packing, PCIe both ways and the frame are inside).  The device-resident "
                                    "step -- the list already in HBM, what the bench contract's `value` names -- is timed in a second region "
-                                   "of the same run: `device_step`; `--step device` makes it the line.")
+                                   "of the same run with --full: `device_step`; `--step device` makes it the line.")
+        if args.dump_outputs and last_frame is not None:
+            out["_outputs"] = frame_outputs(last_frame, names, args.top_n)
         if res is not None and last_frame is not None:
             # the frame IS the device result: every To cell of every rank column, all rows
             ok = True
@@ -968,6 +1047,8 @@ def run_editdistance(world, ctx, args, steps=None, warmup=None, cpu_seconds=None
                        "traffic": None, "algorithmic_int_ops_per_step": int_ops, "dp_cell_updates_per_s": cells / k4_step_s,
                        "what": "5 integer operations per to-character per 32-bit word of the from-string (bit-parallel LCS), "
                                "against 256 CU x 4 SIMD x 32 lanes x 2.4 GHz"}
+    if args.dump_outputs:
+        out["_outputs"] = topn_outputs(idx, score)
     if not args.no_cpu_baseline:
         import oracle
         oracle.build_native()
@@ -1040,6 +1121,8 @@ def run_rapidfuzz(world, ctx, args, steps=3, warmup=1, cpu_seconds=None):
                     "transport": world.kind})
     out["kernel_ms_per_step"] = {"k7_fuzz": round(k7_ms / steps, 3), "launches_per_step": k7_launches / steps}
     out["roofline"] = job.roofline(k7_ms / steps * 1e-3, INT32_PEAK_TOPS)
+    if args.dump_outputs:
+        out["_outputs"] = topn_outputs(idx, score)
     if not args.no_cpu_baseline:
         import oracle
         oracle.build_native()
@@ -1117,6 +1200,8 @@ def run_dense(world, ctx, args, steps=None, warmup=None):
                        "end_to_end_frac": flop * steps / (wall / 1.0) / 1e12 / FP32_MFMA_PEAK_TFLOPS,
                        "what": "2 n_from n_to d flops of exact fp32 products (v_mfma_f32_32x32x2_f32) over the GEMM panels' "
                                "summed launch time; end_to_end_frac = over the whole step (row top-n included)"}
+    if args.dump_outputs:
+        out["_outputs"] = topn_outputs(idx, val)
     if not args.no_cpu_baseline:
         # CPU arm + parity on a bounded random sample: float64 BLAS cosine + canonical top-n (oracle/dense.py)
         import oracle
@@ -1222,6 +1307,11 @@ def main():
                 out["config"]["rendezvous"] = "torch.distributed over gloo (host): id broadcast, barrier, max over ranks; RCCL is the library's alone"
             world.close()
     if out is not None:
+        outputs = out.pop("_outputs", None)
+        if args.dump_outputs:
+            if outputs is None:
+                raise SystemExit(f"--dump-outputs: this run ({args.config}, --step {args.step}, {args.gpus} GPU(s)) has no outputs to write")
+            write_outputs(args.dump_outputs, outputs)
         if args.small:
             out["config"]["rehearsal"] = "--small: reduced sizes, NOT the BASELINE configuration"
         print(json.dumps(out))

@@ -9,7 +9,7 @@ as "self") -> `_utils.py:104-125` (the frame).  "knn" is the one back-end of the
 this container (the dense "sklearn" branch needs 80 GB; sparse_dot_topn is not installable), and BASELINE.md §3 lists
 it as the reference arm of the headline.
 
-The GPU box has no /root/reference: the OUTPUT is committed (`headline_knn_golden.npz`, data only) together with
+The reference is not where the GPU tests run: the OUTPUT is committed (`headline_knn_golden_{0,1,2,3}.npz`, data only) with
 this script (python tests/golden/make_golden_headline.py; ~6 min on 8 vCPU).
 
 What is stored, per from-row r and rank k < 5:
@@ -95,15 +95,20 @@ def main():
         assert np.array_equal(to_none[:, k], exp < 0.001)
     self_kept = int((idx == np.arange(len(names))[:, None]).any(axis=1).sum())
     print(f"rows whose own index survived the column-0 drop: {self_kept}")
-    np.savez_compressed(os.path.join(HERE, "headline_knn_golden.npz"),
-                        idx=idx, sim=sim64.astype(np.float32), sim3=sim3, to_none=to_none,
+    arrays = dict(idx=idx, sim=sim64.astype(np.float32), sim3=sim3, to_none=to_none,
                         meta=np.array(json.dumps({
                             "call": 'TFIDF(min_similarity=0, top_n=5, cosine_method="knn").match(names)',
                             "reference": "MaartenGr/PolyFuzz v0.4.3 (/root/reference), run by tests/golden/make_golden_headline.py",
                             "sklearn": sklearn.__version__, "numpy": np.__version__,
                             "wall_s": round(wall, 1), "cores": os.cpu_count(),
                             "rows_with_self_kept": self_kept})))
-    print("wrote headline_knn_golden.npz", os.path.getsize(os.path.join(HERE, "headline_knn_golden.npz")), "bytes")
+    # four consecutive row blocks (tests/helpers.py HEADLINE_GOLDEN_PARTS): each file stays well below 1 MiB
+    parts = 4
+    rows = -(-len(names) // parts)
+    for p in range(parts):
+        path = os.path.join(HERE, f"headline_knn_golden_{p}.npz")
+        np.savez_compressed(path, **{k: (v[p * rows:(p + 1) * rows] if v.ndim else v) for k, v in arrays.items()})
+        print(f"wrote headline_knn_golden_{p}.npz", os.path.getsize(path), "bytes")
 
 
 if __name__ == "__main__":

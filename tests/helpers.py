@@ -75,12 +75,16 @@ def assert_topn_parity(idx, val, exp_idx, exp_val, oracle, a3, b3, n_col, exclud
                 f"{exp_idx[i, r]} (score {exp_val[i, r]!r})"
 
 
-# ---- the headline held to the REFERENCE's own run (tests/golden/headline_knn_golden.npz, make_golden_headline.py) -----------
+# ---- the headline held to the REFERENCE's own run (tests/golden/headline_knn_golden_*.npz, make_golden_headline.py) ---------
+
+HEADLINE_GOLDEN_PARTS = 4          # consecutive row blocks of 25 000 rows: each file stays well below 1 MiB
+
 
 def load_headline_golden():
     import os
-    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "headline_knn_golden.npz"))
-    return {k: g[k] for k in ("idx", "sim", "sim3", "to_none")}
+    d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    parts = [np.load(os.path.join(d, f"headline_knn_golden_{p}.npz")) for p in range(HEADLINE_GOLDEN_PARTS)]
+    return {k: np.concatenate([g[k] for g in parts]) for k in ("idx", "sim", "sim3", "to_none")}
 
 
 def assert_topn_equals_reference_knn(idx, val, golden, true_score, rows=None, score_tol=SCORE_TOL):

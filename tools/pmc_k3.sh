@@ -3,7 +3,7 @@
 # usage: tools/pmc_k3.sh <outdir>
 OUT=${1:-gpurun_out/pmc}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" && mkdir -p "$OUT"
-run() { rocprofv3 --pmc $2 --kernel-trace -d "$OUT/$1" -o bench -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/$1.log" 2>&1; }
+run() { rocprofv3 --pmc $2 --kernel-trace -d "$OUT/$1" -o bench -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/$1.log" 2>&1; }
 run sq1 "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA"
 run sq2 "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_INST_CYCLES_VMEM SQ_WAIT_INST_LDS"
 run sq3 "SQ_INST_LEVEL_VMEM SQ_INST_LEVEL_LDS SQ_ACTIVE_INST_VMEM SQ_INSTS_BRANCH SQ_WAVES SQ_LDS_ADDR_CONFLICT SQ_ACTIVE_INST_MISC SQ_INSTS_SMEM"

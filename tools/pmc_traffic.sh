@@ -7,7 +7,7 @@ for cfg in tfidf c2 tfidf_1m; do
   extra=""; [ $cfg = tfidf ] && extra="--no-configs --step device"
   for c in FETCH_SIZE WRITE_SIZE; do
     timeout 240 rocprofv3 --pmc $c --kernel-trace -d "$OUT/${cfg}_$c" -o bench -- python bench.py --config $cfg --steps 2 --warmup 1 \
-      --no-cpu-baseline --no-match-wall $extra > "$OUT/${cfg}_$c.log" 2>&1
+      --full --no-cpu-baseline --no-match-wall $extra > "$OUT/${cfg}_$c.log" 2>&1
     echo "$cfg $c rc=$?"
   done
 done

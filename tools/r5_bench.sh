@@ -1,10 +1,10 @@
 #!/bin/bash
-# round 5: the driver's default bench line (all configs) -> gpurun_out/r5_bench_<tag>.json + a short digest.  usage (GPU box): bash tools/r5_bench.sh [tag] [bench flags]
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"; T=${1:-a}; shift; mkdir -p gpurun_out
-timeout 900 python bench.py "$@" > gpurun_out/r5_bench_$T.json 2> gpurun_out/r5_bench_$T.err; echo "bench rc=$?"; tail -2 gpurun_out/r5_bench_$T.err
+# round 5: the driver's default bench line (--full: all configs) -> $OUT/r5_bench_<tag>.json + a short digest.  usage (GPU box): bash tools/r5_bench.sh [tag] [bench flags]
+cd "$(dirname "$0")/.."; OUT=${OUT:?set OUT to the directory the results go to}; T=${1:-a}; shift; mkdir -p "$OUT"
+timeout 900 python bench.py --full "$@" > $OUT/r5_bench_$T.json 2> $OUT/r5_bench_$T.err; echo "bench rc=$?"; tail -2 $OUT/r5_bench_$T.err
 python - <<PY
 import json
-d=json.loads(open('gpurun_out/r5_bench_$T.json').read().strip().splitlines()[-1])
+d=json.loads(open('$OUT/r5_bench_$T.json').read().strip().splitlines()[-1])
 print('value %.4g %s  ms_per_step %.4f  match_wall_ms %s  latency_top1_ms %s'%(d['value'],d['unit'],d['ms_per_step'],d.get('match_wall_ms'),d.get('latency_top1_ms')))
 print('kernel_ms', d.get('kernel_ms_per_step'))
 rf=d.get('roofline',{}); print('roofline', {k:rf.get(k) for k in ('bound','frac','frac_hbm_priced','lds_floor_ms','avg_launch_ms','symmetric_form')})

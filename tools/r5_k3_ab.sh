@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 5: the headline's K3 -- the product and variants/*.so side by side on one box (three rounds), then the K3 tests on the product
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-B="python bench.py --no-configs --steps 12 --warmup 3 --no-cpu-baseline --no-match-wall"
+B="python bench.py --full --no-configs --steps 12 --warmup 3 --no-cpu-baseline --no-match-wall"
 for rep in 1 2 3; do for lib in "" variants/*.so; do
   [ -f "$lib" ] || [ -z "$lib" ] || continue
   if [ -n "$lib" ]; then export POLYFUZZ_HIP_LIB=$PWD/$lib; else unset POLYFUZZ_HIP_LIB; fi

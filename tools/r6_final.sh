@@ -9,7 +9,7 @@ HEAD_ID=$(cat tools/.build_head 2>/dev/null) || { echo "tools/.build_head is mis
 O=gpurun_out/r06_final; rm -rf $O; mkdir -p $O; echo "$HEAD_ID" > $O/source_commit.txt
 timeout 2400 python -m pytest tests/ -m gpu -q --timeout 900 > $O/gpu_tests.log 2>&1; echo "tests rc=$?"; tail -3 $O/gpu_tests.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -2 $O/smoke.log
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 300 $O/bench.err
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 300 $O/bench.err
 timeout 1200 bash tools/profile_bench.sh $O/profile > $O/profile.log 2>&1
 timeout 900 bash tools/pmc_traffic.sh $O/pmc > $O/pmc.log 2>&1
 timeout 600 bash tools/profile_other.sh $O/other > $O/other.log 2>&1
