@@ -76,7 +76,8 @@ int pfz_event_wait(pfz_ctx *ctx, int32_t slot);
  * on = 1: every profiled kernel; on = 2: only the dominant ones (k3_cossim_topn, k4_indel, k5_gemm_panel). */
 int pfz_prof_enable(pfz_ctx *ctx, int32_t on);
 int pfz_prof_reset(pfz_ctx *ctx);
-/* total ms and launch count of kernel `name` since the last reset (blocks). */
+/* total ms and launch count of kernel `name` since the last reset (blocks).  Every form of K3 is timed as
+ * `k3_cossim_topn`; `k3_lockstep` (0 ms, a count only) says how many of those launches the lock-step form served. */
 int pfz_prof_get(pfz_ctx *ctx, const char *name, double *total_ms, int64_t *launches);
 
 /* ---- CSR matrices --------------------------------------------------------

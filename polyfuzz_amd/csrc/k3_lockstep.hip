@@ -382,6 +382,7 @@ int k3_lockstep_launch(pfz_ctx *ctx, const pfz_index *ix, const pfz_csr *A, int6
     }
 #undef PFZ_K3_LS
     PFZ_HIP(hipGetLastError());
+    prof_count(ctx, "k3_lockstep");      // (timed by the caller as k3_cossim_topn, like every form of K3: this says which form ran)
     return PFZ_OK;
 }
 

@@ -324,6 +324,11 @@ ProfScope::~ProfScope()
     pe.end.push_back(e);
 }
 
+void prof_count(pfz_ctx *ctx, const char *name)
+{
+    if (ctx->prof) ctx->prof_entries[name].launches += 1;
+}
+
 static void prof_fold(pfz_ctx *ctx, ProfEntry &pe)
 {
     for (size_t i = 0; i < pe.begin.size(); ++i) {

@@ -279,6 +279,9 @@ struct ProfScope {
     ProfScope(pfz_ctx *c, const char *n, hipStream_t on = nullptr);   // on: the stream the launch goes to (default ctx->stream)
     ~ProfScope();
 };
+// a launch counted under a name of its own while ctx->prof is on: no events, no time (pfz_prof_get: 0 ms, the count) -- which of
+// several kernels that share one timed scope served a call
+void prof_count(pfz_ctx *ctx, const char *name);
 
 // Caching device allocator of a context (pfz_api.hip).  hipMalloc/hipFree are
 // slow and hipFree synchronises the device, so blocks are size-classed and

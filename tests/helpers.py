@@ -1,4 +1,6 @@
 """Shared helpers of the parity tests (test infrastructure; may use oracle/)."""
+import contextlib
+
 import numpy as np
 
 SCORE_TOL = 1e-5      # north-star tolerance for fp32 cosine scores
@@ -44,8 +46,9 @@ def random_csr(rng, n_rows, n_cols, density, empty_rows=()):
 
 
 def assert_topn_parity(idx, val, exp_idx, exp_val, oracle, a3, b3, n_col, exclude_diag=False,
-                       max_near_tie_frac=0.01):
-    """idx/val: engine output (int32, fp32); exp_*: oracle (canonical order, float64)."""
+                       max_near_tie_frac=0.01, rows=None):
+    """idx/val: engine output (int32, fp32); exp_*: oracle (canonical order, float64).
+    rows: the from-rows of a3 that idx / val / exp_* hold, position by position (default: all of them, in order)."""
     idx = np.asarray(idx)
     val = np.asarray(val, np.float64)
     exp_idx = np.asarray(exp_idx)
@@ -58,12 +61,13 @@ def assert_topn_parity(idx, val, exp_idx, exp_val, oracle, a3, b3, n_col, exclud
     assert len(bad_rows) <= max(1, int(max_near_tie_frac * len(idx))), \
         f"{len(bad_rows)} of {len(idx)} rows differ from the oracle's indices"
     for i in bad_rows:
-        dense = oracle.cossim_dense(a3, b3, n_col, rows=(int(i), int(i) + 1))[0]
+        row = int(i) if rows is None else int(rows[i])
+        dense = oracle.cossim_dense(a3, b3, n_col, rows=(row, row + 1))[0]
         got = idx[i]
         real = got[got >= 0]
-        assert len(set(real.tolist())) == len(real), f"row {i}: duplicate indices {got}"
+        assert len(set(real.tolist())) == len(real), f"row {row}: duplicate indices {got}"
         if exclude_diag:
-            assert i not in real.tolist()
+            assert row not in real.tolist()
         for r in range(idx.shape[1]):
             if got[r] == exp_idx[i, r]:
                 continue
@@ -71,7 +75,7 @@ def assert_topn_parity(idx, val, exp_idx, exp_val, oracle, a3, b3, n_col, exclud
             # separates by less than NEAR_TIE
             s_got = dense[got[r]] if got[r] >= 0 else 0.0
             assert abs(s_got - exp_val[i, r]) < NEAR_TIE, \
-                f"row {i} rank {r}: got col {got[r]} (oracle score {s_got!r}), expected col " \
+                f"row {row} rank {r}: got col {got[r]} (oracle score {s_got!r}), expected col " \
                 f"{exp_idx[i, r]} (score {exp_val[i, r]!r})"
 
 
@@ -122,3 +126,64 @@ def assert_topn_equals_reference_knn(idx, val, golden, true_score, rows=None, sc
     # an empty cell of ours facing a real cell of the reference (or the other way round) was caught by the None test above
     return {"cells": int(idx.size), "cells_index_differs": int(len(rr)), "of_them_reference_kept_self": int(is_self.sum()),
             "max_abs_score_err": float(err.max())}
+
+
+# ---- config 3's lists under all ten fuzz scorers, the C oracle's answers (tests/golden/c3_fuzz_oracle_*.npz, make_golden_c3_fuzz.py) ----
+
+# scorer -> row stride of its fixture: every row for seven, every 10th row (0, 10, 20, ...) for the three partial_token_* scorers
+# (0.27 - 0.54 s per row on one core of the oracle: 46 minutes of eight cores for all rows)
+C3_FUZZ_SCORERS = {"ratio": 1, "QRatio": 1, "token_sort_ratio": 1, "token_set_ratio": 1, "token_ratio": 1, "partial_ratio": 1,
+                   "WRatio": 1, "partial_token_sort_ratio": 10, "partial_token_set_ratio": 10, "partial_token_ratio": 10}
+
+
+def c3_fuzz_lists():
+    """the one place the fixture's generator, its self-check and the GPU tests take the two lists from"""
+    from polyfuzz_amd import datasets
+    fl, tl = datasets.c3_lists()
+    assert len(fl) == len(tl) == 20_000 and fl[0] == "Polly Blue Eyes"
+    return fl, tl
+
+
+def lists_sha256(from_list, to_list):
+    import hashlib
+    h = hashlib.sha256()
+    for lst in (from_list, to_list):
+        h.update("\0".join(lst).encode("utf-8", "surrogatepass"))
+        h.update(b"\0\0")
+    return h.hexdigest()
+
+
+def c3_fuzz_golden_path(scorer):
+    import os
+    return os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", f"c3_fuzz_oracle_{scorer}.npz")
+
+
+def load_c3_fuzz_golden(scorer):
+    """-> (rows int64, idx int32, score float64) of the fixture; a missing file raises (a test fails on it, it does not skip)"""
+    g = np.load(c3_fuzz_golden_path(scorer))
+    stride = C3_FUZZ_SCORERS[scorer]
+    assert str(g["scorer"]) == scorer and int(g["stride"]) == stride and str(g["source"]) == "oracle"
+    rows = np.arange(0, 20_000, stride)
+    idx, score = g["idx"], g["score"]
+    assert idx.dtype == np.int32 and score.dtype == np.float64 and idx.shape == score.shape == rows.shape
+    return rows, idx, score
+
+
+# ---- which form of K3 served a call ---------------------------------------------------------------------------------------------
+
+@contextlib.contextmanager
+def lockstep_launches(ctx):
+    """with lockstep_launches(ctx) as box: ...calls...  ->  box["launches"] = how many of them k3_lockstep.hip served (every form of
+    K3 is timed as `k3_cossim_topn`; the lock-step launch counts itself as `k3_lockstep` beside it while profiling is on) and
+    box["k3"] = (ms, launches) of `k3_cossim_topn` over the same calls."""
+    box = {}
+    ctx.prof_enable(True)
+    ctx.prof_reset()
+    try:
+        yield box
+        ctx.sync()
+        ms, n = ctx.prof_get("k3_lockstep")
+        assert ms == 0.0                          # a count, not a second timer inside the timed scope
+        box["launches"], box["k3"] = n, ctx.prof_get("k3_cossim_topn")
+    finally:
+        ctx.prof_enable(False)

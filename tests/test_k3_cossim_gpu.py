@@ -525,14 +525,18 @@ def test_symmetric_switch_over_large(ctx, monkeypatch, n, expect_sym):
     names = synth.company_names(n, seed=11)
     s = _lib.DeviceStrings.upload(ctx, names)
     a = _lib.DeviceTfidf.fit(ctx, _lib.TfidfParams(3, 3, 1, 1), s, None).transform(s)
+    from tests.helpers import lockstep_launches
     monkeypatch.setenv("PFZ_K3_SYM", "0")
     monkeypatch.setenv("PFZ_K3_LOCKSTEP", "0")
-    ref = _lib.cossim_topn(ctx, _lib.DeviceIndex.build(ctx, a), a, 3, 0.0, exclude_diag=True).download()
+    with lockstep_launches(ctx) as ls_ref:
+        ref = _lib.cossim_topn(ctx, _lib.DeviceIndex.build(ctx, a), a, 3, 0.0, exclude_diag=True).download()
     monkeypatch.delenv("PFZ_K3_SYM", raising=False)
     monkeypatch.delenv("PFZ_K3_LOCKSTEP", raising=False)
     ix = _lib.DeviceIndex.build(ctx, a)
-    got = _lib.cossim_topn(ctx, ix, a, 3, 0.0, exclude_diag=True).download()
+    with lockstep_launches(ctx) as ls_got:
+        got = _lib.cossim_topn(ctx, ix, a, 3, 0.0, exclude_diag=True).download()
     assert ix.symmetric_launches()[0] == expect_sym
+    assert ls_ref["launches"] == 0 and ls_got["launches"] == 1 - expect_sym      # beyond 250 000 rows: the lock-step kernel
     np.testing.assert_array_equal(got[0], ref[0])
     np.testing.assert_array_equal(got[1], ref[1])
     # at this size the BOUND of the index' pieces (characters / 16 + one per list: ~2.0 M) is beyond the 2^20 up to

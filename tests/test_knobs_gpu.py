@@ -47,9 +47,13 @@ def test_lockstep_threshold_knob(ctx, monkeypatch):
     vec = _lib.DeviceTfidf.fit(ctx, _lib.TfidfParams(3, 3, 1, 1), t, f)
     a, b = vec.transform(f), vec.transform(t)
     ix = _lib.DeviceIndex.build(ctx, b)
-    ref = _lib.cossim_topn(ctx, ix, a, 4, 0.0).download()
+    from tests.helpers import lockstep_launches
+    with lockstep_launches(ctx) as ls_ref:
+        ref = _lib.cossim_topn(ctx, ix, a, 4, 0.0).download()
     monkeypatch.setenv("PFZ_K3_LS_MIN_TO", "1000")
-    got = _lib.cossim_topn(ctx, ix, a, 4, 0.0).download()
+    with lockstep_launches(ctx) as ls_got:
+        got = _lib.cossim_topn(ctx, ix, a, 4, 0.0).download()
+    assert ls_ref["launches"] == 0 and ls_got["launches"] == 1
     np.testing.assert_array_equal(got[0], ref[0])
     np.testing.assert_array_equal(got[1], ref[1])
 
