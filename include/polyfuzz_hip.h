@@ -338,6 +338,22 @@ void pfz_dense_free(pfz_dense *m);
 int pfz_dense_topn(pfz_ctx *ctx, const pfz_dense *from_vectors, const pfz_dense *to_vectors, int32_t ntop,
                    float lower_bound, int32_t exclude_diag, int64_t diag_offset, pfz_topn *out);
 
+/* 16-bit operands for the same operator (reference _embeddings.py:127-133 on float16 / bfloat16 embedding matrices,
+ * _utils.py:74-77,94-102): the vectors are kept as 16-bit values (half the HBM footprint) and multiplied on the 16-bit
+ * matrix cores with fp32 accumulation; the scores are the cosines (dot products) OF THE 16-BIT VECTORS, to fp32 accuracy.
+ * `dtype` is PFZ_DENSE_F16 or PFZ_DENSE_BF16.  `source` says what `vec` holds: PFZ_DENSE_SRC_SAME = n x dim 16-bit values
+ * of that type, copied as they are; PFZ_DENSE_SRC_F32 = n x dim float32 values, rounded to nearest even on the device.
+ * The width is padded with zeros to a multiple of the 64-value k-chunk.  pfz_dense_topn takes two operands of one
+ * type (PFZ_ERR_INVALID otherwise: it never converts); pfz_dense_dtype tells a handle's. */
+#define PFZ_DENSE_F32 0
+#define PFZ_DENSE_F16 1
+#define PFZ_DENSE_BF16 2
+#define PFZ_DENSE_SRC_SAME 0
+#define PFZ_DENSE_SRC_F32 1
+int pfz_dense_upload16(pfz_ctx *ctx, const void *vec, int64_t n, int64_t dim, int32_t normalize, int32_t dtype,
+                       int32_t source, pfz_dense **out);
+int pfz_dense_dtype(const pfz_dense *m, int32_t *dtype);
+
 /* ---- K6: reductions on the hot path's output --------------------------------
  * precision_recall_curve (reference polyfuzz/metrics.py:12-53): for every threshold p_k
  * (ascending, n_thresholds <= 4096) count_ge[k] = #{i : sim[i] >= p_k} and sum_ge[k] = the sum of

@@ -98,6 +98,8 @@ SIGNATURES = {
     "pfz_dense_dot_topn_host": (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_f32, c_i32,
                                                c_vp, c_vp]),
     "pfz_dense_upload": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, c_i32, P(c_vp)]),
+    "pfz_dense_upload16": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, P(c_vp)]),
+    "pfz_dense_dtype": (ctypes.c_int, [c_vp, P(c_i32)]),
     "pfz_dense_shape": (ctypes.c_int, [c_vp, P(c_i64), P(c_i64)]),
     "pfz_dense_free": (None, [c_vp]),
     "pfz_dense_topn": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_f32, c_i32, c_i64, c_vp]),
@@ -715,8 +717,33 @@ def indel_matrix(ctx, from_dev, to_dev, begin=0, end=None):
     return out
 
 
-def dense_cossim_topn_host(ctx, from_vec, to_vec, ntop, lower_bound, exclude_diag=False, normalize=True):
-    """normalize=False: raw dot products (the reference's "sparse" back-end on dense input)."""
+# compute_dtype of the dense path -> PFZ_DENSE_* (include/polyfuzz_hip.h)
+DENSE_DTYPES = {"float32": 0, "float16": 1, "bfloat16": 2}
+_DENSE_SRC_SAME, _DENSE_SRC_F32 = 0, 1
+
+
+def check_compute_dtype(compute_dtype):
+    """None / "float32": fp32 operands and the fp32 matrix cores (the default: scores of the vectors as given to 1e-5).
+    "float16" / "bfloat16": the vectors are kept as 16-bit values and multiplied on the 16-bit matrix cores (16 x the fp32
+    rate, half the memory) with fp32 accumulation.  The similarity is then that of the 16-BIT vectors, exact to fp32
+    accuracy for vectors that are 16-bit to begin with; float32 vectors are rounded first, which moves every element by
+    about 1e-3 (float16) or 1e-2 (bfloat16) relative and the scores with them -- that is why the keyword is opt-in."""
+    name = "float32" if compute_dtype is None else compute_dtype
+    if not isinstance(name, str) or name not in DENSE_DTYPES:
+        raise ValueError(f"compute_dtype must be None or one of {sorted(DENSE_DTYPES)}, got {compute_dtype!r}")
+    return name
+
+
+def dense_cossim_topn_host(ctx, from_vec, to_vec, ntop, lower_bound, exclude_diag=False, normalize=True, compute_dtype=None):
+    """normalize=False: raw dot products (the reference's "sparse" back-end on dense input).
+    compute_dtype: see check_compute_dtype -- with "float16" / "bfloat16" the scores are those of the 16-bit vectors
+    (float32 input is rounded: about 1e-3 / 1e-2 relative per element), so it is opt-in; None / "float32" is the fp32 path."""
+    if check_compute_dtype(compute_dtype) != "float32":
+        a = DeviceDense.upload(ctx, from_vec, normalize, compute_dtype)
+        b = a if to_vec is from_vec else DeviceDense.upload(ctx, to_vec, normalize, compute_dtype)
+        if a.dim != b.dim:
+            raise ValueError(f"dense cosine needs two 2-D arrays with equal width, got {(a.n, a.dim)} and {(b.n, b.dim)}")
+        return dense_topn(ctx, a, b, ntop, lower_bound, exclude_diag).download()
     a = np.ascontiguousarray(from_vec, np.float32)
     b = np.ascontiguousarray(to_vec, np.float32)
     if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1]:
@@ -730,19 +757,35 @@ def dense_cossim_topn_host(ctx, from_vec, to_vec, ntop, lower_bound, exclude_dia
 
 
 class DeviceDense(_Handle):
-    """Device-resident row-major fp32 matrix + inverse row norms (K5 operand)."""
+    """Device-resident row-major matrix (fp32, or float16 / bfloat16 values) + inverse row norms (K5 operand)."""
     _free = "pfz_dense_free"
 
     @classmethod
-    def upload(cls, ctx, vec, normalize=True):
-        a = np.ascontiguousarray(vec, np.float32)
-        if a.ndim != 2:
-            raise ValueError(f"dense vectors must be a 2-D array, got shape {a.shape}")
+    def upload(cls, ctx, vec, normalize=True, compute_dtype=None):
+        """compute_dtype None / "float32": widened to fp32 whatever `vec` holds (also a float16 array).
+        "float16": a np.float16 array is uploaded as it is, any other float array as fp32 and rounded (to nearest even) on
+        the device.  "bfloat16": a np.uint16 array is taken as raw bfloat16 bits (numpy has no such dtype), a float array is
+        rounded on the device.  The similarity is then that of the 16-bit vectors: rounding float32 vectors changes the
+        scores by about 1e-3 (float16) or 1e-2 (bfloat16) relative per element, which is why this is opt-in."""
+        name = check_compute_dtype(compute_dtype)
+        vec = np.asarray(vec)
+        if vec.ndim != 2:
+            raise ValueError(f"dense vectors must be a 2-D array, got shape {vec.shape}")
         h = c_vp()
-        check(ctx.lib.pfz_dense_upload(ctx.h, _ptr(a) if a.size else None, a.shape[0], max(a.shape[1], 1), int(bool(normalize)),
-                                       ctypes.byref(h)))
+        if name == "float32":
+            a = np.ascontiguousarray(vec, np.float32)
+            check(ctx.lib.pfz_dense_upload(ctx.h, _ptr(a) if a.size else None, a.shape[0], max(a.shape[1], 1), int(bool(normalize)),
+                                           ctypes.byref(h)))
+        else:
+            given = vec.dtype == (np.float16 if name == "float16" else np.uint16)
+            if not given and vec.dtype.kind != "f":
+                raise ValueError(f"compute_dtype={name!r} takes a float array"
+                                 + (" or raw bfloat16 bits as uint16" if name == "bfloat16" else "") + f", got {vec.dtype}")
+            a = np.ascontiguousarray(vec) if given else np.ascontiguousarray(vec, np.float32)
+            check(ctx.lib.pfz_dense_upload16(ctx.h, _ptr(a) if a.size else None, a.shape[0], max(a.shape[1], 1), int(bool(normalize)),
+                                             DENSE_DTYPES[name], _DENSE_SRC_SAME if given else _DENSE_SRC_F32, ctypes.byref(h)))
         m = cls(ctx, h)
-        m.n, m.dim, m.normalize = a.shape[0], a.shape[1], bool(normalize)
+        m.n, m.dim, m.normalize, m.dtype = a.shape[0], a.shape[1], bool(normalize), name
         return m
 
 

@@ -14,6 +14,9 @@
 //                         through two LDS buffers, and the maximum of every row over each 64-column block on the
 //                         side (M).  The score panel IS written to HBM (two panels of <= 4 GiB): at d = 768 that is
 //                         4 B per 1536 flops, far below the machine balance.
+//   k5_gemm16_panel<T>  : the same panel and block maxima from float16 / bfloat16 operands (pfz_dense_upload16, opt-in):
+//                         256x256x64 tiles, 8 waves x (4x2) v_mfma_f32_32x32x16_f16 / _bf16, fp32 accumulation; with
+//                         k5_inv_norms16 (norms of the 16-bit values) and k5_round16 (float32 input, nearest even).
 //   k5_row_topn         : wave per row; with M it selects the ntop-th largest block maximum and reads only the
 //                         blocks that reach it, without M it streams the row (float4); threshold filter, 64-bit
 //                         keys score_bits<<32 | ~col, compaction by wave-max rounds (same scheme as K3), writes
@@ -83,6 +86,81 @@ __device__ inline int block_row_slot(int lane)
 }
 
 __device__ inline float f4c(const float4 &v, int s) { return s == 0 ? v.x : s == 1 ? v.y : s == 2 ? v.z : v.w; }
+
+// The tile programs' common end: scale by both inverse norms, store the 128 x 128 tile of S, leave the block maxima in M.
+__device__ __forceinline__ void tile_epilogue(f32x16 (&acc)[2][2], const float *__restrict__ inv_a, const float *__restrict__ inv_b,
+                                              int64_t a0, int64_t a1, int64_t n_b, float *__restrict__ S, int64_t ld,
+                                              float *__restrict__ M, int64_t ldm, int64_t row0, int64_t col0, int wm, int wn, int lane)
+{
+    // Epilogue.  MFMA 32x32 accumulator r of lane l = row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31.
+    // Besides the scores, every wave leaves the maximum of each of its 64 rows over its 64 columns in M[row][col / 64]:
+    // the row top-n reads those block maxima (1/64 of the panel) and then only the few blocks that can hold a winner.
+    const int cb = (int)((col0 + wn) >> 6);
+    if (row0 + kTile <= a1) {
+        // interior tile (all but the last row tile of the last panel; ld is a whole number of tiles): the 1/|a| factors
+        // come as eight float4 loads issued together, the 64 stores go out back to back from a wave-uniform base plus
+        // one 32-bit lane offset.  (Row-by-row predicated code makes the compiler wait for EVERYTHING in flight,
+        // the previous store included, before each element: 5.5 us per tile, 13 % of a tile's MFMA time.)
+        const int uwm = __builtin_amdgcn_readfirstlane(wm), uwn = __builtin_amdgcn_readfirstlane(wn);
+        const float4 *ia = (const float4 *)(inv_a + row0 + uwm) + (lane >> 5);
+        float4 sa[2][4];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) sa[i][q] = ia[i * 8 + q * 2];
+        float sb[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int64_t col = col0 + uwn + j * 32 + (lane & 31);
+            sb[j] = col < n_b ? inv_b[col] : 0.f;
+        }
+        float *tile = S + (row0 - a0 + uwm) * ld + col0 + uwn;
+        const uint32_t lane_off = (uint32_t)(4 * (lane >> 5)) * (uint32_t)ld + (uint32_t)(lane & 31);
+        float x[32];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float f = f4c(sa[i][r / 4], r % 4);
+                float *rowp = tile + (int64_t)(i * 32 + (r & 3) + 8 * (r >> 2)) * ld;
+                const float v0 = acc[i][0][r] * f * sb[0], v1 = acc[i][1][r] * f * sb[1];
+                rowp[lane_off] = v0;
+                (rowp + 32)[lane_off] = v1;
+                x[i * 16 + r] = fmaxf(v0, v1);
+            }
+        if (M) {
+            const float m = block_row_max(x, lane);
+            const int q = block_row_slot(lane), rl = (q >> 4) * 32 + (q & 3) + 8 * ((q & 15) >> 2) + 4 * (lane >> 5);
+            M[(row0 - a0 + uwm + rl) * ldm + cb] = m;
+        }
+        return;
+    }
+    const float sb0 = col0 + wn + (lane & 31) < n_b ? inv_b[col0 + wn + (lane & 31)] : 0.f;
+    const float sb1 = col0 + wn + 32 + (lane & 31) < n_b ? inv_b[col0 + wn + 32 + (lane & 31)] : 0.f;
+    float xe[32];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int64_t row = row0 + wm + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            const bool ok = row < a1;
+            const float f = ok ? inv_a[row] : 0.f;
+            const float v0 = acc[i][0][r] * f * sb0, v1 = acc[i][1][r] * f * sb1;
+            if (ok) {
+                float *rowp = S + (row - a0) * ld + col0 + wn + (lane & 31);
+                rowp[0] = v0;
+                rowp[32] = v1;
+            }
+            xe[i * 16 + r] = ok ? fmaxf(v0, v1) : 0.f;
+        }
+    }
+    if (M) {
+        const float m = block_row_max(xe, lane);
+        const int q = block_row_slot(lane);
+        const int64_t row = row0 + wm + (q >> 4) * 32 + (q & 3) + 8 * ((q & 15) >> 2) + 4 * (lane >> 5);
+        if (row < a1) M[(row - a0) * ldm + cb] = m;
+    }
+}
 
 // The tile program for d % 32 == 0 (embedding widths: 128 ... 768 ... 4096), software-pipelined: the operands of chunk
 // c + 2 travel from HBM / L2 into registers and those of chunk c + 1 from registers into the other LDS buffer while the
@@ -205,74 +283,189 @@ __global__ __launch_bounds__(256, 2) void k5_gemm_panel_pipe(const float *__rest
         cur ^= 1;
     }
 
-    // Epilogue.  MFMA 32x32 accumulator r of lane l = row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31.
-    // Besides the scores, every wave leaves the maximum of each of its 64 rows over its 64 columns in M[row][col / 64]:
-    // the row top-n reads those block maxima (1/64 of the panel) and then only the few blocks that can hold a winner.
-    const int cb = (int)((col0 + wn) >> 6);
-    if (row0 + kTile <= a1) {
-        // interior tile (all but the last row tile of the last panel; ld is a whole number of tiles): the 1/|a| factors
-        // come as eight float4 loads issued together, the 64 stores go out back to back from a wave-uniform base plus
-        // one 32-bit lane offset.  (Row-by-row predicated code makes the compiler wait for EVERYTHING in flight,
-        // the previous store included, before each element: 5.5 us per tile, 13 % of a tile's MFMA time.)
-        const int uwm = __builtin_amdgcn_readfirstlane(wm), uwn = __builtin_amdgcn_readfirstlane(wn);
-        const float4 *ia = (const float4 *)(inv_a + row0 + uwm) + (lane >> 5);
-        float4 sa[2][4];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) sa[i][q] = ia[i * 8 + q * 2];
-        float sb[2];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int64_t col = col0 + uwn + j * 32 + (lane & 31);
-            sb[j] = col < n_b ? inv_b[col] : 0.f;
-        }
-        float *tile = S + (row0 - a0 + uwm) * ld + col0 + uwn;
-        const uint32_t lane_off = (uint32_t)(4 * (lane >> 5)) * (uint32_t)ld + (uint32_t)(lane & 31);
-        float x[32];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float f = f4c(sa[i][r / 4], r % 4);
-                float *rowp = tile + (int64_t)(i * 32 + (r & 3) + 8 * (r >> 2)) * ld;
-                const float v0 = acc[i][0][r] * f * sb[0], v1 = acc[i][1][r] * f * sb[1];
-                rowp[lane_off] = v0;
-                (rowp + 32)[lane_off] = v1;
-                x[i * 16 + r] = fmaxf(v0, v1);
-            }
-        if (M) {
-            const float m = block_row_max(x, lane);
-            const int q = block_row_slot(lane), rl = (q >> 4) * 32 + (q & 3) + 8 * ((q & 15) >> 2) + 4 * (lane >> 5);
-            M[(row0 - a0 + uwm + rl) * ldm + cb] = m;
-        }
+    tile_epilogue(acc, inv_a, inv_b, a0, a1, n_b, S, ld, M, ldm, row0, col0, wm, wn, lane);
+}
+
+// ---- 16-bit operands (float16 / bfloat16 embeddings) ----------------------------------------------------------------
+// The vectors are stored as their 16 bits; what differs between the two types is how a value widens and rounds and which
+// MFMA multiplies it.  The product of two such values is exact in fp32 and the MFMA sums in fp32: against the 16-bit
+// vectors as given the scores are as good as the fp32 kernel's.
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+struct f16 {
+    __device__ static inline float widen(uint16_t b) { return (float)__builtin_bit_cast(_Float16, b); }
+    __device__ static inline uint16_t narrow(float x) { return __builtin_bit_cast(uint16_t, (_Float16)x); }   // round to nearest even
+    __device__ static inline f32x16 mfma(const u32x4 &a, const u32x4 &b, const f32x16 &c)
+    {
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    }
+};
+struct bf16 {
+    __device__ static inline float widen(uint16_t b) { return __uint_as_float((uint32_t)b << 16); }
+    __device__ static inline uint16_t narrow(float x)
+    {
+        const uint32_t u = __float_as_uint(x);
+        if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);      // NaN stays NaN
+        return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);                       // round to nearest even
+    }
+    __device__ static inline f32x16 mfma(const u32x4 &a, const u32x4 &b, const f32x16 &c)
+    {
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+    }
+};
+
+constexpr int kTile16 = 256; // workgroup tile of the 16-bit tile program
+constexpr int kBK16 = 64;    // k-depth staged per step of the 16-bit tile program (128 B of a row, as kBK floats are)
+
+// the norm of the 16-bit values as stored: the cosine is that of the vectors the GEMM multiplies
+template <typename T>
+__global__ __launch_bounds__(256) void k5_inv_norms16(const uint16_t *__restrict__ x, int64_t n, int64_t d,
+                                                       float *__restrict__ inv, int32_t normalize)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n) return;
+    if (!normalize) {
+        if (lane == 0) inv[row] = 1.f;
         return;
     }
-    const float sb0 = col0 + wn + (lane & 31) < n_b ? inv_b[col0 + wn + (lane & 31)] : 0.f;
-    const float sb1 = col0 + wn + 32 + (lane & 31) < n_b ? inv_b[col0 + wn + 32 + (lane & 31)] : 0.f;
-    float xe[32];
+    const uint16_t *p = x + row * d;
+    double ss = 0.0;
+    for (int64_t k = lane; k < d; k += 64) {
+        const double v = (double)T::widen(p[k]);
+        ss += v * v;
+    }
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
+    for (int o = 32; o >= 1; o >>= 1) ss += __shfl_xor(ss, o, 64);
+    if (lane == 0) inv[row] = ss > 0.0 ? (float)(1.0 / sqrt(ss)) : 0.f;
+}
+
+// fp32 [n][dim] -> T [n][ld], round to nearest even, the columns beyond dim zero (16-bit compute asked for float32 input)
+template <typename T>
+__global__ __launch_bounds__(256) void k5_round16(const float *__restrict__ src, int64_t n, int64_t dim, int64_t ld,
+                                                   uint16_t *__restrict__ dst)
+{
+    const int64_t total = n * ld;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t row = i / ld, col = i - row * ld;
+        dst[i] = col < dim ? T::narrow(src[row * dim + col]) : (uint16_t)0;
+    }
+}
+
+// The tile program for 16-bit operands: v_mfma_f32_32x32x16_f16 / _bf16.  Lane (r = l & 31, h = l >> 5) holds
+// A[row r][k = 8 h .. 8 h + 7] and the same of B: both matrices are row-major [n][d] and the product is A . B^T, so every
+// fragment is eight consecutive values of one row -- one ds_read_b128, no transposed read.  A k-chunk is 64 values: the 128 B
+// of a row that 32 floats are, so the staging (8 lanes x 16 B per row), the LDS image (rows of 144 B: ds_write_b128 and
+// ds_read_b128 conflict-free, see the fp32 program) and the software pipeline (chunk c + 2 into registers, chunk c + 1 into
+// the other LDS buffer, one barrier per chunk, clamped edge rows) are those of k5_gemm_panel_pipe.  What changes is the MFMA
+// count -- a fragment feeds ONE instruction instead of four -- and with it the balance: at 128 x 128 tiles with 64 x 64 per
+// wave, the MFMAs, the LDS (one ds_read_b128 per MFMA) and the CU's 64 B / clk of global loads each need the same 1024 cycles
+// per chunk and CU, and the program ran at 0.23 of the MFMA peak (measured).  So the tile is 256 x 256:
+// 8 waves of 128 x 64 (eight accumulators), 6 fragment reads per 8 MFMAs, half the LDS stores and global bytes per flop:
+// 0.28 - 0.29.  147 456 B of LDS and 512 threads: ONE workgroup per CU, two waves per SIMD.  The epilogue sees a wave's
+// 128 x 64 as the halves wm = 0, 64 of a 128 x 128 tile.
+template <typename T>
+__global__ __launch_bounds__(512, 1) void k5_gemm16_panel(const uint16_t *__restrict__ A, const uint16_t *__restrict__ B,
+                                                           const float *__restrict__ inv_a, const float *__restrict__ inv_b,
+                                                           int64_t a0, int64_t a1, int64_t n_b, int64_t d,
+                                                           float *__restrict__ S, int64_t ld, int tiles_m, int tiles_n,
+                                                           float *__restrict__ M, int64_t ldm)
+{
+    constexpr int BK = kBK16, LD = 72, NP = 4;              // LD: LDS row pitch in 16-bit values (144 B)
+    __shared__ __attribute__((aligned(16))) uint16_t As[2][kTile16 * LD];
+    __shared__ __attribute__((aligned(16))) uint16_t Bs[2][kTile16 * LD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // workgroup -> tile: consecutive workgroup ids go round-robin over the 8 XCDs; the 32 workgroups an XCD runs at a time (one
+    // per CU) get one block of 8 x 4 tiles: 8 A + 4 B tiles (4.7 MB at d = 768) feed 32 tile products out of that XCD's L2
+    const int w = blockIdx.x, xcd = w & 7, idx = w >> 3, pos = idx & 31;
+    const int g = (idx >> 5) * 8 + xcd, bm = (tiles_m + 7) >> 3;
+    const int tm = (g % bm) * 8 + (pos & 7), tn = (g / bm) * 4 + (pos >> 3);
+    if (tm >= tiles_m || tn >= tiles_n) return;
+    const int64_t row0 = a0 + (int64_t)tm * kTile16;
+    const int64_t col0 = (int64_t)tn * kTile16;
+    // a wave owns 128 x 64 of the tile: rows 128 vr .., columns 128 vc + wn ..; as seen by the epilogue, the two 64 x 64
+    // halves wm = 0, 64 of the 128 x 128 tile (vr, vc)
+    const int vr = wave >> 2, vc = (wave >> 1) & 1, wn = (wave & 1) * 64;
+
+    f32x16 acc[2][2][2];           // [half][i][j]
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int64_t row = row0 + wm + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            const bool ok = row < a1;
-            const float f = ok ? inv_a[row] : 0.f;
-            const float v0 = acc[i][0][r] * f * sb0, v1 = acc[i][1][r] * f * sb1;
-            if (ok) {
-                float *rowp = S + (row - a0) * ld + col0 + wn + (lane & 31);
-                rowp[0] = v0;
-                rowp[32] = v1;
-            }
-            xe[i * 16 + r] = ok ? fmaxf(v0, v1) : 0.f;
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[h][i][j][r] = 0.f;
+
+    const int lr = tid >> 3, lk = (tid & 7) * 8;          // staging: 8 threads per tile row, 64 rows per pass
+    const __amdgpu_buffer_rsrc_t resA = __builtin_amdgcn_make_buffer_rsrc((void *)(A + row0 * d), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t resB = __builtin_amdgcn_make_buffer_rsrc((void *)(B + col0 * d), 0, 0x7fffffff, 0x00020000);
+    uint32_t offA[NP], offB[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {        // rows beyond the edge are clamped to the last row (their products are not stored)
+        offA[p] = (uint32_t)((min(row0 + lr + p * 64, a1 - 1) - row0) * d + lk) * 2u;
+        offB[p] = (uint32_t)((min(col0 + lr + p * 64, n_b - 1) - col0) * d + lk) * 2u;
+    }
+    u32x4 ra[NP], rb[NP];
+    auto load = [&](int p, int k) {
+        ra[p] = __builtin_amdgcn_raw_buffer_load_b128(resA, offA[p], k * 2, 0);
+        rb[p] = __builtin_amdgcn_raw_buffer_load_b128(resB, offB[p], k * 2, 0);
+    };
+    auto stage = [&](int p, int buf) {
+        *(u32x4 *)(As[buf] + (lr + p * 64) * LD + lk) = ra[p];
+        *(u32x4 *)(Bs[buf] + (lr + p * 64) * LD + lk) = rb[p];
+    };
+#pragma unroll
+    for (int p = 0; p < NP; ++p) load(p, 0);
+#pragma unroll
+    for (int p = 0; p < NP; ++p) stage(p, 0);
+    const int dk = (int)d;
+#pragma unroll
+    for (int p = 0; p < NP; ++p) load(p, min(BK, dk - BK));
+    __syncthreads();
+
+    const int frag_off = (lane & 31) * LD + 8 * (lane >> 5);
+    int cur = 0;
+    for (int k0 = 0; k0 < dk; k0 += BK) {
+        const int k2 = min(k0 + 2 * BK, dk - BK);      // (the last two chunks re-fetch the last one: no branches in the loop)
+        const uint16_t *ap = As[cur] + vr * 128 * LD + frag_off, *bp = Bs[cur] + (vc * 128 + wn) * LD + frag_off;
+        auto frag = [&](int s, u32x4 (&a)[4], u32x4 (&b)[2]) {      // MFMA step s: k = 16 s + 8 h .. + 7
+#pragma unroll
+            for (int i = 0; i < 4; ++i) a[i] = *(const u32x4 *)(ap + i * 32 * LD + 16 * s);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) b[j] = *(const u32x4 *)(bp + j * 32 * LD + 16 * s);
+        };
+        auto mfma4 = [&](const u32x4 (&a)[4], const u32x4 (&b)[2], int h) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[h][i][j] = T::mfma(a[2 * h + i], b[j], acc[h][i][j]);
+        };
+        // one operand pair per four MFMAs: items 0..3 store chunk c + 1 (in registers since the previous chunk) to the other
+        // LDS buffer, items 4..7 fetch chunk c + 2 into the registers just freed
+        auto item = [&](int it) {
+            if (it < 4) stage(it, cur ^ 1);
+            else load(it - 4, k2);
+        };
+        u32x4 fa[2][4], fb[2][2];
+        frag(0, fa[0], fb[0]);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            if (s + 1 < 4) frag(s + 1, fa[(s + 1) & 1], fb[(s + 1) & 1]);      // fragments are read one step (8 MFMAs) ahead
+            __builtin_amdgcn_sched_barrier(0);
+            mfma4(fa[s & 1], fb[s & 1], 0);
+            item(2 * s);
+            __builtin_amdgcn_sched_barrier(0);
+            mfma4(fa[s & 1], fb[s & 1], 1);
+            item(2 * s + 1);
         }
+        __syncthreads();
+        cur ^= 1;
     }
-    if (M) {
-        const float m = block_row_max(xe, lane);
-        const int q = block_row_slot(lane);
-        const int64_t row = row0 + wm + (q >> 4) * 32 + (q & 3) + 8 * ((q & 15) >> 2) + 4 * (lane >> 5);
-        if (row < a1) M[(row - a0) * ldm + cb] = m;
-    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+        tile_epilogue(acc[h], inv_a, inv_b, a0, a1, n_b, S, ld, M, ldm, row0 + vr * 128, col0 + vc * 128, h * 64, wn, lane);
 }
 
 __device__ inline uint64_t wave_max_u64_5(uint64_t v)
@@ -450,9 +643,51 @@ struct pfz_dense {
     int64_t n = 0, dim = 0;
     int64_t ld = 0;          // dim rounded up to a multiple of 32 (the GEMM's k-chunk), the extra columns are zero
     int32_t normalize = 1;
-    float *x = nullptr;      // device [n][ld] row-major
+    float *x = nullptr;      // device [n][ld] row-major (dtype == PFZ_DENSE_F32)
+    int32_t dtype = PFZ_DENSE_F32;
+    uint16_t *x16 = nullptr; // device [n][ld] row-major float16 / bfloat16 bits, ld a multiple of 64 (the 16-bit k-chunk)
     float *inv = nullptr;    // device [n]: 1 / ||row|| (1 when normalize == 0)
 };
+
+static const char *dense_dtype_name(int32_t dtype)
+{
+    return dtype == PFZ_DENSE_F16 ? "float16" : dtype == PFZ_DENSE_BF16 ? "bfloat16" : "float32";
+}
+
+template <typename T>
+static int dense_fill16(pfz_ctx *ctx, pfz_dense *m, const void *vec, int32_t source)
+{
+    const int64_t n = m->n, dim = m->dim, ld = m->ld;
+    if (source == PFZ_DENSE_SRC_F32) {
+        // float32 values: uploaded as they are, rounded (and padded) on the device
+        struct Tmp {
+            float *p = nullptr;
+            ~Tmp() { if (p) pool_free(p); }     // (stream order keeps it alive until k5_round16 is done)
+        } tmp;
+        PFZ_TRY(pool_alloc(ctx, &tmp.p, (size_t)n * (size_t)dim * sizeof(float)));
+        PFZ_TRY(copy_h2d(ctx, tmp.p, vec, (size_t)n * (size_t)dim * sizeof(float)));
+        const int64_t blocks = std::min<int64_t>((n * ld + 255) / 256, 65536);
+        hipLaunchKernelGGL(k5_round16<T>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, (const float *)tmp.p, n, dim, ld, m->x16);
+        PFZ_HIP(hipGetLastError());
+    }
+    else if (ld == dim)
+        PFZ_TRY(copy_h2d(ctx, m->x16, vec, (size_t)n * (size_t)dim * sizeof(uint16_t)));
+    else {
+        const uint16_t *v = (const uint16_t *)vec;
+        const int64_t rows_per = std::max<int64_t>(1, ((int64_t)32 << 20) / (ld * (int64_t)sizeof(uint16_t)));
+        std::vector<uint16_t> padded((size_t)std::min(rows_per, n) * (size_t)ld, (uint16_t)0);
+        for (int64_t r0 = 0; r0 < n; r0 += rows_per) {
+            const int64_t rows = std::min(rows_per, n - r0);
+            for (int64_t r = 0; r < rows; ++r)
+                std::copy(v + (r0 + r) * dim, v + (r0 + r + 1) * dim, padded.begin() + (size_t)r * (size_t)ld);
+            PFZ_TRY(copy_h2d(ctx, m->x16 + r0 * ld, padded.data(), (size_t)rows * (size_t)ld * sizeof(uint16_t)));
+        }
+    }
+    hipLaunchKernelGGL(k5_inv_norms16<T>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, ctx->stream, (const uint16_t *)m->x16, n, ld,
+                       m->inv, m->normalize);
+    PFZ_HIP(hipGetLastError());
+    return PFZ_OK;
+}
 
 extern "C" {
 
@@ -461,6 +696,7 @@ void pfz_dense_free(pfz_dense *m)
     if (!m) return;
     if (m->ctx) (void)hipSetDevice(m->ctx->device);
     if (m->x) pool_free(m->x);
+    if (m->x16) pool_free(m->x16);
     if (m->inv) pool_free(m->inv);
     delete m;
 }
@@ -505,6 +741,41 @@ int pfz_dense_upload(pfz_ctx *ctx, const float *vec, int64_t n, int64_t dim, int
     return PFZ_OK;
 }
 
+int pfz_dense_upload16(pfz_ctx *ctx, const void *vec, int64_t n, int64_t dim, int32_t normalize, int32_t dtype, int32_t source,
+                       pfz_dense **out)
+{
+    PFZ_REQUIRE(ctx && out && (n == 0 || vec), "pfz_dense_upload16: NULL argument");
+    PFZ_REQUIRE(n >= 0 && dim >= 1, "pfz_dense_upload16: bad shape %lld x %lld", (long long)n, (long long)dim);
+    PFZ_REQUIRE(dtype == PFZ_DENSE_F16 || dtype == PFZ_DENSE_BF16, "pfz_dense_upload16: dtype %d is neither PFZ_DENSE_F16 nor PFZ_DENSE_BF16",
+                dtype);
+    PFZ_REQUIRE(source == PFZ_DENSE_SRC_SAME || source == PFZ_DENSE_SRC_F32, "pfz_dense_upload16: unknown source %d", source);
+    if (n >= ((int64_t)1 << 31) - 256) {
+        set_error("pfz_dense_upload16: %lld rows exceed the int32 result indices", (long long)n);
+        return PFZ_ERR_UNSUPPORTED;
+    }
+    PFZ_HIP(hipSetDevice(ctx->device));
+    Owner<pfz_dense, pfz_dense_free> m(new pfz_dense());
+    m->ctx = ctx;
+    m->n = n;
+    m->dim = dim;
+    m->dtype = dtype;
+    m->ld = (dim + kBK16 - 1) / kBK16 * kBK16;      // zero columns up to a whole k-chunk, as in pfz_dense_upload
+    m->normalize = normalize ? 1 : 0;
+    PFZ_TRY(pool_alloc(ctx, &m->x16, (size_t)(n > 0 ? n : 1) * (size_t)m->ld * sizeof(uint16_t)));
+    PFZ_TRY(pool_alloc(ctx, &m->inv, (size_t)(n > 0 ? n : 1) * sizeof(float)));
+    if (n > 0)
+        PFZ_TRY(dtype == PFZ_DENSE_F16 ? dense_fill16<f16>(ctx, m.p, vec, source) : dense_fill16<bf16>(ctx, m.p, vec, source));
+    *out = m.release();
+    return PFZ_OK;
+}
+
+int pfz_dense_dtype(const pfz_dense *m, int32_t *dtype)
+{
+    PFZ_REQUIRE(m && dtype, "pfz_dense_dtype: NULL argument");
+    *dtype = m->dtype;
+    return PFZ_OK;
+}
+
 int pfz_dense_shape(const pfz_dense *m, int64_t *n, int64_t *dim)
 {
     PFZ_REQUIRE(m, "pfz_dense_shape: NULL matrix");
@@ -519,12 +790,14 @@ int pfz_dense_topn(pfz_ctx *ctx, const pfz_dense *from, const pfz_dense *to, int
     PFZ_REQUIRE(ctx && from && to && out, "pfz_dense_topn: NULL argument");
     PFZ_REQUIRE(from->dim == to->dim, "pfz_dense_topn: from-vectors have %lld columns, to-vectors %lld", (long long)from->dim,
                 (long long)to->dim);
+    PFZ_REQUIRE(from->dtype == to->dtype, "pfz_dense_topn: from-vectors are %s, to-vectors %s: upload both with one compute type",
+                dense_dtype_name(from->dtype), dense_dtype_name(to->dtype));
     PFZ_REQUIRE(ntop >= 1, "pfz_dense_topn: ntop must be >= 1");
     PFZ_REQUIRE(lower_bound == lower_bound, "pfz_dense_topn: lower_bound is NaN");
     constexpr int32_t kDeepPass = 1024;      // keys one pass keeps (k5_row_topn<1152>)
     PFZ_REQUIRE(out->n_rows >= from->n && out->ntop == ntop, "pfz_dense_topn: result buffer is %lldx%d, need %lldx%d",
                 (long long)out->n_rows, out->ntop, (long long)from->n, ntop);
-    const int64_t n_from = from->n, n_to = to->n, dim = from->ld;        // the padded width: a multiple of 32
+    const int64_t n_from = from->n, n_to = to->n, dim = from->ld;        // the padded width: a multiple of the type's k-chunk
     if (n_from == 0) return PFZ_OK;
     PFZ_HIP(hipSetDevice(ctx->device));
     if (lower_bound < 0.f) lower_bound = 0.f;   // non-positive similarities are "no match" (_utils.py:122-123)
@@ -571,8 +844,17 @@ int pfz_dense_topn(pfz_ctx *ctx, const pfz_dense *from, const pfz_dense *to, int
                 // 1-D grid of 8 x 8 tile blocks dealt round-robin to the XCDs (see the kernel)
                 const dim3 grid_p((unsigned)((((tiles_m + 7) / 8) * ((tiles_n + 7) / 8) + 7) / 8 * 512));
                 M = getenv("PFZ_K5_NO_BLOCK_MAX") ? nullptr : (const float *)dM[buf].p;      // A/B knob, tests
-                hipLaunchKernelGGL(k5_gemm_panel_pipe, grid_p, dim3(256), 0, ctx->stream, from->x, to->x, from->inv, to->inv, a0, a1,
-                                   n_to, dim, S, ld, tiles_m, tiles_n, (float *)M, ld / 64);
+                if (from->dtype == PFZ_DENSE_F32)
+                    hipLaunchKernelGGL(k5_gemm_panel_pipe, grid_p, dim3(256), 0, ctx->stream, from->x, to->x, from->inv, to->inv, a0, a1,
+                                       n_to, dim, S, ld, tiles_m, tiles_n, (float *)M, ld / 64);
+                else {
+                    // 256 x 256 tiles (ld is a whole number of them), blocks of 8 x 4 tiles dealt round-robin to the XCDs
+                    const int t16_m = (int)((a1 - a0 + kTile16 - 1) / kTile16), t16_n = (int)(ld / kTile16);
+                    const dim3 grid16((unsigned)((((t16_m + 7) / 8) * ((t16_n + 3) / 4) + 7) / 8 * 256));
+                    auto *gemm16 = from->dtype == PFZ_DENSE_F16 ? k5_gemm16_panel<f16> : k5_gemm16_panel<bf16>;
+                    hipLaunchKernelGGL(gemm16, grid16, dim3(512), 0, ctx->stream, (const uint16_t *)from->x16, (const uint16_t *)to->x16,
+                                       from->inv, to->inv, a0, a1, n_to, dim, S, ld, t16_m, t16_n, (float *)M, ld / 64);
+                }
             }
         }
         hipStream_t ts = two ? ctx->stream2 : ctx->stream;

@@ -32,6 +32,15 @@ class Embeddings(BaseMatcher):
                        "sklearn" / "knn" (true cosine, ignore `min_similarity`) -- the reference's
                        semantics, _utils.py:59-102 -- or "hip" (true cosine, honours `min_similarity`)
         model_id: The name of the particular instance, used when comparing models
+
+    Attribute (ours; the constructor keeps the reference's signature, tests/test_reference_interface_cpu.py):
+        compute_dtype: None / "float32" (default): fp32 operands.  "float16" / "bfloat16": the embeddings are kept as
+                       16-bit values on the device (a np.float16 array, or raw bfloat16 bits as np.uint16, is taken as it
+                       is; float32 / float64 embeddings are rounded to nearest even) and multiplied on the 16-bit matrix
+                       cores with fp32 accumulation.  The similarity is then that of the 16-bit vectors: rounding float32
+                       vectors changes the scores by about 1e-3 (float16) or 1e-2 (bfloat16) relative per element, which
+                       is why this is opt-in: `m = Embeddings(...); m.compute_dtype = "float16"`.  Anything else raises
+                       ValueError; it is kept through pickling, and the resident to-side is re-uploaded when it changes.
     """
     def __init__(self,
                  embedding_method: Optional[Callable[[List[str]], np.ndarray]] = None,
@@ -51,6 +60,17 @@ class Embeddings(BaseMatcher):
         self.embeddings_to = None
         self._dev_to = None            # _lib.DeviceDense of the to-side
         self._dev_to_normalize = None
+        self._compute_dtype = None
+        self._dev_to_dtype = None      # compute type the resident to-side was uploaded with
+
+    @property
+    def compute_dtype(self) -> Optional[str]:
+        return self._compute_dtype
+
+    @compute_dtype.setter
+    def compute_dtype(self, value: Optional[str]):
+        _lib.check_compute_dtype(value)
+        self._compute_dtype = value
 
     def match(self,
               from_list: List[str],
@@ -81,12 +101,14 @@ class Embeddings(BaseMatcher):
         # the to-side stays in HBM: match(..., re_train=False) (PolyFuzz.transform, polyfuzz.py:234-240) uploads
         # the new from-vectors only; an explicitly passed to-side is uploaded unless it IS the resident one
         stale = explicit_to and embeddings_to is not self.embeddings_to
-        if re_train or stale or self._dev_to is None or self._dev_to_normalize != normalize:
-            self._dev_to = _lib.DeviceDense.upload(ctx, np.asarray(embeddings_to), normalize)
+        dtype = _lib.check_compute_dtype(self.compute_dtype)
+        if re_train or stale or self._dev_to is None or self._dev_to_normalize != normalize or self._dev_to_dtype != dtype:
+            self._dev_to = _lib.DeviceDense.upload(ctx, np.asarray(embeddings_to), normalize, dtype)
             self._dev_to_normalize = normalize
+            self._dev_to_dtype = dtype
         self_match = to_list is None
         same = self_match and embeddings_to is embeddings_from
-        from_dev = self._dev_to if same else _lib.DeviceDense.upload(ctx, np.asarray(embeddings_from), normalize)
+        from_dev = self._dev_to if same else _lib.DeviceDense.upload(ctx, np.asarray(embeddings_from), normalize, dtype)
         if from_dev.dim != self._dev_to.dim:
             raise ValueError(f"dense cosine needs two 2-D arrays with equal width, got {from_dev.dim} and {self._dev_to.dim}")
         top_n = clip_top_n(self.top_n, to_list)
@@ -100,6 +122,7 @@ class Embeddings(BaseMatcher):
 
     def __setstate__(self, state):
         self.__dict__.update(state)
+        self.__dict__.setdefault("_compute_dtype", None)      # (pickled before the keyword existed)
         self._dev_to = None
 
     def _embed(self, strings: List[str]) -> np.ndarray:

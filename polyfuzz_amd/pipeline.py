@@ -286,15 +286,18 @@ class DenseMatchJob:
     """Device-resident dense cosine top-n (K5) of a row shard of from-vectors against replicated to-vectors
     (reference _embeddings.py:127-133 -> _utils.py:74-77,94-102 on ready-made embeddings; BASELINE config 5:
     500k x 500k x 768 on 8 GPUs = 62.5k from-rows per rank).  Shards are independent; the only exchange is the
-    all-gather of the padded per-shard top-n blocks."""
+    all-gather of the padded per-shard top-n blocks.
+    compute_dtype "float16" / "bfloat16": both operands are kept as 16-bit values and multiplied on the 16-bit matrix cores
+    (_lib.check_compute_dtype): the similarity is that of the 16-bit vectors, float32 input is rounded (about 1e-3 / 1e-2
+    relative per element), so it is opt-in."""
 
     def __init__(self, ctx, from_shard, to_vectors, top_n=1, min_similarity=0.0, normalize=True, comm=None,
-                 self_match=False, shard_offset=0, rows_per_rank=None):
+                 self_match=False, shard_offset=0, rows_per_rank=None, compute_dtype=None):
         self.ctx, self.comm = ctx, comm
         self.top_n, self.min_similarity = int(top_n), float(min_similarity)
         self.self_match, self.shard_offset = bool(self_match), int(shard_offset)
-        self.from_dev = _lib.DeviceDense.upload(ctx, from_shard, normalize)
-        self.to_dev = self.from_dev if to_vectors is None else _lib.DeviceDense.upload(ctx, to_vectors, normalize)
+        self.from_dev = _lib.DeviceDense.upload(ctx, from_shard, normalize, compute_dtype)
+        self.to_dev = self.from_dev if to_vectors is None else _lib.DeviceDense.upload(ctx, to_vectors, normalize, compute_dtype)
         if to_vectors is None and (not self.self_match or self.shard_offset != 0):
             raise ValueError("to_vectors=None means a whole-matrix self-match (self_match=True, shard_offset=0)")
         self.n_from, self.n_to = self.from_dev.n, self.to_dev.n

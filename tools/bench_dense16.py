@@ -1,0 +1,95 @@
+"""K5 with fp32, float16 and bfloat16 operands on one panel's worth of BASELINE configuration 5, in one process.
+
+usage: python tools/bench_dense16.py [--rows 4096] [--to 500000] [--dim 768] [--top-n 5] [--repeats 7] [--out FILE]
+
+Seeded unit-norm random-normal vectors, device-resident operands (pipeline.DenseMatchJob), top-5.  Every arm is warmed up
+and then timed over `repeats` steps with device events (pfz_event_*), one pair per step; a further profiled pass
+(pfz_prof_*) gives the GEMM's and the row top-n's share.  The fp32 arm is the baseline: the fp32 tile program of the same
+build, on the same data, in the same run.  Roofline figures per arm: the fraction of the 16-bit MFMA peak (2.5 PF; the
+fp32 arm also against its own 157 TF) and the time the fp32 score panel alone takes at 6.3 TB/s.
+Prints one JSON object; --out also writes it to a file.  Run it under a time limit (timeout 600 ...)."""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+
+PEAK16, PEAK32, HBM = 2.5e15, 157e12, 6.3e12
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=4096)
+    ap.add_argument("--to", type=int, default=500_000)
+    ap.add_argument("--dim", type=int, default=768)
+    ap.add_argument("--top-n", type=int, default=5)
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if args.repeats < 5:
+        ap.error("--repeats must be at least 5")
+    import polyfuzz_amd
+    from polyfuzz_amd import pipeline
+    ctx = polyfuzz_amd.Context.default()
+
+    rng = np.random.default_rng(5)
+    def unit(n):
+        v = rng.standard_normal((n, args.dim), dtype=np.float32)
+        v /= np.sqrt((v.astype(np.float64) ** 2).sum(1))[:, None].astype(np.float32)
+        return v
+    a, b = unit(args.rows), unit(args.to)
+    flop = 2.0 * args.rows * args.to * args.dim
+    panel_bytes = 4.0 * args.rows * args.to
+    res = {"shape": [args.rows, args.to, args.dim], "top_n": args.top_n, "repeats": args.repeats, "device": ctx.info()["name"],
+           "data": "seeded unit-norm random normal", "flop": flop, "panel_write_ms_at_6.3TB/s": panel_bytes / HBM * 1e3, "arms": {}}
+    top1 = {}
+    for arm, dtype in (("fp32", None), ("f16", "float16"), ("bf16", "bfloat16")):
+        job = pipeline.DenseMatchJob(ctx, a, b, top_n=args.top_n, compute_dtype=dtype)
+        for _ in range(2):                        # warm-up: code objects, the pool's panels, clocks
+            job.step()
+        ctx.sync()
+        ms = []
+        for _ in range(args.repeats):
+            ctx.event_record(0)
+            job.step()
+            ctx.event_record(1)
+            ctx.sync()
+            ms.append(ctx.event_elapsed_ms(0, 1))
+        ctx.prof_enable(True)
+        ctx.prof_reset()
+        out = job.step()
+        ctx.sync()
+        gemm_ms, n_panels = ctx.prof_get("k5_gemm_panel")
+        topn_ms, _ = ctx.prof_get("k5_row_topn")
+        ctx.prof_enable(False)
+        idx, _ = out.download()
+        top1[arm] = idx[:, 0].copy()
+        med = float(np.median(ms))
+        res["arms"][arm] = {
+            "ms_per_step_median": med, "ms_min": float(min(ms)), "ms_max": float(max(ms)), "ms_all": [round(x, 3) for x in ms],
+            "flop_per_s": flop / (med * 1e-3), "gemm_ms": gemm_ms, "row_topn_ms": topn_ms, "panels": n_panels,
+            "gemm_share": gemm_ms / (gemm_ms + topn_ms), "row_topn_share": topn_ms / (gemm_ms + topn_ms),
+            "gemm_flop_per_s": flop / (gemm_ms * 1e-3), "gemm_fraction_of_2.5PF": flop / (gemm_ms * 1e-3) / PEAK16,
+            "gemm_over_panel_write_time": gemm_ms / (panel_bytes / HBM * 1e3)}
+        if arm == "fp32":
+            res["arms"][arm]["gemm_fraction_of_fp32_peak_157TF"] = flop / (gemm_ms * 1e-3) / PEAK32
+        del job, out
+    base = res["arms"]["fp32"]
+    for arm in ("f16", "bf16"):
+        r = res["arms"][arm]
+        r["speedup_over_fp32"] = base["ms_per_step_median"] / r["ms_per_step_median"]
+        # faster by more than the spread of the repeats: the slowest 16-bit step against the fastest fp32 step
+        r["beats_fp32_beyond_spread"] = bool(r["ms_max"] < base["ms_min"])
+        r["top1_agrees_with_fp32_rows"] = int((top1[arm] == top1["fp32"]).sum())
+    print(json.dumps(res))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+    return 0 if all(res["arms"][k]["beats_fp32_beyond_spread"] for k in ("f16", "bf16")) else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
