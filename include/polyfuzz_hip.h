@@ -57,6 +57,8 @@ void pfz_ctx_destroy(pfz_ctx *ctx);
 int pfz_ctx_sync(pfz_ctx *ctx);
 /* device properties of the context: name (<=255 chars), CU count, HBM bytes */
 int pfz_ctx_info(pfz_ctx *ctx, char *name256, int32_t *n_cu, int64_t *hbm_bytes);
+/* the context's caching allocator: bytes in blocks that handles and running calls hold, bytes it keeps for re-use */
+int pfz_pool_stats(pfz_ctx *ctx, int64_t *live_bytes, int64_t *cached_bytes);
 
 /* HIP-event timers on the context's stream (used by bench.py for the live
  * per-kernel timing the roofline is computed from).  slot in [0, 64). */

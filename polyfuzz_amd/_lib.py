@@ -43,6 +43,7 @@ SIGNATURES = {
     "pfz_ctx_destroy": (None, [c_vp]),
     "pfz_ctx_sync": (ctypes.c_int, [c_vp]),
     "pfz_ctx_info": (ctypes.c_int, [c_vp, ctypes.c_char_p, P(c_i32), P(c_i64)]),
+    "pfz_pool_stats": (ctypes.c_int, [c_vp, P(c_i64), P(c_i64)]),
     "pfz_event_record": (ctypes.c_int, [c_vp, c_i32]),
     "pfz_event_elapsed_ms": (ctypes.c_int, [c_vp, c_i32, c_i32, P(c_f32)]),
     "pfz_prof_enable": (ctypes.c_int, [c_vp, c_i32]),
@@ -207,6 +208,12 @@ class Context:
         ncu, mem = c_i32(), c_i64()
         check(self.lib.pfz_ctx_info(self.h, name, ctypes.byref(ncu), ctypes.byref(mem)))
         return {"name": name.value.decode(), "n_cu": ncu.value, "hbm_bytes": mem.value}
+
+    def pool_stats(self):
+        """(live_bytes, cached_bytes) of the context's caching device allocator"""
+        live, cached = c_i64(), c_i64()
+        check(self.lib.pfz_pool_stats(self.h, ctypes.byref(live), ctypes.byref(cached)))
+        return live.value, cached.value
 
     # timers ---------------------------------------------------------------
     def event_record(self, slot):

@@ -952,6 +952,9 @@ __global__ __launch_bounds__(256) void k_copy_i32(const int32_t *__restrict__ sr
 // ---------------------------------------------------------------------------
 static inline unsigned grid_for(int64_t n, int per_block = 256) { return (unsigned)((n + per_block - 1) / per_block); }
 
+// PFZ_K1_TWO_LISTS=0: the second list never in the same launch (extraction, rows, histograms: they must agree)
+static inline bool k1_two_lists_allowed() { const char *k = knob_str(knob::K1_TWO_LISTS); return !(k && atoi(k) == 0); }
+
 static int bits_for(uint64_t max_value)
 {
     int b = 1;
@@ -988,19 +991,18 @@ static int run_extract(pfz_ctx *ctx, const pfz_tfidf *v, pfz_strings *s, bool ma
     ProfScope ps(ctx, "k1_extract");
     // a wave per string (a lane per character) when every string fits the wave's symbol line; PFZ_K1_EXTRACT=thread forces
     // the thread-per-string kernel (tests)
-    const char *which = getenv("PFZ_K1_EXTRACT");
+    const char *which = knob_str(knob::K1_EXTRACT);
     const bool wave = s->max_len <= kWaveMaxLen && (which ? which[0] == 'w' : s->n <= 32768);
     // (10 000 + 10 000 names, both launches: thread per string 0.119 ms; a wave per string with 16 / 32 / 64 / 128 strings per
     // workgroup 0.091 / 0.068 / 0.077 / 0.104 ms.  At 100 000 strings the thread-per-string kernel wins, 0.071 against 0.115 ms:
     // a wave's strings are a chain of dependent LDS round trips, and there the chip is full of threads anyway)
     int per_wg = 32;
-    if (const char *e = getenv("PFZ_K1_WAVE_STRINGS")) per_wg = std::max(4, std::min(kWaveStringsMax, atoi(e)));
+    if (const char *e = knob_str(knob::K1_WAVE_STRINGS)) per_wg = std::max(4, std::min(kWaveStringsMax, atoi(e)));
     // the second list in the same launch (PFZ_K1_TWO_LISTS=0: never -- tests, A/B)
     ListB B;
     unsigned grid_b = 0;
-    const char *two_knob = getenv("PFZ_K1_TWO_LISTS");
     if (sb && sb_done && wave && sb->n > 0 && sb->n <= 32768 && sb->max_len <= kWaveMaxLen && sb->char_width == s->char_width &&
-        !(which && which[0] != 'w') && !(two_knob && atoi(two_knob) == 0)) {
+        !(which && which[0] != 'w') && k1_two_lists_allowed()) {
         PFZ_TRY(prepare_slots(ctx, v, sb));
         B.chars = sb->chars;
         B.off = sb->offsets;
@@ -1012,7 +1014,7 @@ static int run_extract(pfz_ctx *ctx, const pfz_tfidf *v, pfz_strings *s, bool ma
         *sb_done = true;
     }
     // a transform of a list the wave kernel takes: extraction and the short rows in ONE launch (see k_extract_wave<.., ROWS>)
-    const char *fuse_knob = getenv("PFZ_K1_FUSE_ROWS");      // (tests: 0 = two launches)
+    const char *fuse_knob = knob_str(knob::K1_FUSE_ROWS);      // (tests: 0 = two launches)
     if (rows_done) *rows_done = false;
     if (rows_done && !mark && wave && !(fuse_knob && atoi(fuse_knob) == 0)) {
         VocabView V{v->bitmap, v->prefix, v->vcodes, v->vocab};
@@ -1140,15 +1142,12 @@ static int64_t vocab_bound(int64_t a, int lo, int hi)
 static int build_sorted_vocab(pfz_ctx *ctx, pfz_tfidf *v, pfz_strings *const lists[2])
 {
     const int R = v->params.ngram_hi - v->params.ngram_lo + 1;
-    struct Tmp {
-        void *p = nullptr;
-        ~Tmp() { if (p) pool_free(p); }
-    } code_off[2], gathered, sorted, flags;
+    DevBuf code_off[2], gathered, sorted, flags;
     int64_t base[2] = {0, 0}, total = 0;
     for (int li = 0; li < 2; ++li) {
         pfz_strings *s = lists[li];
         if (!s || s->n == 0) continue;
-        PFZ_TRY(pool_alloc(ctx, &code_off[li].p, (size_t)(s->n + 1) * sizeof(int32_t)));
+        PFZ_TRY(code_off[li].alloc(ctx, (size_t)(s->n + 1) * sizeof(int32_t)));
         hipLaunchKernelGGL(k_copy_i32, dim3(grid_for(s->n)), dim3(256), 0, ctx->stream, s->row_cnt, s->n, (int32_t *)code_off[li].p);
         PFZ_TRY(exclusive_scan_i32(ctx, (int32_t *)code_off[li].p, s->n));
         int32_t t = 0;
@@ -1163,9 +1162,9 @@ static int build_sorted_vocab(pfz_ctx *ctx, pfz_tfidf *v, pfz_strings *const lis
         set_error("pfz_tfidf_fit: %lld n-gram occurrences exceed the int32 layout of the sorted-vocabulary path", (long long)total);
         return PFZ_ERR_UNSUPPORTED;
     }
-    PFZ_TRY(pool_alloc(ctx, &gathered.p, (size_t)total * sizeof(uint64_t)));
-    PFZ_TRY(pool_alloc(ctx, &sorted.p, (size_t)sort_codes_capacity(total) * sizeof(uint64_t)));
-    PFZ_TRY(pool_alloc(ctx, &flags.p, (size_t)(total + 1) * sizeof(int32_t)));
+    PFZ_TRY(gathered.alloc(ctx, (size_t)total * sizeof(uint64_t)));
+    PFZ_TRY(sorted.alloc(ctx, (size_t)sort_codes_capacity(total) * sizeof(uint64_t)));
+    PFZ_TRY(flags.alloc(ctx, (size_t)(total + 1) * sizeof(int32_t)));
     for (int li = 0; li < 2; ++li) {
         pfz_strings *s = lists[li];
         if (!s || s->n == 0) continue;
@@ -1194,11 +1193,8 @@ static int build_sorted_vocab(pfz_ctx *ctx, pfz_tfidf *v, pfz_strings *const lis
 static int merge_sorted_vocab(pfz_ctx *ctx, pfz_comm *comm, pfz_tfidf *v)
 {
     const int world = comm_world(comm);
-    struct Tmp {
-        void *p = nullptr;
-        ~Tmp() { if (p) pool_free(p); }
-    } sizes, send, gathered, sorted, flags;
-    PFZ_TRY(pool_alloc(ctx, &sizes.p, (size_t)(world + 1) * sizeof(int64_t)));
+    DevBuf sizes, send, gathered, sorted, flags;
+    PFZ_TRY(sizes.alloc(ctx, (size_t)(world + 1) * sizeof(int64_t)));
     const int64_t mine = v->vocab;
     PFZ_TRY(copy_h2d(ctx, (int64_t *)sizes.p + world, &mine, sizeof(int64_t)));
     PFZ_TRY(comm_allgather_bytes(comm, (int64_t *)sizes.p + world, sizes.p, sizeof(int64_t)));
@@ -1209,7 +1205,7 @@ static int merge_sorted_vocab(pfz_ctx *ctx, pfz_comm *comm, pfz_tfidf *v)
         longest = std::max(longest, x);
         total += x;
     }
-    Tmp old_codes;                        // this rank's own codes: released when the merge is enqueued
+    DevBuf old_codes;                      // this rank's own codes: released when the merge is enqueued
     old_codes.p = v->vcodes;
     v->vcodes = nullptr;
     v->vocab = 0;
@@ -1220,13 +1216,13 @@ static int merge_sorted_vocab(pfz_ctx *ctx, pfz_comm *comm, pfz_tfidf *v)
         return PFZ_ERR_UNSUPPORTED;
     }
     const int64_t padded = (int64_t)world * longest;
-    PFZ_TRY(pool_alloc(ctx, &send.p, (size_t)longest * sizeof(uint64_t)));
+    PFZ_TRY(send.alloc(ctx, (size_t)longest * sizeof(uint64_t)));
     PFZ_HIP(hipMemsetAsync(send.p, 0xff, (size_t)longest * sizeof(uint64_t), ctx->stream));
     if (mine > 0) PFZ_HIP(hipMemcpyAsync(send.p, old_codes.p, (size_t)mine * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
-    PFZ_TRY(pool_alloc(ctx, &gathered.p, (size_t)padded * sizeof(uint64_t)));
+    PFZ_TRY(gathered.alloc(ctx, (size_t)padded * sizeof(uint64_t)));
     PFZ_TRY(comm_allgather_bytes(comm, send.p, gathered.p, (size_t)longest * sizeof(uint64_t)));
-    PFZ_TRY(pool_alloc(ctx, &sorted.p, (size_t)sort_codes_capacity(padded) * sizeof(uint64_t)));
-    PFZ_TRY(pool_alloc(ctx, &flags.p, (size_t)(total + 1) * sizeof(int32_t)));
+    PFZ_TRY(sorted.alloc(ctx, (size_t)sort_codes_capacity(padded) * sizeof(uint64_t)));
+    PFZ_TRY(flags.alloc(ctx, (size_t)(total + 1) * sizeof(int32_t)));
     PFZ_TRY(sort_codes_u64(ctx, (const uint64_t *)gathered.p, (uint64_t *)sorted.p, padded));
     // (the first `total` keys are the real ones: a real all-ones code would be among them, the padding behind)
     hipLaunchKernelGGL(k_flag_heads, dim3(grid_for(total)), dim3(256), 0, ctx->stream, (const uint64_t *)sorted.p, total,
@@ -1401,11 +1397,8 @@ static int fit_impl(pfz_ctx *ctx, pfz_comm *comm, const pfz_tfidf_params *params
     // the n-gram cache lives inside the (otherwise read-only) string lists
     pfz_strings *lists[2] = {const_cast<pfz_strings *>(docs_a_c), const_cast<pfz_strings *>(docs_b_c)};
     if (lists[0] == lists[1]) lists[1] = nullptr;
-    pfz_tfidf *v = new pfz_tfidf();
-    struct Guard {
-        pfz_tfidf *p;
-        ~Guard() { if (p) pfz_tfidf_free(p); }
-    } guard{v};
+    Owner<pfz_tfidf, pfz_tfidf_free> guard(new pfz_tfidf());
+    pfz_tfidf *v = guard.p;
     v->ctx = ctx;
     v->params = *params;
     v->gen = g_gen.fetch_add(1);
@@ -1488,11 +1481,10 @@ static int fit_impl(pfz_ctx *ctx, pfz_comm *comm, const pfz_tfidf_params *params
     if (!sorted_vocab) {
         PFZ_TRY(build_prefix(ctx, v, &vsize));
         const int64_t a_syms = params->clean ? 37 : (int64_t)v->alphabet.size() + 1;
-        const bool small = vocab_bound(a_syms, params->ngram_lo, params->ngram_hi) <= 2 * (int64_t)kHistWords && !getenv("PFZ_NO_LDS_HIST");
+        const bool small = lds_hist_fits(vocab_bound(a_syms, params->ngram_lo, params->ngram_hi));
         int rc = PFZ_OK;
         if (small && world == 1) {
-            const char *two_knob = getenv("PFZ_K1_TWO_LISTS");
-            if (lists[0] && lists[1] && !(two_knob && atoi(two_knob) == 0)) {
+            if (lists[0] && lists[1] && k1_two_lists_allowed()) {
                 rc = run_rows(ctx, v, lists[0], DfSink{nullptr, 0}, false, lists[1]);
             } else {
                 for (pfz_strings *s : lists)
@@ -1515,29 +1507,25 @@ static int fit_impl(pfz_ctx *ctx, pfz_comm *comm, const pfz_tfidf_params *params
     PFZ_TRY(pool_alloc(ctx, &v->idf, (size_t)v->vocab * sizeof(double)));
     // document frequencies: LDS histograms per kHistRows strings when the vocabulary fits one
     // (every realistic case), else sharded global counters -- up to 32 per n-gram, at most 64 Mi in total
-    const bool lds_hist = v->vocab <= 2 * (int64_t)kHistWords && !getenv("PFZ_NO_LDS_HIST");   // env: tests
+    const bool lds_hist = lds_hist_fits(v->vocab);
     int df_shift = 5;
     while (df_shift > 0 && (v->vocab << df_shift) > ((int64_t)64 << 20)) --df_shift;
     const int32_t words = (int32_t)((v->vocab + 1) / 2);
     int64_t chunks = 0;
     for (int li = 0; li < 2; ++li)
         if (lists[li] && ((li == 1) || rank == 0 || world == 1)) chunks += (lists[li]->n + kHistRows - 1) / kHistRows;
-    int32_t *df_sh = nullptr;   // sharded counters, or the partial histograms
+    DevBuf sh_guard;            // sharded counters, or the partial histograms
     const size_t df_sh_bytes = lds_hist ? (size_t)(chunks > 0 ? chunks : 1) * (size_t)words * sizeof(uint32_t)
                                         : (size_t)(v->vocab << df_shift) * sizeof(int32_t);
-    PFZ_TRY(pool_alloc(ctx, &df_sh, df_sh_bytes));
-    struct ShGuard {
-        int32_t *p;
-        ~ShGuard() { pool_free(p); }
-    } sh_guard{df_sh};
+    PFZ_TRY(sh_guard.alloc(ctx, df_sh_bytes));
+    int32_t *const df_sh = sh_guard.as<int32_t>();
     if (!lds_hist) PFZ_HIP(hipMemsetAsync(df_sh, 0, df_sh_bytes, ctx->stream));
     v->n_docs = 0;
     int64_t local_docs = 0, chunk0 = 0;
     const int R = v->params.ngram_hi - v->params.ngram_lo + 1;
     // (both lists' histograms in one launch where both count and the rows are done: the second list's chunks follow the first's)
-    const char *two_knob = getenv("PFZ_K1_TWO_LISTS");
     const bool hist_both = world == 1 && rows_done && lds_hist && lists[0] && lists[1] && lists[0]->n > 0 && lists[1]->n > 0 &&
-                           !(two_knob && atoi(two_knob) == 0);
+                           k1_two_lists_allowed();
     if (hist_both) {
         pfz_strings *a = lists[0], *b = lists[1];
         const int64_t nch_a = (a->n + kHistRows - 1) / kHistRows, nch_b = (b->n + kHistRows - 1) / kHistRows;
@@ -1578,25 +1566,20 @@ static int fit_impl(pfz_ctx *ctx, pfz_comm *comm, const pfz_tfidf_params *params
     v->n_docs = local_docs;
     if (world > 1) {
         PFZ_TRY(comm_allreduce_sum_i32(comm, v->df, (size_t)v->vocab));
-        int64_t *d_n = nullptr;
-        PFZ_TRY(pool_alloc(ctx, &d_n, sizeof(int64_t)));
-        hipError_t e = hipMemcpyAsync(d_n, &local_docs, sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream);
-        int rc = PFZ_OK;
-        if (e == hipSuccess) rc = comm_allreduce_sum_i64(comm, d_n, 1);
+        DevBuf d_n;
+        PFZ_TRY(d_n.alloc(ctx, sizeof(int64_t)));
+        PFZ_HIP(hipMemcpyAsync(d_n.p, &local_docs, sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+        PFZ_TRY(comm_allreduce_sum_i64(comm, d_n.as<int64_t>(), 1));
         int64_t total = 0;
-        if (e == hipSuccess && rc == PFZ_OK) e = hipMemcpyAsync(&total, d_n, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && rc == PFZ_OK) e = hipStreamSynchronize(ctx->stream);
-        pool_free(d_n);
-        PFZ_TRY(rc);
-        PFZ_HIP(e);
+        PFZ_HIP(hipMemcpyAsync(&total, d_n.p, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+        PFZ_HIP(hipStreamSynchronize(ctx->stream));
         v->n_docs = total;
     }
     if (!idf_fused)
         hipLaunchKernelGGL(k_idf, dim3(grid_for(v->vocab)), dim3(256), 0, ctx->stream, v->df, v->vocab, (double)v->n_docs,
                            v->idf);
     PFZ_HIP(hipGetLastError());
-    guard.p = nullptr;
-    *out = v;
+    *out = guard.release();
     return PFZ_OK;
 }
 
@@ -1656,7 +1639,7 @@ int pfz_tfidf_transform(pfz_ctx *ctx, const pfz_tfidf *v, const pfz_strings *doc
     PFZ_TRY(pool_alloc(ctx, &m->data, (size_t)cap * sizeof(float)));
     if (s->n > 0) {
         const int32_t *row_nnz = s->row_cnt + (s->n + 1);
-        const char *knob = getenv("PFZ_K2_SELF_SCAN");      // (tests: 0 = the long-list path on short lists too)
+        const char *knob = knob_str(knob::K2_SELF_SCAN);      // (tests: 0 = the long-list path on short lists too)
         const bool no_self_scan = knob && atoi(knob) == 0;
         if (s->n <= kSelfScanRows && !no_self_scan) {
             PFZ_TRY(lazy_acquire(ctx, &m->nnz_lazy));
@@ -1698,14 +1681,12 @@ int pfz_tfidf_export(pfz_ctx *ctx, const pfz_tfidf *v, uint32_t *ngrams, double 
         if (v->vcodes) {
             PFZ_HIP(hipMemcpy(codes.data(), v->vcodes, codes.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
         } else {
-            uint64_t *d_codes = nullptr;
-            PFZ_TRY(pool_alloc(ctx, &d_codes, (size_t)v->vocab * sizeof(uint64_t)));
+            DevBuf d_codes;
+            PFZ_TRY(d_codes.alloc(ctx, (size_t)v->vocab * sizeof(uint64_t)));
             hipLaunchKernelGGL(k_export_codes, dim3(grid_for(v->n_groups)), dim3(256), 0, ctx->stream, v->bitmap, v->prefix,
-                               v->n_groups, d_codes);
-            hipError_t e = hipMemcpyAsync(codes.data(), d_codes, codes.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            pool_free(d_codes);
-            PFZ_HIP(e);
+                               v->n_groups, d_codes.as<uint64_t>());
+            PFZ_HIP(hipMemcpyAsync(codes.data(), d_codes.p, codes.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+            PFZ_HIP(hipStreamSynchronize(ctx->stream));
         }
         const int hi = v->params.ngram_hi, w = v->bits_per_char;
         const uint64_t cmask = (1ull << w) - 1ull;
@@ -1726,11 +1707,8 @@ int pfz_tfidf_import(pfz_ctx *ctx, const pfz_tfidf_params *params, int64_t vocab
     PFZ_REQUIRE(ctx && out && ngrams && idf && vocab > 0, "pfz_tfidf_import: bad arguments");
     PFZ_TRY(check_params(params));
     PFZ_HIP(hipSetDevice(ctx->device));
-    pfz_tfidf *v = new pfz_tfidf();
-    struct Guard {
-        pfz_tfidf *p;
-        ~Guard() { if (p) pfz_tfidf_free(p); }
-    } guard{v};
+    Owner<pfz_tfidf, pfz_tfidf_free> guard(new pfz_tfidf());
+    pfz_tfidf *v = guard.p;
     v->ctx = ctx;
     v->params = *params;
     v->gen = g_gen.fetch_add(1);
@@ -1779,15 +1757,13 @@ int pfz_tfidf_import(pfz_ctx *ctx, const pfz_tfidf_params *params, int64_t vocab
         v->vocab = vocab;
     } else {
         PFZ_TRY(alloc_vocab_space(ctx, v));
-        uint64_t *d_codes = nullptr;
-        PFZ_TRY(pool_alloc(ctx, &d_codes, (size_t)vocab * sizeof(uint64_t)));
-        hipError_t e = hipMemcpyAsync(d_codes, codes.data(), (size_t)vocab * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_set_bits, dim3(grid_for(vocab)), dim3(256), 0, ctx->stream, d_codes, vocab, v->bitmap);
-            e = hipStreamSynchronize(ctx->stream);
+        {
+            DevBuf d_codes;
+            PFZ_TRY(d_codes.alloc(ctx, (size_t)vocab * sizeof(uint64_t)));
+            PFZ_HIP(hipMemcpyAsync(d_codes.p, codes.data(), (size_t)vocab * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+            hipLaunchKernelGGL(k_set_bits, dim3(grid_for(vocab)), dim3(256), 0, ctx->stream, d_codes.as<uint64_t>(), vocab, v->bitmap);
+            PFZ_HIP(hipStreamSynchronize(ctx->stream));
         }
-        pool_free(d_codes);
-        PFZ_HIP(e);
         LazyI32 vsize;
         PFZ_TRY(build_prefix(ctx, v, &vsize));
         int32_t total = 0;
@@ -1800,8 +1776,7 @@ int pfz_tfidf_import(pfz_ctx *ctx, const pfz_tfidf_params *params, int64_t vocab
     PFZ_HIP(hipMemsetAsync(v->df, 0, (size_t)vocab * sizeof(int32_t), ctx->stream));
     PFZ_HIP(hipMemcpyAsync(v->idf, idf, (size_t)vocab * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     PFZ_HIP(hipStreamSynchronize(ctx->stream));
-    guard.p = nullptr;
-    *out = v;
+    *out = guard.release();
     return PFZ_OK;
 }
 

@@ -518,12 +518,6 @@ __global__ __launch_bounds__(256) void k_topn_place(const int32_t *__restrict__ 
     out_val[r * ntop + col0 + c] = t_val[i];
 }
 
-static int env_int(const char *name, int dflt)
-{
-    const char *v = getenv(name);
-    return v && *v ? atoi(v) : dflt;
-}
-
 int index_ready(const pfz_index *ix)
 {
     int32_t v = 0;
@@ -553,7 +547,7 @@ int pfz_index_build(pfz_ctx *ctx, const pfz_csr *B, pfz_index **out)
     // 210 MB instead of 267: 47 ms against 52 for the 125k x 1M shard, fabric-bound); the lock-step kernel (k3_lockstep.hip)
     // serves the postings from L2 and is fastest on 2048-row blocks (33 ms), and small query batches against the big
     // index are as fast or faster with 2048 (600 rows 0.39 ms against 0.44, 5 000 rows 2.39 against 2.52)
-    int block = env_int("PFZ_K3_BLOCK", 2048);
+    int block = knob_int(knob::K3_BLOCK, 2048);
     if (block != 1024 && block != 1536 && block != 2048 && block != 4096) block = 2048;
     const int64_t nb = (B->n_rows + block - 1) / block;
     const int64_t slots = B->n_cols * nb;
@@ -570,40 +564,37 @@ int pfz_index_build(pfz_ctx *ctx, const pfz_csr *B, pfz_index **out)
     ix->n_blocks = (int32_t)nb;
     ix->max_norm = B->max_norm;
     ix->src_serial = B->serial;
-    struct Tmp {
-        int32_t *p = nullptr;
-        ~Tmp() { if (p) pool_free(p); }
-    } cnt, sub;
+    DevBuf cnt, sub;
     // (a device-vectorised matrix does not know its number of non-zeros on the host yet -- csr_nnz() would wait for it; the
     // build runs on whatever it is, zero included)
     const bool any = B->n_rows > 0;
     // per-block LDS histograms when the vocabulary fits (PFZ_NO_LDS_HIST=1 forces the global-atomics
     // path of huge vocabularies: tests)
-    const bool lds_hist = B->n_cols <= 2 * (int64_t)kHistWords && !getenv("PFZ_NO_LDS_HIST");
+    const bool lds_hist = lds_hist_fits(B->n_cols);
     // tab_base[0] = 1 (the dummy piece), tab_base[1 + i] = pieces of list i; after the scan tab = tab_base + 1 holds every
     // list's first piece and tab[slots] the number of pieces, dummy included
     PFZ_TRY(pool_alloc(ctx, &ix->tab_base, (size_t)(slots + 3) * sizeof(int32_t)));
     ix->tab = ix->tab_base + 1;
-    PFZ_TRY(pool_alloc(ctx, &cnt.p, (size_t)(slots + 2) * sizeof(int32_t)));
+    PFZ_TRY(cnt.alloc(ctx, (size_t)(slots + 2) * sizeof(int32_t)));
     // (no memset of the table: k_index_pieces writes every entry, the dummy's and the two of the tail included)
     if (lds_hist && any) {      // counts per (list, sub-block); cnt itself is written by k_index_pieces
-        PFZ_TRY(pool_alloc(ctx, &sub.p, (size_t)(slots + 1) * kSub * sizeof(int32_t)));
-        PFZ_HIP(hipMemsetAsync(sub.p, 0, (size_t)slots * kSub * sizeof(int32_t), ctx->stream));
+        PFZ_TRY(sub.alloc(ctx, (size_t)(slots + 1) * kSub * sizeof(int32_t)));
+        PFZ_HIP(hipMemsetAsync(sub.as<int32_t>(), 0, (size_t)slots * kSub * sizeof(int32_t), ctx->stream));
     } else {
-        PFZ_HIP(hipMemsetAsync(cnt.p, 0, (size_t)(slots + 2) * sizeof(int32_t), ctx->stream));
+        PFZ_HIP(hipMemsetAsync(cnt.as<int32_t>(), 0, (size_t)(slots + 2) * sizeof(int32_t), ctx->stream));
     }
     // the heavy lists, for k_index_bank_order (only where the counts survive the fill: the LDS-histogram path)
     // ... and where K3 is long enough to pay for the pass: 100k x 100k K3 2.80 -> 2.63 ms for 0.02 ms, 125k x 1M 33.7 -> 33.0 ms
     // for 0.05; at 10k x 10k (K3 0.07 ms) it only costs.  PFZ_K3_BANK_ORDER=1 forces it (tests)
-    const char *bo_env = getenv("PFZ_K3_BANK_ORDER");
-    const bool bank_order = any && lds_hist && !getenv("PFZ_K3_NO_BANK_ORDER") &&
+    const char *bo_env = knob_str(knob::K3_BANK_ORDER);
+    const bool bank_order = any && lds_hist && !knob_set(knob::K3_NO_BANK_ORDER) &&
                             ((bo_env && atoi(bo_env) > 0) || (!bo_env && B->n_rows >= 32768));
     const int32_t bank_min = kBankMin;
     const int32_t heavy_cap = (int32_t)std::min<int64_t>(slots, (int64_t)1 << 22);
-    Tmp heavy;
+    DevBuf heavy;
     if (bank_order) {
-        PFZ_TRY(pool_alloc(ctx, &heavy.p, (size_t)(heavy_cap + 1) * sizeof(int32_t)));
-        PFZ_HIP(hipMemsetAsync(heavy.p, 0, sizeof(int32_t), ctx->stream));
+        PFZ_TRY(heavy.alloc(ctx, (size_t)(heavy_cap + 1) * sizeof(int32_t)));
+        PFZ_HIP(hipMemsetAsync(heavy.as<int32_t>(), 0, sizeof(int32_t), ctx->stream));
     }
     const int32_t words = (int32_t)((B->n_cols + 1) / 2);
     const unsigned row_grid = (unsigned)((B->n_rows * 16 + 255) / 256);
@@ -612,12 +603,12 @@ int pfz_index_build(pfz_ctx *ctx, const pfz_csr *B, pfz_index **out)
         ProfScope ps(ctx, "k_index_count");
         if (any && lds_hist)
             hipLaunchKernelGGL(k_index_count_lds, dim3((unsigned)nb * kSub), dim3(1024), 0, ctx->stream, B->indptr, B->indices,
-                               (int32_t)B->n_rows, (int32_t)nb, block, words, sub.p);
+                               (int32_t)B->n_rows, (int32_t)nb, block, words, sub.as<int32_t>());
         else if (any)
             hipLaunchKernelGGL(k_index_count, dim3(row_grid), dim3(256), 0, ctx->stream, B->indptr, B->indices,
-                               (int32_t)B->n_rows, (int32_t)nb, block, cnt.p);
-        hipLaunchKernelGGL(k_index_pieces, dim3(slot_grid), dim3(256), 0, ctx->stream, cnt.p, lds_hist && any ? sub.p : nullptr, slots,
-                           ix->tab, heavy.p, heavy_cap, bank_min);
+                               (int32_t)B->n_rows, (int32_t)nb, block, cnt.as<int32_t>());
+        hipLaunchKernelGGL(k_index_pieces, dim3(slot_grid), dim3(256), 0, ctx->stream, cnt.as<int32_t>(), lds_hist && any ? sub.as<int32_t>() : nullptr, slots,
+                           ix->tab, heavy.as<int32_t>(), heavy_cap, bank_min);
     }
     PFZ_TRY(exclusive_scan_i32(ctx, ix->tab_base, slots + 1, &ix->pieces_lazy));   // tab[i] = first piece of list i, tab[slots] = pieces + the dummy
     // The postings are allocated by a BOUND of the number of pieces (a list of c postings has ceil(c / 16) pieces: at most nnz / 16
@@ -647,20 +638,20 @@ int pfz_index_build(pfz_ctx *ctx, const pfz_csr *B, pfz_index **out)
     {
         ProfScope ps(ctx, "k_index_fill");
         // (before the fill: the global-atomics fill counts cnt down)
-        hipLaunchKernelGGL(k_index_pad, dim3(slot_grid), dim3(256), 0, ctx->stream, cnt.p, ix->tab, slots, ix->post, ix->pblk, (int32_t)nb,
+        hipLaunchKernelGGL(k_index_pad, dim3(slot_grid), dim3(256), 0, ctx->stream, cnt.as<int32_t>(), ix->tab, slots, ix->post, ix->pblk, (int32_t)nb,
                            B->indptr + B->n_rows, ix->nnz_lazy.slot);
         PFZ_TRY(lazy_mark(ctx, &ix->nnz_lazy));
         if (any && lds_hist)
             hipLaunchKernelGGL(k_index_fill_lds, dim3((unsigned)nb * kSub), dim3(1024), 0, ctx->stream, B->indptr, B->indices,
-                               B->data, (int32_t)B->n_rows, (int32_t)nb, block, words, ix->tab, sub.p, ix->post);
+                               B->data, (int32_t)B->n_rows, (int32_t)nb, block, words, ix->tab, sub.as<int32_t>(), ix->post);
         else if (any)
             hipLaunchKernelGGL(k_index_fill, dim3(row_grid), dim3(256), 0, ctx->stream, B->indptr, B->indices, B->data,
-                               (int32_t)B->n_rows, (int32_t)nb, block, cnt.p, ix->tab, ix->post);
+                               (int32_t)B->n_rows, (int32_t)nb, block, cnt.as<int32_t>(), ix->tab, ix->post);
     }
     if (bank_order) {
         ProfScope ps(ctx, "k_index_bank_order");
-        hipLaunchKernelGGL(k_index_bank_order, dim3((unsigned)ctx->prop.multiProcessorCount * 4), dim3(256), 0, ctx->stream, cnt.p,
-                           ix->tab, heavy.p, heavy_cap, ix->post);
+        hipLaunchKernelGGL(k_index_bank_order, dim3((unsigned)ctx->prop.multiProcessorCount * 4), dim3(256), 0, ctx->stream, cnt.as<int32_t>(),
+                           ix->tab, heavy.as<int32_t>(), heavy_cap, ix->post);
     }
     PFZ_HIP(hipGetLastError());
     *out = ix.release();
@@ -736,13 +727,10 @@ int pfz_cossim_topn_rows(pfz_ctx *ctx, const pfz_index *ix, const pfz_csr *A, in
         // Deep top-n (the reference clips top_n to the number of distinct to-strings only, _utils.py:54-56): passes of kMaxTop.
         // A pass keeps, per row, the kMaxTop best keys BELOW the last key of the pass before (keys are distinct: sum << 32 |
         // ~column), so the passes continue each other exactly; a row that runs out of candidates is marked exhausted.
-        struct Tmp {
-            void *p = nullptr;
-            ~Tmp() { if (p) pool_free(p); }
-        } t_idx, t_val, ub;
-        PFZ_TRY(pool_alloc(ctx, &t_idx.p, (size_t)n_rows * kMaxTop * sizeof(int32_t)));
-        PFZ_TRY(pool_alloc(ctx, &t_val.p, (size_t)n_rows * kMaxTop * sizeof(float)));
-        PFZ_TRY(pool_alloc(ctx, &ub.p, (size_t)n_rows * sizeof(uint64_t)));
+        DevBuf t_idx, t_val, ub;
+        PFZ_TRY(t_idx.alloc(ctx, (size_t)n_rows * kMaxTop * sizeof(int32_t)));
+        PFZ_TRY(t_val.alloc(ctx, (size_t)n_rows * kMaxTop * sizeof(float)));
+        PFZ_TRY(ub.alloc(ctx, (size_t)n_rows * sizeof(uint64_t)));
         PFZ_HIP(hipMemsetAsync(ub.p, 0xff, (size_t)n_rows * sizeof(uint64_t), ctx->stream));
         const int64_t max_grid = (int64_t)ctx->prop.multiProcessorCount * 16 * 64 * 8;
         const unsigned grid = (unsigned)(n_rows < max_grid ? n_rows : max_grid);
@@ -784,7 +772,7 @@ int pfz_cossim_topn_rows(pfz_ctx *ctx, const pfz_index *ix, const pfz_csr *A, in
     }
     // to-side slices (tuning knob PFZ_K3_SLICES).  Slicing LOSES on a full job -- every slice restarts the
     // top-n threshold and pays the row set-up again -- and stays off there
-    int n_slices = env_int("PFZ_K3_SLICES", 0);
+    int n_slices = knob_int(knob::K3_SLICES, 0);
     if (n_slices <= 0) {
         // auto: a small query batch (fit once / transform many, reference polyfuzz.py:234-240) cannot fill
         // 256 CUs x 18 resident workgroups with one workgroup per row -- cut the to-side until ~24 work items
@@ -813,7 +801,7 @@ int pfz_cossim_topn_rows(pfz_ctx *ctx, const pfz_index *ix, const pfz_csr *A, in
     // many from-rows a CU works on at once: 8 KiB of accumulators + 96 keys is 8960 B = 18 workgroups per CU
     const int cap = ntop <= 32 ? 96 : (ntop <= 64 ? 128 : (ntop <= 128 ? 256 : 1152));
 #ifdef PFZ_EXPERIMENTS
-    const int ablate = env_int("PFZ_K3_ABLATE", 0);   // timing experiments (variant builds only: tools/build_variant.sh -DPFZ_EXPERIMENTS): 1 = no scatter, 2 = no sweep, 3 = no warm start
+    const int ablate = knob_int(knob::K3_ABLATE, 0);   // timing experiments (variant builds only: tools/build_variant.sh -DPFZ_EXPERIMENTS): 1 = no scatter, 2 = no sweep, 3 = no warm start
 #else
     const int ablate = 0;                              // (the shipped library has no knob that makes results wrong: tests/test_abi_cpu.py)
 #endif
@@ -875,7 +863,7 @@ int pfz_cossim_topn_ranges(pfz_ctx *ctx, const pfz_index *ix, const pfz_csr *A, 
                 "pfz_cossim_topn_ranges: arguments as for pfz_cossim_topn");
     PFZ_HIP(hipSetDevice(ctx->device));
     // a list against itself in the symmetric form: ONE pass-1 launch, the ranges handed on as they finish (k3_symmetric.hip)
-    if (on_blocks && ntop <= kMaxTop && !getenv("PFZ_K3_NO_STREAMED")) {
+    if (on_blocks && ntop <= kMaxTop && !knob_set(knob::K3_NO_STREAMED)) {
         float scale, inv_scale;
         int32_t thr0;
         k3_fixed_point(A, ix, lower_bound, &scale, &inv_scale, &thr0);

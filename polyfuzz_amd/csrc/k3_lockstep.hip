@@ -291,22 +291,16 @@ __global__ __launch_bounds__(64) void k3_lockstep_kernel(const K3LsArgs a)
     }
 }
 
-static int ls_env_int(const char *name, int dflt)
-{
-    const char *v = getenv(name);
-    return v && *v ? atoi(v) : dflt;
-}
-
 bool k3_lockstep_wanted(const pfz_ctx *ctx, const pfz_index *ix, int64_t n_rows, int32_t ntop)
 {
     if (ntop > kLsKeep || ix->n_blocks < 2) return false;
     if (ix->block_cols != 2048 && ix->block_cols != 4096) return false;
-    const int force = ls_env_int("PFZ_K3_LOCKSTEP", -1);    // 1: whenever possible (tests), 0: never
+    const int force = knob_int(knob::K3_LOCKSTEP, -1);    // 1: whenever possible (tests), 0: never
     if (force >= 0) return force != 0;
     // auto: the index no longer fits the L2s by a wide margin and there are enough from-rows for the slices to stay in
     // step (1M to-rows: 40 000 from-rows 10.9 ms against 15.8 row-major, 125 000: 33.3 against 46.9; 125 000 from-rows against
     // 500k / 300k / 200k to-rows: 17.2 / 10.8 / 7.7 ms against 23.7 / 12.6 / 7.9)
-    return ix->n_rows > ls_env_int("PFZ_K3_LS_MIN_TO", 250000) && n_rows >= 16384;
+    return ix->n_rows > knob_int(knob::K3_LS_MIN_TO, 250000) && n_rows >= 16384;
 }
 
 int k3_lockstep_launch(pfz_ctx *ctx, const pfz_index *ix, const pfz_csr *A, int64_t row_begin, int64_t n_rows, int32_t ntop,
@@ -316,16 +310,16 @@ int k3_lockstep_launch(pfz_ctx *ctx, const pfz_index *ix, const pfz_csr *A, int6
     // round trips of narrower ones.  125k x 1M, top-10, K3 alone, 32 rows per pull: row-major 46.9 ms; lock-step 4096-row
     // blocks S = 1 / 2 / 4: 43.9 / 41.4 / 40.3 ms, 2048-row blocks S = 2 / 4 / 8: 41.3 / 39.5 / 38.9 ms; with 8 rows per pull
     // (18 waves per CU want more chunks than 125 000 / 32) 2048-row blocks, S = 8: 33.3 ms
-    int S = ls_env_int("PFZ_K3_LS_BLOCKS", ix->block_cols == 4096 ? 4 : 8);
+    int S = knob_int(knob::K3_LS_BLOCKS, ix->block_cols == 4096 ? 4 : 8);
     if (S != 1 && S != 2 && S != 4 && S != 8) S = 1;
     const int n_slices = (ix->n_blocks + S - 1) / S;
     // persistent one-wave workgroups: as many as the LDS lets a CU hold (8 KiB / 16 KiB of accumulators + 768 B)
     const int lds = ix->block_cols * 4 + kLsCap * 8;
-    const int per_cu = ls_env_int("PFZ_K3_LS_WAVES", (160 * 1024) / lds);
+    const int per_cu = knob_int(knob::K3_LS_WAVES, (160 * 1024) / lds);
     int64_t grid = (int64_t)ctx->prop.multiProcessorCount * (per_cu < 1 ? 1 : per_cu);
     // rows per pull: 32 when that still leaves every wave ~8 chunks per slice (the waves take chunks as they finish: the
     // slowest wave of a slice is one chunk behind), fewer for shorter from-lists
-    int chunk_rows = ls_env_int("PFZ_K3_LS_CHUNK", 0);
+    int chunk_rows = knob_int(knob::K3_LS_CHUNK, 0);
     if (chunk_rows <= 0) {
         chunk_rows = kLsChunkMax;
         while (chunk_rows > 4 && n_rows / chunk_rows < 8 * grid) chunk_rows >>= 1;

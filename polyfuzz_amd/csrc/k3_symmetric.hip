@@ -753,23 +753,10 @@ __global__ __launch_bounds__(256) void k3_sym_merge_slices(const K3SymArgs a)
 // ---- host side -------------------------------------------------------------------------------------------------------
 
 struct K3SymState {
-    pfz_ctx *ctx = nullptr;
     int64_t n = 0;
-    int32_t *thrv = nullptr;
-    uint16_t *slot4 = nullptr;
-    uint32_t *gmin = nullptr;
-    int32_t *thr_slot = nullptr;
-    uint16_t *row_slot = nullptr;
-    int32_t *mag = nullptr;
-    int2 *post_sym = nullptr;
-    uint64_t *keys = nullptr;
-    int32_t *push_cnt = nullptr;
-    uint64_t *push_buf = nullptr;
-    int32_t *ovf = nullptr;
-    uint64_t *part = nullptr;
-    int32_t *ovfx[3] = {nullptr, nullptr, nullptr};      // streamed sessions: the further side streams' lists of rows to recompute and partial lists
-    uint64_t *partx[3] = {nullptr, nullptr, nullptr};
-    uint32_t *done = nullptr;            // [nb] streamed sessions: pass-1 items finished per block
+    DevBuf thrv, slot4, gmin, thr_slot, row_slot, mag, post_sym, keys, push_cnt, push_buf, ovf, part;      // (element types: K3SymArgs)
+    DevBuf ovfx[3], partx[3];            // streamed sessions: the further side streams' lists of rows to recompute and partial lists
+    DevBuf done;                         // [nb] streamed sessions: pass-1 items finished per block
     // the running session: the next range must start where the last one ended, with the same job
     int64_t next_row = -1;
     uint64_t a_serial = 0;
@@ -781,19 +768,8 @@ struct K3SymState {
 
 void k3_sym_free(pfz_index *ix)
 {
-    K3SymState *s = ix->sym;
-    if (!s) return;
-    void *const bufs[] = {s->thrv, s->slot4, s->gmin, s->thr_slot, s->row_slot, s->mag, s->post_sym, s->keys, s->push_cnt, s->push_buf, s->ovf, s->part, s->ovfx[0], s->partx[0], s->ovfx[1], s->partx[1], s->ovfx[2], s->partx[2], s->done};
-    for (void *p : bufs)
-        if (p) pool_free(p);
-    delete s;
+    delete ix->sym;
     ix->sym = nullptr;
-}
-
-static int sym_env_int(const char *name, int dflt)
-{
-    const char *v = getenv(name);
-    return v && *v ? atoi(v) : dflt;
 }
 
 // 1: start a session with this range, 2: this range continues the running session, 0: not a job for this form
@@ -801,7 +777,7 @@ int k3_sym_wanted(const pfz_ctx *ctx, const pfz_index *ix, const pfz_csr *A, int
                   int32_t thr0, float scale, int32_t exclude_diag, int64_t diag_offset, const pfz_topn *out)
 {
     (void)ctx;
-    const int force = sym_env_int("PFZ_K3_SYM", -1);    // 0: never; 1: whenever the arithmetic allows (tests); default: auto
+    const int force = knob_int(knob::K3_SYM, -1);    // 0: never; 1: whenever the arithmetic allows (tests); default: auto
     if (force == 0) return 0;
     if (!exclude_diag || diag_offset != 0 || A->serial != ix->src_serial || A->n_rows != ix->n_rows) return 0;
     if (ix->block_cols != kSymC || !ix->pblk || ntop > kSymKeep || ix->n_blocks < 2 || ix->n_rows >= ((int64_t)1 << 30)) return 0;
@@ -816,7 +792,7 @@ int k3_sym_wanted(const pfz_ctx *ctx, const pfz_index *ix, const pfz_csr *A, int
     // auto: where halving K3 pays for seven more launches and the state round trip, and where the row-major kernel is the one that
     // would run (k3_lockstep.hip takes the to-sides beyond 250 000 rows); a first range of less than a fifth of the rows is a
     // shard of a bigger job (bench --scaling strong), not the start of a whole self-match
-    if (ix->n_rows < sym_env_int("PFZ_K3_SYM_MIN", 20480) || ix->n_rows > 250000) return 0;
+    if (ix->n_rows < knob_int(knob::K3_SYM_MIN, 20480) || ix->n_rows > 250000) return 0;
     return (row_end - row_begin) * 5 >= ix->n_rows ? 1 : 0;
 }
 
@@ -825,23 +801,23 @@ static int sym_state_alloc(pfz_ctx *ctx, const pfz_index *ix, K3SymState *s)
 {
     const int64_t n = ix->n_rows;
     const size_t cells = (size_t)ix->n_blocks * kSymC;
-    PFZ_TRY(pool_alloc(ctx, &s->thrv, (size_t)(n + 64) * sizeof(int32_t)));      // (part by part, every part's stretch rounded up: k3_sym_sharded)
-    PFZ_TRY(pool_alloc(ctx, &s->slot4, cells * sizeof(uint16_t)));
-    PFZ_TRY(pool_alloc(ctx, &s->gmin, cells / 32 * sizeof(uint32_t)));
-    PFZ_TRY(pool_alloc(ctx, &s->thr_slot, cells * sizeof(int32_t)));
-    PFZ_TRY(pool_alloc(ctx, &s->row_slot, cells * sizeof(uint16_t)));
-    PFZ_TRY(pool_alloc(ctx, &s->mag, (size_t)ix->n_blocks * 32 * kSymMag * sizeof(int32_t)));
-    PFZ_TRY(pool_alloc(ctx, &s->post_sym, (size_t)ix->piece_cap * kPiece * sizeof(int2)));
-    PFZ_TRY(pool_alloc(ctx, &s->keys, (size_t)n * kSymKeep * sizeof(uint64_t)));
-    PFZ_TRY(pool_alloc(ctx, &s->push_cnt, (size_t)n * sizeof(int32_t)));
-    PFZ_TRY(pool_alloc(ctx, &s->push_buf, (size_t)n * kSymPush * sizeof(uint64_t)));
-    PFZ_TRY(pool_alloc(ctx, &s->ovf, (size_t)(n + 1) * sizeof(int32_t)));
-    PFZ_TRY(pool_alloc(ctx, &s->part, (size_t)kSymSlicedRows * kSymSlices * kSymKeep * sizeof(uint64_t)));
+    PFZ_TRY(s->thrv.alloc(ctx, (size_t)(n + 64) * sizeof(int32_t)));      // (part by part, every part's stretch rounded up: k3_sym_sharded)
+    PFZ_TRY(s->slot4.alloc(ctx, cells * sizeof(uint16_t)));
+    PFZ_TRY(s->gmin.alloc(ctx, cells / 32 * sizeof(uint32_t)));
+    PFZ_TRY(s->thr_slot.alloc(ctx, cells * sizeof(int32_t)));
+    PFZ_TRY(s->row_slot.alloc(ctx, cells * sizeof(uint16_t)));
+    PFZ_TRY(s->mag.alloc(ctx, (size_t)ix->n_blocks * 32 * kSymMag * sizeof(int32_t)));
+    PFZ_TRY(s->post_sym.alloc(ctx, (size_t)ix->piece_cap * kPiece * sizeof(int2)));
+    PFZ_TRY(s->keys.alloc(ctx, (size_t)n * kSymKeep * sizeof(uint64_t)));
+    PFZ_TRY(s->push_cnt.alloc(ctx, (size_t)n * sizeof(int32_t)));
+    PFZ_TRY(s->push_buf.alloc(ctx, (size_t)n * kSymPush * sizeof(uint64_t)));
+    PFZ_TRY(s->ovf.alloc(ctx, (size_t)(n + 1) * sizeof(int32_t)));
+    PFZ_TRY(s->part.alloc(ctx, (size_t)kSymSlicedRows * kSymSlices * kSymKeep * sizeof(uint64_t)));
     for (int q = 0; q + 1 < kSymSides; ++q) {
-        PFZ_TRY(pool_alloc(ctx, &s->ovfx[q], (size_t)(n + 1) * sizeof(int32_t)));
-        PFZ_TRY(pool_alloc(ctx, &s->partx[q], (size_t)kSymSlicedRows * kSymSlices * kSymKeep * sizeof(uint64_t)));
+        PFZ_TRY(s->ovfx[q].alloc(ctx, (size_t)(n + 1) * sizeof(int32_t)));
+        PFZ_TRY(s->partx[q].alloc(ctx, (size_t)kSymSlicedRows * kSymSlices * kSymKeep * sizeof(uint64_t)));
     }
-    PFZ_TRY(pool_alloc(ctx, &s->done, (size_t)(ix->n_blocks + 64) * kSymDoneStride * sizeof(uint32_t)));
+    PFZ_TRY(s->done.alloc(ctx, (size_t)(ix->n_blocks + 64) * kSymDoneStride * sizeof(uint32_t)));
     return PFZ_OK;
 }
 
@@ -852,15 +828,10 @@ static K3SymState *sym_state_of(pfz_ctx *ctx, const pfz_index *ix)
     K3SymState *s = ix->sym;
     if (s) return s->n < 0 ? nullptr : s;
     s = new K3SymState();
-    s->ctx = ctx;
     s->n = ix->n_rows;
     ix->sym = s;      // (freed with the index, whatever happens below)
-    if (getenv("PFZ_K3_SYM_FAIL_ALLOC") || sym_state_alloc(ctx, ix, s) != PFZ_OK) {      // (the knob: tests of this fallback)
-        void *const bufs[] = {s->thrv, s->slot4, s->gmin, s->thr_slot, s->row_slot, s->mag, s->post_sym, s->keys, s->push_cnt, s->push_buf, s->ovf, s->part, s->ovfx[0], s->partx[0], s->ovfx[1], s->partx[1], s->ovfx[2], s->partx[2], s->done};
-        for (void *p : bufs)
-            if (p) pool_free(p);
-        *s = K3SymState();
-        s->ctx = ctx;
+    if (knob_set(knob::K3_SYM_FAIL_ALLOC) || sym_state_alloc(ctx, ix, s) != PFZ_OK) {      // (the knob: tests of this fallback)
+        *s = K3SymState();      // (whatever was allocated goes back to the pool)
         s->n = -1;
         (void)hipGetLastError();
         return nullptr;
@@ -887,7 +858,7 @@ static void sym_fill_args(K3SymArgs &a, const pfz_index *ix, const pfz_csr *A, K
     a.n = (int32_t)ix->n_rows;
     a.tab = ix->tab;
     a.post = ix->post;
-    a.post_sym = s->post_sym;
+    a.post_sym = s->post_sym.as<int2>();
     a.pblk = ix->pblk;
     a.nb = ix->n_blocks;
     a.n_pieces1 = ix->tab + ix->n_cols * ix->n_blocks;
@@ -902,20 +873,20 @@ static void sym_fill_args(K3SymArgs &a, const pfz_index *ix, const pfz_csr *A, K
     a.per = (int32_t)ix->n_rows;
     a.thr_by_part = 0;
     a.keys_out = nullptr;
-    a.thrv = s->thrv;
-    a.slot4 = s->slot4;
-    a.gmin = s->gmin;
-    a.thr_slot = s->thr_slot;
-    a.row_slot = s->row_slot;
-    a.mag = s->mag;
+    a.thrv = s->thrv.as<int32_t>();
+    a.slot4 = s->slot4.as<uint16_t>();
+    a.gmin = s->gmin.as<uint32_t>();
+    a.thr_slot = s->thr_slot.as<int32_t>();
+    a.row_slot = s->row_slot.as<uint16_t>();
+    a.mag = s->mag.as<int32_t>();
     a.n_mag_items = 0;
     a.mag_b0 = 0;
     a.mag_row_end = 0;
-    a.keys = s->keys;
-    a.push_cnt = s->push_cnt;
-    a.push_buf = s->push_buf;
-    a.ovf = s->ovf;
-    a.part = s->part;
+    a.keys = s->keys.as<uint64_t>();
+    a.push_cnt = s->push_cnt.as<int32_t>();
+    a.push_buf = s->push_buf.as<uint64_t>();
+    a.ovf = s->ovf.as<int32_t>();
+    a.part = s->part.as<uint64_t>();
     a.ovf_base = 0;
     a.ovf_max = 0;
     a.n_sl = 1;
@@ -984,7 +955,7 @@ int k3_sym_launch(pfz_ctx *ctx, const pfz_index *ix, const pfz_csr *A, int64_t r
         const int64_t pairs = sym_repost_pairs(ix);
         hipLaunchKernelGGL(k3_sym_repost, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, ctx->stream, a);
     }
-    PFZ_HIP(hipMemsetAsync(s->ovf, 0, sizeof(int32_t), ctx->stream));
+    PFZ_HIP(hipMemsetAsync(s->ovf.p, 0, sizeof(int32_t), ctx->stream));
     // pass 1: the rows of this range that have blocks above their own
     const int64_t last_block_row = (int64_t)(nb - 1) * kSymC;
     a.row_begin = (int32_t)row_begin;
@@ -997,7 +968,7 @@ int k3_sym_launch(pfz_ctx *ctx, const pfz_index *ix, const pfz_csr *A, int64_t r
 #ifdef PFZ_EXPERIMENTS
     // tools/predict_scaling.py: pass 1 of ONE part of a job cut over N GPUs, alone on this GPU ("p/N"; whole jobs only; the result is
     // that part's share -- wrong on purpose, compiled into variant builds only)
-    if (const char *solo = getenv("PFZ_K3_SYM_SOLO")) {
+    if (const char *solo = knob_str(knob::K3_SYM_SOLO)) {
         int p = 0, np_ = 1;
         if (sscanf(solo, "%d/%d", &p, &np_) == 2 && np_ > 1 && p >= 0 && p < np_ && row_begin == 0) {
             a.n_parts = np_;
@@ -1052,18 +1023,7 @@ int k3_sym_launch_streamed(pfz_ctx *ctx, const pfz_index *ix, const pfz_csr *A, 
         *declined = true;
         return PFZ_OK;
     }
-    if (!ctx->stream3) {
-        // HIGH priority: the merges are a few microseconds of work that must get wave slots while pass 1 still has tens of thousands of
-        // workgroups to dispatch (at equal priority the side stream's kernels were served when pass 1 had finished: measured)
-        int pr_lo = 0, pr_hi = 0;
-        PFZ_HIP(hipDeviceGetStreamPriorityRange(&pr_lo, &pr_hi));
-        PFZ_HIP(hipStreamCreateWithPriority(&ctx->stream3, hipStreamNonBlocking, pr_hi));
-        PFZ_HIP(hipEventCreateWithFlags(&ctx->ev3, hipEventDisableTiming));
-        for (int q = 0; q + 1 < kSymSides; ++q) {
-            PFZ_HIP(hipStreamCreateWithPriority(&ctx->stream3x[q], hipStreamNonBlocking, pr_hi));
-            PFZ_HIP(hipEventCreateWithFlags(&ctx->ev3x[q], hipEventDisableTiming));
-        }
-    }
+    PFZ_TRY(ensure_sym_streams(ctx, kSymSides));
     s->next_row = -1;
     K3SymArgs a;
     sym_fill_args(a, ix, A, s, ntop, thr0, scale, inv_scale);
@@ -1071,7 +1031,7 @@ int k3_sym_launch_streamed(pfz_ctx *ctx, const pfz_index *ix, const pfz_csr *A, 
     a.out_val = out->val;
     a.host_idx = host_idx;
     a.host_val = host_val;
-    a.done = s->done;          // (k3_sym_order clears push_cnt and the blocks' counters: no memset of their own in front of pass 0)
+    a.done = s->done.as<uint32_t>();          // (k3_sym_order clears push_cnt and the blocks' counters: no memset of their own in front of pass 0)
     const unsigned grid0 = (unsigned)std::min<int64_t>(n, (int64_t)ctx->prop.multiProcessorCount * kSymP0PerCu);
     hipLaunchKernelGGL((k3_sym_kernel<kSymC, 0>), dim3(grid0), dim3(64), 0, ctx->stream, a);
     hipLaunchKernelGGL(k3_sym_order, dim3((unsigned)nb), dim3(1024), 0, ctx->stream, a);
@@ -1085,7 +1045,7 @@ int k3_sym_launch_streamed(pfz_ctx *ctx, const pfz_index *ix, const pfz_csr *A, 
     a.mag_b0 = 0;
     a.mag_row_end = (int32_t)n;
     a.n_mag_items = (int32_t)((int64_t)nb * 32 * kSymMag * ((nb - 1 + kSymMagBlocks - 1) / kSymMagBlocks));
-    a.done = s->done;
+    a.done = s->done.as<uint32_t>();
     hipLaunchKernelGGL((k3_sym_kernel<kSymC, 1>), dim3((unsigned)(a.row_end + a.n_mag_items)), dim3(64), 0, ctx->stream, a);
     PFZ_HIP(hipGetLastError());
     a.n_mag_items = 0;
@@ -1108,8 +1068,8 @@ int k3_sym_launch_streamed(pfz_ctx *ctx, const pfz_index *ix, const pfz_csr *A, 
         const int q = i % n_sides;
         hipStream_t side = sides[q];
         const int64_t row1 = ends[i];
-        a.ovf = q ? s->ovfx[q - 1] : s->ovf;
-        a.part = q ? s->partx[q - 1] : s->part;
+        a.ovf = (q ? s->ovfx[q - 1] : s->ovf).as<int32_t>();
+        a.part = (q ? s->partx[q - 1] : s->part).as<uint64_t>();
         a.blk_lo = (int32_t)(covered[q] / kSymC);
         a.blk_hi = (int32_t)((row1 + kSymC - 1) / kSymC);
         covered[q] = row1;
@@ -1125,8 +1085,8 @@ int k3_sym_launch_streamed(pfz_ctx *ctx, const pfz_index *ix, const pfz_csr *A, 
         row0 = row1;
     }
     a.blk_lo = a.blk_hi = 0;
-    a.ovf = s->ovf;
-    a.part = s->part;
+    a.ovf = s->ovf.as<int32_t>();
+    a.part = s->part.as<uint64_t>();
     for (int q = 0; q < n_sides; ++q) {
         hipLaunchKernelGGL(k3_sym_wait, dim3(1), dim3(64), 0, sides[q], a, flag[q], flag_value[q]);      // (the stream's last range's word)
         PFZ_HIP(hipGetLastError());
@@ -1188,9 +1148,9 @@ bool k3_sym_sharded_ok(const pfz_index *ix, const pfz_csr *A, int32_t ntop, int3
     if (ix->block_cols != kSymC || !ix->pblk || ntop > kSymKeep || ix->n_blocks < 2 || ix->n_rows >= ((int64_t)1 << 30)) return false;
     if (n_parts < 1 || (int64_t)n_parts * ntop > 256 || n_parts > 64) return false;
     if (ix->sym && ix->sym->n < 0) return false;
-    const int force = sym_env_int("PFZ_K3_SYM", -1);      // 0: never; 1: whenever the arithmetic allows (tests); default: by size, as on one GPU
+    const int force = knob_int(knob::K3_SYM, -1);      // 0: never; 1: whenever the arithmetic allows (tests); default: by size, as on one GPU
     if (force >= 0) return force != 0;
-    return ix->n_rows >= sym_env_int("PFZ_K3_SYM_MIN", 20480) && ix->n_rows <= 250000;
+    return ix->n_rows >= knob_int(knob::K3_SYM_MIN, 20480) && ix->n_rows <= 250000;
 }
 
 // Every allocation of the job happens BEFORE its first collective, and a rank that fails there (or in any launch behind) tears the
@@ -1222,21 +1182,18 @@ static int k3_sym_sharded_body(pfz_ctx *ctx, pfz_comm *comm, const pfz_index *ix
     int32_t thr0;
     k3_fixed_point(A, ix, lower_bound, &scale, &inv_scale, &thr0);
     s->next_row = -1;
-    struct Tmp {
-        uint64_t *p = nullptr;
-        ~Tmp() { if (p) pool_free(p); }
-    } mine, all;
+    DevBuf mine, all;
     const size_t list_bytes = (size_t)n * ntop * sizeof(uint64_t);
-    PFZ_TRY(pool_alloc(ctx, &mine.p, list_bytes));
-    PFZ_TRY(pool_alloc(ctx, &all.p, list_bytes * n_parts));
+    PFZ_TRY(mine.alloc(ctx, list_bytes));
+    PFZ_TRY(all.alloc(ctx, list_bytes * n_parts));
     K3SymArgs a;
     sym_fill_args(a, ix, A, s, ntop, thr0, scale, inv_scale);
     a.n_parts = n_parts;
     a.my_part = part;
     a.per = (int32_t)((n + n_parts - 1) / n_parts);
     a.thr_by_part = 1;
-    a.keys_out = mine.p;
-    PFZ_HIP(hipMemsetAsync(s->ovf, 0, sizeof(int32_t), ctx->stream));      // (push_cnt: cleared by k3_sym_order)
+    a.keys_out = mine.as<uint64_t>();
+    PFZ_HIP(hipMemsetAsync(s->ovf.p, 0, sizeof(int32_t), ctx->stream));      // (push_cnt: cleared by k3_sym_order)
     // pass 0 of this part's rows; the parts' thresholds, stretch by stretch, complete thrv on every GPU
     a.row_begin = part;
     a.row_end = (int32_t)n;
@@ -1244,7 +1201,7 @@ static int k3_sym_sharded_body(pfz_ctx *ctx, pfz_comm *comm, const pfz_index *ix
     const unsigned grid0 = std::min<unsigned>(mine0, (unsigned)ctx->prop.multiProcessorCount * (unsigned)kSymP0PerCu);
     if (mine0) hipLaunchKernelGGL((k3_sym_kernel<kSymC, 0>), dim3(grid0), dim3(64), 0, ctx->stream, a);
     PFZ_HIP(hipGetLastError());
-    if (n_parts > 1) PFZ_TRY(comm_allgather_bytes(comm, s->thrv + (size_t)part * a.per, s->thrv, (size_t)a.per * sizeof(int32_t)));
+    if (n_parts > 1) PFZ_TRY(comm_allgather_bytes(comm, a.thrv + (size_t)part * a.per, a.thrv, (size_t)a.per * sizeof(int32_t)));
     hipLaunchKernelGGL(k3_sym_order, dim3((unsigned)nb), dim3(1024), 0, ctx->stream, a);
     const int64_t pairs = sym_repost_pairs(ix);
     hipLaunchKernelGGL(k3_sym_repost, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, ctx->stream, a);
@@ -1265,10 +1222,10 @@ static int k3_sym_sharded_body(pfz_ctx *ctx, pfz_comm *comm, const pfz_index *ix
     sym_launch_pass2(ctx, a);
     PFZ_HIP(hipGetLastError());
     // the parts' lists -> the result, on every GPU
-    const uint64_t *lists = mine.p;
+    const uint64_t *lists = mine.as<uint64_t>();
     if (n_parts > 1) {
         PFZ_TRY(comm_allgather_bytes(comm, mine.p, all.p, list_bytes));
-        lists = all.p;
+        lists = all.as<uint64_t>();
     }
     hipLaunchKernelGGL(k3_sym_merge_parts, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, ctx->stream, lists, n_parts, (int32_t)n, ntop,
                        inv_scale, out->idx, out->val);
@@ -1297,8 +1254,8 @@ extern "C" int pfz_index_symmetric_census(const pfz_index *ix, int64_t *magnet_r
         PFZ_HIP(hipSetDevice(ix->ctx->device));
         std::vector<int32_t> mag((size_t)ix->n_blocks * 32 * pfz::kSymMag);
         int32_t n_ovf = 0;
-        PFZ_TRY(pfz::copy_d2h(ix->ctx, mag.data(), s->mag, mag.size() * sizeof(int32_t)));
-        PFZ_TRY(pfz::copy_d2h(ix->ctx, &n_ovf, s->ovf, sizeof(int32_t)));
+        PFZ_TRY(pfz::copy_d2h(ix->ctx, mag.data(), s->mag.p, mag.size() * sizeof(int32_t)));
+        PFZ_TRY(pfz::copy_d2h(ix->ctx, &n_ovf, s->ovf.p, sizeof(int32_t)));
         for (int32_t r : mag) mags += r >= 0;
         rec = n_ovf;
     }

@@ -596,25 +596,15 @@ void pfz_indel_plan_free(pfz_indel_plan *p) { delete p; }
 
 namespace pfz {
 
-template <typename T> static int up(pfz_ctx *ctx, T **dst, const std::vector<T> &v)
-{
-    PFZ_TRY(pool_alloc(ctx, dst, (v.empty() ? 1 : v.size()) * sizeof(T)));
-    if (!v.empty()) PFZ_TRY(copy_h2d(ctx, *dst, v.data(), v.size() * sizeof(T)));
-    return PFZ_OK;
-}
-
 static int build_plan(pfz_ctx *ctx, const pfz_strings *T, pfz_indel_plan **out)
 {
     Owner<pfz_indel_plan, pfz_indel_plan_free> pl(new pfz_indel_plan());
     pl->ctx = ctx;
     // alphabet of the to-list: presence bitmap on the device, ranks on the host
     const size_t words = 0x110000 / 32;
-    uint32_t *present = nullptr;
-    PFZ_TRY(pool_alloc(ctx, &present, words * sizeof(uint32_t)));
-    struct Free {
-        void *p;
-        ~Free() { pool_free(p); }
-    } free_present{present};
+    DevBuf free_present;
+    PFZ_TRY(free_present.alloc(ctx, words * sizeof(uint32_t)));
+    uint32_t *const present = free_present.as<uint32_t>();
     const size_t used_words = T->char_width == 1 ? 8 : words;
     PFZ_HIP(hipMemsetAsync(present, 0, used_words * sizeof(uint32_t), ctx->stream));
     if (T->n_units > 0) {
@@ -648,7 +638,7 @@ static int build_plan(pfz_ctx *ctx, const pfz_strings *T, pfz_indel_plan **out)
     pl->n_sym = S;
     pl->idb = S <= 255 ? 8 : 16;
     pl->lut_len = (uint32_t)lut.size();
-    PFZ_TRY(up(ctx, &pl->lut, lut));
+    PFZ_TRY(upload_owned(ctx, &pl->lut, lut));
     // groups of 64 to-strings of similar length: counting sort by length on the host (O(n) ints), packing on the device
     const int per = 32 / pl->idb;
     const int64_t n_to = T->n;
@@ -673,10 +663,10 @@ static int build_plan(pfz_ctx *ctx, const pfz_strings *T, pfz_indel_plan **out)
     }
     pl->n_groups = n_groups;
     pl->char_steps = total_dw * per;
-    PFZ_TRY(up(ctx, &pl->g_off, g_off));
-    PFZ_TRY(up(ctx, &pl->g_steps, g_steps));
-    PFZ_TRY(up(ctx, &pl->b_len, b_len));
-    PFZ_TRY(up(ctx, &pl->b_orig, b_orig));
+    PFZ_TRY(upload_owned(ctx, &pl->g_off, g_off));
+    PFZ_TRY(upload_owned(ctx, &pl->g_steps, g_steps));
+    PFZ_TRY(upload_owned(ctx, &pl->b_len, b_len));
+    PFZ_TRY(upload_owned(ctx, &pl->b_orig, b_orig));
     PFZ_TRY(pool_alloc(ctx, &pl->packed, (size_t)(total_dw + 128) * sizeof(uint32_t)));     // + two steps: the quad kernel reads ahead
     if (n_groups > 0) {
         ProfScope ps(ctx, "k4_pack");
@@ -706,13 +696,6 @@ static int launch_class(pfz_ctx *ctx, const IndelArgs &A, int idb, unsigned grid
     PFZ_HIP(hipGetLastError());
     return PFZ_OK;
 }
-
-struct DevBuf {
-    pfz_ctx *ctx = nullptr;
-    void *p = nullptr;
-    ~DevBuf() { if (p) pool_free(p); }
-    int alloc(size_t bytes) { return pool_alloc(ctx, &p, bytes > 0 ? bytes : 16); }
-};
 
 static int indel_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T_c, const int32_t *skip_idx, int64_t begin,
                      int64_t end, int32_t *out_idx, double *out_score, double *out_matrix, pfz_topn *out_dev = nullptr)
@@ -747,7 +730,7 @@ static int indel_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T_c,
             cls[6].insert(cls[6].end(), cls[c].begin(), cls[c].end());
             cls[c].clear();
         }
-    if (getenv("PFZ_K4_FORCE_GENERAL")) {       // tests: everything through the general kernel
+    if (knob_set(knob::K4_FORCE_GENERAL)) {       // tests: everything through the general kernel
         for (int c = 0; c < 6; ++c) {
             cls[6].insert(cls[6].end(), cls[c].begin(), cls[c].end());
             cls[c].clear();
@@ -755,20 +738,16 @@ static int indel_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T_c,
     }
     const int64_t n_to = T->n;
     DevBuf d_skip, d_oidx, d_oscore, d_matrix, d_rows[7], d_pm, d_v;
-    for (DevBuf *b : {&d_skip, &d_oidx, &d_oscore, &d_matrix, &d_rows[0], &d_rows[1], &d_rows[2], &d_rows[3], &d_rows[4], &d_rows[5],
-                      &d_rows[6], &d_pm, &d_v})
-        b->ctx = ctx;
     int skip_up_to = 0;
     if (skip_idx) {
         std::vector<int32_t> codes(skip_idx, skip_idx + F->n);
         skip_up_to = decode_skip_codes(codes);
         PFZ_REQUIRE(skip_up_to >= 0, "pfz_indel_argmax: skip_idx mixes single choices (>= 0) and 'up to' codes (<= -2)");
-        PFZ_TRY(d_skip.alloc((size_t)F->n * sizeof(int32_t)));
-        PFZ_TRY(copy_h2d(ctx, d_skip.p, codes.data(), (size_t)F->n * sizeof(int32_t)));
+        PFZ_TRY(d_skip.upload(ctx, codes));
     }
-    PFZ_TRY(d_oidx.alloc((size_t)n_rows * sizeof(int32_t)));
-    PFZ_TRY(d_oscore.alloc((size_t)n_rows * sizeof(double)));
-    if (out_matrix) PFZ_TRY(d_matrix.alloc((size_t)n_rows * (size_t)n_to * sizeof(double)));
+    PFZ_TRY(d_oidx.alloc(ctx, (size_t)n_rows * sizeof(int32_t)));
+    PFZ_TRY(d_oscore.alloc(ctx, (size_t)n_rows * sizeof(double)));
+    if (out_matrix) PFZ_TRY(d_matrix.alloc(ctx, (size_t)n_rows * (size_t)n_to * sizeof(double)));
 
     IndelArgs A;
     A.a_chars = F->chars;
@@ -800,7 +779,7 @@ static int indel_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T_c,
     auto split = [&](int64_t n_units) {
         const int64_t want = (4 * max_grid + n_units - 1) / n_units, cap = std::max<int64_t>(1, pl->n_groups / 4);
         int64_t parts = std::max<int64_t>(1, std::min(want, cap));
-        if (const char *e = getenv("PFZ_K4_PARTS")) parts = std::max(1, atoi(e));      // tests, A/B timing
+        if (const char *e = knob_str(knob::K4_PARTS)) parts = std::max(1, atoi(e));      // tests, A/B timing
         return (int32_t)parts;
     };
     auto merge = [&](hipStream_t st) -> int {
@@ -816,8 +795,7 @@ static int indel_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T_c,
         A.partial = nullptr;
         if (A.parts <= 1) return PFZ_OK;
         DevBuf &b = d_part[n_part++];
-        b.ctx = ctx;
-        PFZ_TRY(b.alloc((size_t)A.n_rows * (size_t)A.parts * 3 * sizeof(int32_t)));
+        PFZ_TRY(b.alloc(ctx, (size_t)A.n_rows * (size_t)A.parts * 3 * sizeof(int32_t)));
         A.partial = (int32_t *)b.p;
         return PFZ_OK;
     };
@@ -827,23 +805,22 @@ static int indel_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T_c,
     // off by default.  (K7 uses the same scheme where the overlapped launch is 7 ms long.)
     bool any_long = false;
     for (int c = 1; c < 6; ++c) any_long = any_long || !cls[c].empty();
-    const bool side = any_long && !cls[0].empty() && getenv("PFZ_K4_SIDE_STREAM") != nullptr;
+    const bool side = any_long && !cls[0].empty() && knob_set(knob::K4_SIDE_STREAM);
     if (side) PFZ_TRY(ensure_side_stream(ctx));
     // the row lists of all classes first (the side stream starts from an event recorded behind these copies); class 0:
     // several short from-strings per workgroup pass (PFZ_K4_NO_QUAD=1: the one-string kernel, tests) -- eight of <= 16
     // characters, four of 17 .. 32 (PFZ_K4_NO_OCTO=1: four of <= 32)
     const bool quad = !cls[0].empty() && !out_matrix && (size_t)A.n_sym1 * sizeof(uint4) <= 60 * 1024 && T->max_len < (1 << 24) - 64 &&
-                      !getenv("PFZ_K4_NO_QUAD");
+                      !knob_set(knob::K4_NO_QUAD);
     std::vector<int32_t> rows8, rows4;
     if (quad) {
         for (int32_t i : cls[0])
-            (F->h_off[(size_t)i + 1] - F->h_off[(size_t)i] <= 16 && !getenv("PFZ_K4_NO_OCTO") ? rows8 : rows4).push_back(i);
+            (F->h_off[(size_t)i + 1] - F->h_off[(size_t)i] <= 16 && !knob_set(knob::K4_NO_OCTO) ? rows8 : rows4).push_back(i);
         std::copy(rows4.begin(), rows4.end(), std::copy(rows8.begin(), rows8.end(), cls[0].begin()));
     }
     for (int c = 0; c < 6; ++c) {
         if (cls[c].empty()) continue;
-        PFZ_TRY(d_rows[c].alloc(cls[c].size() * sizeof(int32_t)));
-        PFZ_TRY(copy_h2d(ctx, d_rows[c].p, cls[c].data(), cls[c].size() * sizeof(int32_t)));
+        PFZ_TRY(d_rows[c].upload(ctx, cls[c]));
     }
     ProfScope ps_all(ctx, "k4_indel");
     if (side) {
@@ -906,11 +883,10 @@ static int indel_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T_c,
                       (long long)longest, pl->n_sym, pm_per);
             return PFZ_ERR_UNSUPPORTED;
         }
-        PFZ_TRY(d_pm.alloc(pm_per * (size_t)gridg));
-        PFZ_TRY(d_v.alloc((size_t)gridg * (size_t)W * 256 * sizeof(uint64_t)));
+        PFZ_TRY(d_pm.alloc(ctx, pm_per * (size_t)gridg));
+        PFZ_TRY(d_v.alloc(ctx, (size_t)gridg * (size_t)W * 256 * sizeof(uint64_t)));
         PFZ_HIP(hipMemsetAsync(d_pm.p, 0, pm_per * (size_t)gridg, ctx->stream));
-        PFZ_TRY(d_rows[6].alloc(cls[6].size() * sizeof(int32_t)));
-        PFZ_TRY(copy_h2d(ctx, d_rows[6].p, cls[6].data(), cls[6].size() * sizeof(int32_t)));
+        PFZ_TRY(d_rows[6].upload(ctx, cls[6]));
         A.rows = (const int32_t *)d_rows[6].p;
         A.n_rows = (int32_t)cls[6].size();
         if (pl->idb == 8)

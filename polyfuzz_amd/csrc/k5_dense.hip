@@ -660,11 +660,8 @@ static int dense_fill16(pfz_ctx *ctx, pfz_dense *m, const void *vec, int32_t sou
     const int64_t n = m->n, dim = m->dim, ld = m->ld;
     if (source == PFZ_DENSE_SRC_F32) {
         // float32 values: uploaded as they are, rounded (and padded) on the device
-        struct Tmp {
-            float *p = nullptr;
-            ~Tmp() { if (p) pool_free(p); }     // (stream order keeps it alive until k5_round16 is done)
-        } tmp;
-        PFZ_TRY(pool_alloc(ctx, &tmp.p, (size_t)n * (size_t)dim * sizeof(float)));
+        DevBuf tmp;      // (freed at the end of this block: stream order keeps it alive until k5_round16 is done)
+        PFZ_TRY(tmp.alloc(ctx, (size_t)n * (size_t)dim * sizeof(float)));
         PFZ_TRY(copy_h2d(ctx, tmp.p, vec, (size_t)n * (size_t)dim * sizeof(float)));
         const int64_t blocks = std::min<int64_t>((n * ld + 255) / 256, 65536);
         hipLaunchKernelGGL(k5_round16<T>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, (const float *)tmp.p, n, dim, ld, m->x16);
@@ -801,10 +798,7 @@ int pfz_dense_topn(pfz_ctx *ctx, const pfz_dense *from, const pfz_dense *to, int
     if (n_from == 0) return PFZ_OK;
     PFZ_HIP(hipSetDevice(ctx->device));
     if (lower_bound < 0.f) lower_bound = 0.f;   // non-positive similarities are "no match" (_utils.py:122-123)
-    struct Buf {
-        void *p = nullptr;
-        ~Buf() { if (p) pool_free(p); }
-    } dS[2], dM[2], dU[2];
+    DevBuf dS[2], dM[2], dU[2];
     const int64_t ld = ((n_to + 255) / 256) * 256;                      // whole float4 x 64-lane steps
     // Two score panels of <= 4 GiB.  At 500 000 to-vectors that is 2048 rows: each B tile
     // serves 16 row tiles per panel.  (16 GiB panels are 1.5 % faster per step -- B is re-read once per panel -- but
@@ -813,21 +807,21 @@ int pfz_dense_topn(pfz_ctx *ctx, const pfz_dense *from, const pfz_dense *to, int
     // kernel per panel and the overlap no longer matters, without them (d % 32 != 0) it is a full read of the panel.
     const int64_t panel_bytes = (int64_t)4 << 30;
     int64_t panel = ld > 0 ? panel_bytes / (ld * 4) : n_from;
-    if (const char *forced = getenv("PFZ_K5_PANEL_ROWS")) panel = atoll(forced);   // tests: several panels on small inputs
+    if (const char *forced = knob_str(knob::K5_PANEL_ROWS)) panel = atoll(forced);   // tests: several panels on small inputs
     panel = std::max<int64_t>(kTile, std::min<int64_t>(panel / kTile * kTile, ((n_from + kTile - 1) / kTile) * kTile));
     const int64_t n_panels = (n_from + panel - 1) / panel;
-    const bool two = n_panels > 1 && !getenv("PFZ_K5_NO_OVERLAP");       // env: A/B timing
+    const bool two = n_panels > 1 && !knob_set(knob::K5_NO_OVERLAP);       // env: A/B timing
     if (two) PFZ_TRY(ensure_side_stream(ctx));
     if (ld > 0) {
-        PFZ_TRY(pool_alloc(ctx, &dS[0].p, (size_t)panel * (size_t)ld * sizeof(float)));
-        if (two) PFZ_TRY(pool_alloc(ctx, &dS[1].p, (size_t)panel * (size_t)ld * sizeof(float)));
+        PFZ_TRY(dS[0].alloc(ctx, (size_t)panel * (size_t)ld * sizeof(float)));
+        if (two) PFZ_TRY(dS[1].alloc(ctx, (size_t)panel * (size_t)ld * sizeof(float)));
         // block maxima (one float per row and 64 columns), written by the second-generation GEMM
-        PFZ_TRY(pool_alloc(ctx, &dM[0].p, (size_t)panel * (size_t)(ld / 64) * sizeof(float)));
-        if (two) PFZ_TRY(pool_alloc(ctx, &dM[1].p, (size_t)panel * (size_t)(ld / 64) * sizeof(float)));
+        PFZ_TRY(dM[0].alloc(ctx, (size_t)panel * (size_t)(ld / 64) * sizeof(float)));
+        if (two) PFZ_TRY(dM[1].alloc(ctx, (size_t)panel * (size_t)(ld / 64) * sizeof(float)));
     }
     if (ntop > kDeepPass) {      // a deep top-n: every row's last key of the pass before
-        PFZ_TRY(pool_alloc(ctx, &dU[0].p, (size_t)panel * sizeof(uint64_t)));
-        if (two) PFZ_TRY(pool_alloc(ctx, &dU[1].p, (size_t)panel * sizeof(uint64_t)));
+        PFZ_TRY(dU[0].alloc(ctx, (size_t)panel * sizeof(uint64_t)));
+        if (two) PFZ_TRY(dU[1].alloc(ctx, (size_t)panel * sizeof(uint64_t)));
     }
     hipEvent_t *ready = ctx->side_events, *consumed = ctx->side_events + 2;
     int64_t pi = 0;
@@ -843,7 +837,7 @@ int pfz_dense_topn(pfz_ctx *ctx, const pfz_dense *from, const pfz_dense *to, int
             if (n_to > 0) {
                 // 1-D grid of 8 x 8 tile blocks dealt round-robin to the XCDs (see the kernel)
                 const dim3 grid_p((unsigned)((((tiles_m + 7) / 8) * ((tiles_n + 7) / 8) + 7) / 8 * 512));
-                M = getenv("PFZ_K5_NO_BLOCK_MAX") ? nullptr : (const float *)dM[buf].p;      // A/B knob, tests
+                M = knob_set(knob::K5_NO_BLOCK_MAX) ? nullptr : (const float *)dM[buf].p;      // A/B knob, tests
                 if (from->dtype == PFZ_DENSE_F32)
                     hipLaunchKernelGGL(k5_gemm_panel_pipe, grid_p, dim3(256), 0, ctx->stream, from->x, to->x, from->inv, to->inv, a0, a1,
                                        n_to, dim, S, ld, tiles_m, tiles_n, (float *)M, ld / 64);

@@ -235,14 +235,11 @@ int pfz_pr_curve_host(pfz_ctx *ctx, const double *sim, int64_t n, const double *
     frexp((double)(n > 0 ? n : 1) * (max_abs > 0.0 ? max_abs : 1.0), &e);
     const double scale = ldexp(1.0, 61 - e);
     PFZ_HIP(hipSetDevice(ctx->device));
-    struct Buf {
-        void *p = nullptr;
-        ~Buf() { if (p) pool_free(p); }
-    } d_sim, d_thr, d_cnt, d_sum;
-    PFZ_TRY(pool_alloc(ctx, &d_sim.p, (size_t)(n > 0 ? n : 1) * sizeof(double)));
-    PFZ_TRY(pool_alloc(ctx, &d_thr.p, (size_t)n_thr * sizeof(double)));
-    PFZ_TRY(pool_alloc(ctx, &d_cnt.p, (size_t)(n_thr + 1) * sizeof(uint64_t)));
-    PFZ_TRY(pool_alloc(ctx, &d_sum.p, (size_t)(n_thr + 1) * sizeof(int64_t)));
+    DevBuf d_sim, d_thr, d_cnt, d_sum;
+    PFZ_TRY(d_sim.alloc(ctx, (size_t)(n > 0 ? n : 1) * sizeof(double)));
+    PFZ_TRY(d_thr.alloc(ctx, (size_t)n_thr * sizeof(double)));
+    PFZ_TRY(d_cnt.alloc(ctx, (size_t)(n_thr + 1) * sizeof(uint64_t)));
+    PFZ_TRY(d_sum.alloc(ctx, (size_t)(n_thr + 1) * sizeof(int64_t)));
     PFZ_TRY(copy_h2d(ctx, d_sim.p, sim, (size_t)n * sizeof(double)));
     PFZ_TRY(copy_h2d(ctx, d_thr.p, thresholds, (size_t)n_thr * sizeof(double)));
     PFZ_HIP(hipMemsetAsync(d_cnt.p, 0, (size_t)(n_thr + 1) * sizeof(uint64_t), ctx->stream));
@@ -279,12 +276,9 @@ int pfz_linkage_top1(pfz_ctx *ctx, const pfz_topn *result, double min_similarity
     int32_t info[3] = {-1, 0, 0};
     if (n > 0) {
         PFZ_HIP(hipSetDevice(ctx->device));
-        struct Buf {
-            int32_t *p = nullptr;
-            ~Buf() { if (p) pool_free(p); }
-        } work;
-        PFZ_TRY(pool_alloc(ctx, &work.p, ((size_t)n * 6 + 8) * sizeof(int32_t)));
-        int32_t *state = work.p, *fin = state + n, *ptr = fin + n, *scan = ptr + n, *cluster = scan + n, *key = cluster + n,
+        DevBuf work;
+        PFZ_TRY(work.alloc(ctx, ((size_t)n * 6 + 8) * sizeof(int32_t)));
+        int32_t *state = work.as<int32_t>(), *fin = state + n, *ptr = fin + n, *scan = ptr + n, *cluster = scan + n, *key = cluster + n,
                 *d_info = key + n;
         hipLaunchKernelGGL(k_linkage_top1, dim3(1), dim3(kLinkT), 0, ctx->stream, result->idx, result->val, result->ntop, n,
                            min_similarity, state, fin, ptr, scan, cluster, key, d_info);

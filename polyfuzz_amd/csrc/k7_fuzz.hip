@@ -848,20 +848,6 @@ __global__ __launch_bounds__(256) void k_best_to_topn(const int32_t *__restrict_
     ((double *)t_val)[r] = score[r];
 }
 
-struct DevBuf {
-    pfz_ctx *ctx = nullptr;
-    void *p = nullptr;
-    explicit DevBuf(pfz_ctx *c) : ctx(c) {}
-    ~DevBuf() { if (p) pool_free(p); }
-    int alloc(size_t bytes) { return pool_alloc(ctx, &p, bytes > 0 ? bytes : 16); }
-    template <typename T> int upload(const std::vector<T> &v)
-    {
-        PFZ_TRY(alloc(v.size() * sizeof(T)));
-        if (!v.empty()) PFZ_TRY(copy_h2d(ctx, p, v.data(), v.size() * sizeof(T)));
-        return PFZ_OK;
-    }
-};
-
 int fuzz_general_launch(pfz_ctx *ctx, FuzzArgs A, const pfz_strings *F, const pfz_strings *T, const std::vector<int32_t> &rows);   // k7_general.hip
 
 // rows [begin, end) of `from` against all of `to`: (first best index, score) into device buffers d_idx / d_score of end - begin entries
@@ -880,10 +866,10 @@ static int fuzz_run(pfz_ctx *ctx, const pfz_strings *F_c, const pfz_strings *T_c
     const pfz_fuzz_forms *ff = F->fuzz_forms;
 
     // token ids of the from-list in the to-list's table (the same handle: the plan's own)
-    DevBuf d_aid(ctx), d_skip(ctx), d_counters(ctx);
+    DevBuf d_aid, d_skip, d_counters;
     const int32_t *a_tok_id = pl->t_tok_id;
     if (F != T) {
-        PFZ_TRY(d_aid.alloc((size_t)ff->tok_cap * sizeof(int32_t)));
+        PFZ_TRY(d_aid.alloc(ctx, (size_t)ff->tok_cap * sizeof(int32_t)));
         if (F->n > 0) {
             ProfScope ps(ctx, "k7_prepare");
             PFZ_TRY(from_token_ids(ctx, F, T, (int32_t *)d_aid.p));
@@ -895,18 +881,17 @@ static int fuzz_run(pfz_ctx *ctx, const pfz_strings *F_c, const pfz_strings *T_c
         std::vector<int32_t> codes(skip_idx, skip_idx + F->n);
         skip_up_to = decode_skip_codes(codes);
         PFZ_REQUIRE(skip_up_to >= 0, "pfz_fuzz_extract_one: skip_idx mixes single choices (>= 0) and 'up to' codes (<= -2)");
-        PFZ_TRY(d_skip.alloc((size_t)F->n * sizeof(int32_t)));
-        PFZ_TRY(copy_h2d(ctx, d_skip.p, codes.data(), (size_t)F->n * sizeof(int32_t)));
+        PFZ_TRY(d_skip.upload(ctx, codes));
     }
     if (h_counters) {
-        PFZ_TRY(d_counters.alloc(4 * sizeof(unsigned long long)));
+        PFZ_TRY(d_counters.alloc(ctx, 4 * sizeof(unsigned long long)));
         PFZ_HIP(hipMemsetAsync(d_counters.p, 0, 4 * sizeof(unsigned long long), ctx->stream));
     }
 
     // word classes of the from-strings; beyond 256 characters / 32 distinct tokens / a 60 KiB match table: the general kernel
     static const int kWords[3] = {1, 2, 4};
     std::vector<int32_t> cls[4], slot_of[4];
-    const bool force_general = getenv("PFZ_K7_FORCE_GENERAL") != nullptr;
+    const bool force_general = knob_set(knob::K7_FORCE_GENERAL);
     for (int64_t i = begin; i < end; ++i) {
         const int64_t len = F->h_off[(size_t)i + 1] - F->h_off[(size_t)i];
         int c = len > 256 ? 3 : (len > 128 ? 2 : (len > 64 ? 1 : 0));
@@ -985,30 +970,30 @@ static int fuzz_run(pfz_ctx *ctx, const pfz_strings *F_c, const pfz_strings *T_c
         // titles, WRatio, 9.3 ms in two parts each against 5.2 ms whole (2 500: 5.2 against 4.6; 1 000 rows are better
         // split: 2.3 against 3.2).  From 2 048 rows on a row is one unit.
         if (c == 0 && n >= 2048 && kK7Waves == 1) parts_of[c] = 1;
-        if (const char *e = getenv("PFZ_K7_PARTS")) parts_of[c] = std::max(1, atoi(e));
+        if (const char *e = knob_str(knob::K7_PARTS)) parts_of[c] = std::max(1, atoi(e));
         max_parts = std::max(max_parts, parts_of[c]);
     }
     int32_t hand_batches = kHandBatches, hand_min_groups = kHandMinGroups, cont_parts = kContParts;
     int32_t short_len = kHandShortLen, short_batches = kHandShortBatches;
-    if (const char *e = getenv("PFZ_K7_HAND_BATCHES")) hand_batches = atoi(e), hand_min_groups = 0;      // tests: hand over early
+    if (const char *e = knob_str(knob::K7_HAND_BATCHES)) hand_batches = atoi(e), hand_min_groups = 0;      // tests: hand over early
     cont_parts = std::max(1, std::min(cont_parts, 64));
     const int32_t n_parts_total = max_parts + 1 + cont_parts;
-    DevBuf d_ps(ctx), d_pi(ctx);
-    PFZ_TRY(d_ps.alloc((size_t)n_rows * n_parts_total * sizeof(double)));
-    PFZ_TRY(d_pi.alloc((size_t)n_rows * n_parts_total * sizeof(int32_t)));
+    DevBuf d_ps, d_pi;
+    PFZ_TRY(d_ps.alloc(ctx, (size_t)n_rows * n_parts_total * sizeof(double)));
+    PFZ_TRY(d_pi.alloc(ctx, (size_t)n_rows * n_parts_total * sizeof(int32_t)));
     PFZ_HIP(hipMemsetAsync(d_ps.p, 0xff, (size_t)n_rows * n_parts_total * sizeof(double), ctx->stream));      // NaN bits: never taken ...
     PFZ_HIP(hipMemsetAsync(d_pi.p, 0x7f, (size_t)n_rows * n_parts_total * sizeof(int32_t), ctx->stream));     // ... and a huge index
     A.n_parts_total = n_parts_total;
     A.part_score = (double *)d_ps.p;
     A.part_idx = (int32_t *)d_pi.p;
 
-    DevBuf d_rows[4] = {DevBuf(ctx), DevBuf(ctx), DevBuf(ctx), DevBuf(ctx)}, d_slots[4] = {DevBuf(ctx), DevBuf(ctx), DevBuf(ctx), DevBuf(ctx)};
-    DevBuf d_next(ctx), d_stats(ctx), d_cont(ctx), d_cont_cur(ctx);
-    PFZ_TRY(d_next.alloc(16 * sizeof(int32_t)));          // [0..2] unit counters, [4..6] continuation unit counters, [8..10] continuation counts
+    DevBuf d_rows[4], d_slots[4];
+    DevBuf d_next, d_stats, d_cont, d_cont_cur;
+    PFZ_TRY(d_next.alloc(ctx, 16 * sizeof(int32_t)));          // [0..2] unit counters, [4..6] continuation unit counters, [8..10] continuation counts
     PFZ_HIP(hipMemsetAsync(d_next.p, 0, 16 * sizeof(int32_t), ctx->stream));
     const int32_t cont_cap = (int32_t)std::min<int64_t>(4 * n_rows + 64, 1 << 22);      // (continuation units of one launch, at most)
-    PFZ_TRY(d_cont.alloc((size_t)cont_cap * 3 * sizeof(int4)));
-    PFZ_TRY(d_cont_cur.alloc((size_t)cont_cap * 3 * sizeof(unsigned long long)));
+    PFZ_TRY(d_cont.alloc(ctx, (size_t)cont_cap * 3 * sizeof(int4)));
+    PFZ_TRY(d_cont_cur.alloc(ctx, (size_t)cont_cap * 3 * sizeof(unsigned long long)));
     // the bound cache: a byte per (workgroup, to-slot), a stretch of its own for every launch (they may run side by side).
     // Few enough persistent workgroups that it stays within a budget: 1/16 of the device's memory, 16 GiB at most (288 GB:
     // 4096 workgroups up to four million to-strings) -- of the TOTAL, not of what happens to be free, so that the sizes,
@@ -1016,10 +1001,10 @@ static int fuzz_run(pfz_ctx *ctx, const pfz_strings *F_c, const pfz_strings *T_c
     const int64_t ubc_budget = std::max<int64_t>((int64_t)64 << 20, std::min<int64_t>((int64_t)16 << 30, (int64_t)(ctx->prop.totalGlobalMem / 16)));
     const int64_t grid_cap = std::max<int64_t>(64, std::min<int64_t>(max_grid, ubc_budget / (3 * std::max<int64_t>(pl->n_groups, 1) * 64)));
     auto grid_of = [&](int c, bool hand) { return hand ? grid_cap : std::min<int64_t>((int64_t)cls[c].size() * parts_of[c], grid_cap); };
-    const bool hand_over = !getenv("PFZ_K7_NO_HANDOVER");
+    const bool hand_over = !knob_set(knob::K7_NO_HANDOVER);
     // (a launch that hands rows over has spare stretches: a handed-over row keeps the one its bytes are in; when they run out,
     // the continuation units of the rows handed over after that bound their shares again)
-    DevBuf d_ubc(ctx), d_cont_region(ctx);
+    DevBuf d_ubc, d_cont_region;
     int64_t ubc_at[3] = {0, 0, 0}, ubc_regions[3] = {0, 0, 0}, ubc_slots = 0;
     const int64_t region_bytes = std::max<int64_t>(pl->n_groups, 1) * 64;
     for (int c = 0; c < 3; ++c) {
@@ -1031,20 +1016,20 @@ static int fuzz_run(pfz_ctx *ctx, const pfz_strings *F_c, const pfz_strings *T_c
         ubc_regions[c] = grid_of(c, hand) + spare;
         ubc_slots += ubc_regions[c] * region_bytes;
     }
-    PFZ_TRY(d_ubc.alloc((size_t)std::max<int64_t>(ubc_slots, 64)));
-    PFZ_TRY(d_cont_region.alloc((size_t)cont_cap * 3 * sizeof(int32_t)));
-    const char *stats_path = getenv("PFZ_K7_ROW_STATS");
+    PFZ_TRY(d_ubc.alloc(ctx, (size_t)std::max<int64_t>(ubc_slots, 64)));
+    PFZ_TRY(d_cont_region.alloc(ctx, (size_t)cont_cap * 3 * sizeof(int32_t)));
+    const char *stats_path = knob_str(knob::K7_ROW_STATS);
     if (stats_path) {
         // (two per row, then eight phase timers: see the kernel)
-        PFZ_TRY(d_stats.alloc(((size_t)n_rows * 4 + 24) * sizeof(unsigned long long)));
+        PFZ_TRY(d_stats.alloc(ctx, ((size_t)n_rows * 4 + 24) * sizeof(unsigned long long)));
         PFZ_HIP(hipMemsetAsync(d_stats.p, 0, ((size_t)n_rows * 4 + 24) * sizeof(unsigned long long), ctx->stream));
         A.row_stats = (unsigned long long *)d_stats.p;
         A.phase_ticks = A.row_stats + (size_t)n_rows * 2;
     }
 #ifdef PFZ_EXPERIMENTS      // (variant builds only, tools/build_variant.sh -DPFZ_EXPERIMENTS: results wrong on purpose)
-    if (const char *e = getenv("PFZ_K7_EXP")) A.exp = atoi(e);
+    if (const char *e = knob_str(knob::K7_EXP)) A.exp = atoi(e);
 #endif
-    const bool side = !cls[0].empty() && (!cls[1].empty() || !cls[2].empty()) && !getenv("PFZ_K7_NO_SIDE_STREAM");
+    const bool side = !cls[0].empty() && (!cls[1].empty() || !cls[2].empty()) && !knob_set(knob::K7_NO_SIDE_STREAM);
     bool used_side = false;
     if (side) PFZ_TRY(ensure_side_stream(ctx));
     // an error return between a side-stream launch and its join must not free the buffers that launch is still using
@@ -1057,8 +1042,8 @@ static int fuzz_run(pfz_ctx *ctx, const pfz_strings *F_c, const pfz_strings *T_c
     ProfScope ps_all(ctx, "k7_fuzz");
     for (int c = 2; c >= 0; --c) {       // (the side-stream launches first: the persistent waves of class 0 would keep them out)
         if (cls[c].empty() || n_to == 0) continue;
-        PFZ_TRY(d_rows[c].upload(cls[c]));
-        PFZ_TRY(d_slots[c].upload(slot_of[c]));
+        PFZ_TRY(d_rows[c].upload(ctx, cls[c]));
+        PFZ_TRY(d_slots[c].upload(ctx, slot_of[c]));
         A.rows = (const int32_t *)d_rows[c].p;
         A.row_slot = (const int32_t *)d_slots[c].p;
         A.n_rows = (int32_t)cls[c].size();
@@ -1121,7 +1106,7 @@ static int fuzz_run(pfz_ctx *ctx, const pfz_strings *F_c, const pfz_strings *T_c
         A.parts = 1;
         A.part0 = max_parts;
         if (!cls[3].empty()) {
-            PFZ_TRY(d_slots[3].upload(slot_of[3]));
+            PFZ_TRY(d_slots[3].upload(ctx, slot_of[3]));
             A.row_slot = (const int32_t *)d_slots[3].p;
             A.big_slots = nullptr;
             A.n_big = 0;
@@ -1134,8 +1119,8 @@ static int fuzz_run(pfz_ctx *ctx, const pfz_strings *F_c, const pfz_strings *T_c
                 other_slots.insert(other_slots.end(), slot_of[c].begin(), slot_of[c].end());
             }
             if (!others.empty()) {
-                DevBuf d_os(ctx);
-                PFZ_TRY(d_os.upload(other_slots));
+                DevBuf d_os;
+                PFZ_TRY(d_os.upload(ctx, other_slots));
                 A.row_slot = (const int32_t *)d_os.p;
                 A.big_slots = pl->d_big_slots;
                 A.n_big = (int32_t)pl->big_slots.size();
@@ -1193,9 +1178,9 @@ int pfz_fuzz_extract_one(pfz_ctx *ctx, const pfz_strings *from_strings, const pf
     const int64_t n = from_end - from_begin;
     if (n == 0) return PFZ_OK;
     PFZ_HIP(hipSetDevice(ctx->device));
-    DevBuf d_idx(ctx), d_score(ctx);
-    PFZ_TRY(d_idx.alloc((size_t)n * sizeof(int32_t)));
-    PFZ_TRY(d_score.alloc((size_t)n * sizeof(double)));
+    DevBuf d_idx, d_score;
+    PFZ_TRY(d_idx.alloc(ctx, (size_t)n * sizeof(int32_t)));
+    PFZ_TRY(d_score.alloc(ctx, (size_t)n * sizeof(double)));
     PFZ_TRY(fuzz_run(ctx, from_strings, to_strings, scorer, skip_idx, from_begin, from_end, (int32_t *)d_idx.p, (double *)d_score.p, nullptr));
     PFZ_TRY(copy_d2h(ctx, out_idx, d_idx.p, (size_t)n * sizeof(int32_t)));
     PFZ_TRY(copy_d2h(ctx, out_score, d_score.p, (size_t)n * sizeof(double)));
@@ -1213,9 +1198,9 @@ int pfz_fuzz_extract_one_dev(pfz_ctx *ctx, const pfz_strings *from_strings, cons
     if (work_counters) work_counters[0] = work_counters[1] = work_counters[2] = work_counters[3] = 0;
     if (n == 0) return PFZ_OK;
     PFZ_HIP(hipSetDevice(ctx->device));
-    DevBuf d_idx(ctx), d_score(ctx);
-    PFZ_TRY(d_idx.alloc((size_t)n * sizeof(int32_t)));
-    PFZ_TRY(d_score.alloc((size_t)n * sizeof(double)));
+    DevBuf d_idx, d_score;
+    PFZ_TRY(d_idx.alloc(ctx, (size_t)n * sizeof(int32_t)));
+    PFZ_TRY(d_score.alloc(ctx, (size_t)n * sizeof(double)));
     PFZ_TRY(fuzz_run(ctx, from_strings, to_strings, scorer, skip_idx, from_begin, from_end, (int32_t *)d_idx.p, (double *)d_score.p,
                      (unsigned long long *)work_counters));
     return best_to_topn(ctx, (const int32_t *)d_idx.p, (const double *)d_score.p, n, out);

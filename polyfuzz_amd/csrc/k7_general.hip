@@ -315,19 +315,13 @@ int fuzz_general_launch(pfz_ctx *ctx, FuzzArgs A, const pfz_strings *F, const pf
         set_error("pfz_fuzz: strings of %lld / %lld characters need %zu bytes of scratch per workgroup", (long long)max_a, (long long)max_b, per_wg);
         return PFZ_ERR_UNSUPPORTED;
     }
-    void *d_rows = nullptr, *d_scratch = nullptr;
-    PFZ_TRY(pool_alloc_raw(ctx, &d_rows, rows.size() * sizeof(int32_t)));
-    struct Free {
-        void *p;
-        ~Free() { if (p) pool_free(p); }
-    } f1{d_rows};
-    PFZ_TRY(copy_h2d(ctx, d_rows, rows.data(), rows.size() * sizeof(int32_t)));
-    PFZ_TRY(pool_alloc_raw(ctx, &d_scratch, per_wg * (size_t)grid));
-    Free f2{d_scratch};
-    S.row = (int32_t *)d_scratch;
+    DevBuf d_rows, d_scratch;
+    PFZ_TRY(d_rows.upload(ctx, rows));
+    PFZ_TRY(d_scratch.alloc(ctx, per_wg * (size_t)grid));
+    S.row = d_scratch.as<int32_t>();
     S.dpos_a = S.row + (size_t)grid * ((size_t)S.max_row + 2) * 256;
     S.dpos_b = S.dpos_a + (size_t)grid * ((size_t)S.max_a + 1) * 256;
-    A.rows = (const int32_t *)d_rows;
+    A.rows = d_rows.as<int32_t>();
     A.n_rows = (int32_t)rows.size();
     hipLaunchKernelGGL(k7_general_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, A, S, fuzz_forms_tok_pos(F));
     PFZ_HIP(hipGetLastError());

@@ -347,13 +347,6 @@ __global__ __launch_bounds__(256) void k7_pack(PackArgs A)
     A.pres[slot] = make_uint2(pw[0], pw[1]);
 }
 
-template <typename T> static int up(pfz_ctx *ctx, T **dst, const std::vector<T> &v)
-{
-    PFZ_TRY(pool_alloc(ctx, dst, (v.empty() ? 1 : v.size()) * sizeof(T)));
-    if (!v.empty()) PFZ_TRY(copy_h2d(ctx, *dst, v.data(), v.size() * sizeof(T)));
-    return PFZ_OK;
-}
-
 static TokenLists token_lists(const pfz_strings *S)
 {
     const pfz_fuzz_forms *f = S->fuzz_forms;
@@ -369,12 +362,9 @@ int build_plan(pfz_ctx *ctx, pfz_strings *T)
     ProfScope ps(ctx, "k7_prepare");
     // alphabet: presence bitmap on the device, ranks on the host; the joining space is always a symbol
     const size_t words = 0x110000 / 32, used_words = T->char_width == 1 ? 8 : words;
-    uint32_t *present = nullptr;
-    PFZ_TRY(pool_alloc(ctx, &present, words * sizeof(uint32_t)));
-    struct Free {
-        void *p;
-        ~Free() { if (p) pool_free(p); }
-    } free_present{present};
+    DevBuf free_present;
+    PFZ_TRY(free_present.alloc(ctx, words * sizeof(uint32_t)));
+    uint32_t *const present = free_present.as<uint32_t>();
     PFZ_HIP(hipMemsetAsync(present, 0, used_words * sizeof(uint32_t), ctx->stream));
     if (T->n_units > 0) {
         const unsigned grid = (unsigned)std::min<int64_t>((T->n_units + 255) / 256, 2048);
@@ -409,11 +399,11 @@ int build_plan(pfz_ctx *ctx, pfz_strings *T)
     pl->n_sym = S;
     pl->lut_len = (uint32_t)lut.size();
     pl->space_rank = lut[0x20];
-    PFZ_TRY(up(ctx, &pl->lut, lut));
+    PFZ_TRY(upload_owned(ctx, &pl->lut, lut));
     // character classes: symbols in order of decreasing frequency take classes 0, 1, ..., 31, 0, 1, ...
-    unsigned int *d_count = nullptr;
-    PFZ_TRY(pool_alloc(ctx, &d_count, (size_t)(S + 1) * sizeof(unsigned int)));
-    Free free_count{d_count};
+    DevBuf free_count;
+    PFZ_TRY(free_count.alloc(ctx, (size_t)(S + 1) * sizeof(unsigned int)));
+    unsigned int *const d_count = free_count.as<unsigned int>();
     PFZ_HIP(hipMemsetAsync(d_count, 0, (size_t)(S + 1) * sizeof(unsigned int), ctx->stream));
     if (T->n_units > 0) {
         const unsigned grid = (unsigned)std::min<int64_t>((T->n_units + 255) / 256, 1024);
@@ -429,7 +419,7 @@ int build_plan(pfz_ctx *ctx, pfz_strings *T)
     std::vector<uint8_t> cls((size_t)S + 1, 0);
     for (int32_t k = 0; k < S; ++k) cls[(size_t)order[(size_t)k]] = (uint8_t)(k % (4 * kFuzzHistWords));
     pl->space_class = cls[(size_t)pl->space_rank];
-    PFZ_TRY(up(ctx, &pl->cls, cls));
+    PFZ_TRY(upload_owned(ctx, &pl->cls, cls));
     // token table of the to-list
     const int64_t n_to = T->n;
     int64_t total_tok = 0;
@@ -479,9 +469,9 @@ int build_plan(pfz_ctx *ctx, pfz_strings *T)
         if (j >= 0 && f->h_ntok[(size_t)j] > kFuzzMaxTokens) pl->big_slots.push_back((int32_t)sl);
     }
     pl->n_groups = n_groups;
-    PFZ_TRY(up(ctx, &pl->b_orig, b_orig));
-    PFZ_TRY(up(ctx, &pl->meta3, meta3));
-    PFZ_TRY(up(ctx, &pl->d_big_slots, pl->big_slots));
+    PFZ_TRY(upload_owned(ctx, &pl->b_orig, b_orig));
+    PFZ_TRY(upload_owned(ctx, &pl->meta3, meta3));
+    PFZ_TRY(upload_owned(ctx, &pl->d_big_slots, pl->big_slots));
     PFZ_TRY(pool_alloc(ctx, &pl->sym, (size_t)(total + 64) * sizeof(uint16_t)));
     PFZ_TRY(pool_alloc(ctx, &pl->tag, (size_t)(tag_total + 64)));
     PFZ_TRY(pool_alloc(ctx, &pl->tok_id, (size_t)(ttotal + 64) * sizeof(int32_t)));

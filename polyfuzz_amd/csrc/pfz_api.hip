@@ -101,6 +101,15 @@ int64_t csr_nnz(const pfz_csr *m)
     return m->nnz;
 }
 
+// ---- the environment knobs (pfz_knobs.h): read on every call, nothing cached ------
+const char *knob_str(const char *name) { return getenv(name); }
+bool knob_set(const char *name) { return getenv(name) != nullptr; }
+int knob_int(const char *name, int dflt)
+{
+    const char *v = getenv(name);
+    return v && *v ? atoi(v) : dflt;
+}
+
 int ensure_scratch(pfz_ctx *ctx, size_t bytes)
 {
     if (bytes <= ctx->scratch_bytes) return PFZ_OK;
@@ -139,15 +148,55 @@ static int stage_take(pfz_ctx *ctx, size_t bytes, char **out)
 
 int ensure_side_stream(pfz_ctx *ctx)
 {
-    if (!ctx->stream2) {
-        // HIGH priority: what runs here are short pieces beside a long kernel of the context's stream -- the download of a finished
-        // row range while K3's pass 1 fills every CU (at equal priority the copy was served when pass 1 had ended: measured), the row
-        // top-n of one score panel beside the GEMM of the next (K5)
-        int pr_lo = 0, pr_hi = 0;
-        PFZ_HIP(hipDeviceGetStreamPriorityRange(&pr_lo, &pr_hi));
-        PFZ_HIP(hipStreamCreateWithPriority(&ctx->stream2, hipStreamNonBlocking, pr_hi));
-        for (hipEvent_t &ev : ctx->side_events) PFZ_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    if (ctx->stream2) return PFZ_OK;
+    // HIGH priority: what runs here are short pieces beside a long kernel of the context's stream -- the download of a finished
+    // row range while K3's pass 1 fills every CU (at equal priority the copy was served when pass 1 had ended: measured), the row
+    // top-n of one score panel beside the GEMM of the next (K5)
+    int pr_lo = 0, pr_hi = 0;
+    PFZ_HIP(hipDeviceGetStreamPriorityRange(&pr_lo, &pr_hi));
+    // (into locals, committed when all of it exists: a failure leaves the context as it was and the next call tries again)
+    hipStream_t st = nullptr;
+    hipEvent_t ev[4] = {};
+    hipError_t e = hipStreamCreateWithPriority(&st, hipStreamNonBlocking, pr_hi);
+    for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming);
+    if (e != hipSuccess) {
+        for (hipEvent_t x : ev)
+            if (x) (void)hipEventDestroy(x);
+        if (st) (void)hipStreamDestroy(st);
+        return hip_fail(e, "ensure_side_stream", __FILE__, __LINE__);
     }
+    for (int i = 0; i < 4; ++i) ctx->side_events[i] = ev[i];
+    ctx->stream2 = st;
+    return PFZ_OK;
+}
+
+int ensure_sym_streams(pfz_ctx *ctx, int n_sides)
+{
+    if (ctx->stream3) return PFZ_OK;
+    // HIGH priority: the merges are a few microseconds of work that must get wave slots while pass 1 still has tens of thousands of
+    // workgroups to dispatch (at equal priority the side stream's kernels were served when pass 1 had finished: measured)
+    int pr_lo = 0, pr_hi = 0;
+    PFZ_HIP(hipDeviceGetStreamPriorityRange(&pr_lo, &pr_hi));
+    hipStream_t st[4] = {};      // [0] = stream3 / ev3, the rest stream3x / ev3x
+    hipEvent_t ev[4] = {};
+    hipError_t e = hipSuccess;
+    for (int q = 0; q < n_sides && q < 4 && e == hipSuccess; ++q) {
+        e = hipStreamCreateWithPriority(&st[q], hipStreamNonBlocking, pr_hi);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&ev[q], hipEventDisableTiming);
+    }
+    if (e != hipSuccess) {
+        for (int q = 0; q < 4; ++q) {
+            if (ev[q]) (void)hipEventDestroy(ev[q]);
+            if (st[q]) (void)hipStreamDestroy(st[q]);
+        }
+        return hip_fail(e, "ensure_sym_streams", __FILE__, __LINE__);
+    }
+    for (int q = 0; q < 3; ++q) {
+        ctx->stream3x[q] = st[q + 1];
+        ctx->ev3x[q] = ev[q + 1];
+    }
+    ctx->ev3 = ev[0];
+    ctx->stream3 = st[0];
     return PFZ_OK;
 }
 
@@ -310,7 +359,7 @@ ProfScope::ProfScope(pfz_ctx *c, const char *n, hipStream_t on) : ctx(c), name(n
 
 ProfScope::~ProfScope()
 {
-    static const bool debug_sync = getenv("PFZ_DEBUG_SYNC") != nullptr;
+    static const bool debug_sync = knob_set(knob::DEBUG_SYNC);
     if (debug_sync) {  // developer aid: localise an asynchronous device fault to a kernel
         fprintf(stderr, "[pfz] %s ...", name);
         fflush(stderr);
@@ -507,7 +556,7 @@ int exclusive_scan_i32(pfz_ctx *ctx, int32_t *data, int64_t n, LazyI32 *total)
         return total ? lazy_begin(ctx, total, data) : PFZ_OK;
     }
     const int64_t n_tiles = (n + kScanTile - 1) / kScanTile;
-    static const bool three = getenv("PFZ_SCAN3") != nullptr;
+    static const bool three = knob_set(knob::SCAN3);
     if (!three && n_tiles < (1 << 24)) {
         if ((size_t)n_tiles > ctx->scan_tiles) {
             // (grown, never shrunk; the old words may still be read by a scan in flight on this stream: stream order frees it)
@@ -644,6 +693,15 @@ int pfz_ctx_sync(pfz_ctx *ctx)
 {
     PFZ_REQUIRE(ctx, "pfz_ctx_sync: ctx is NULL");
     PFZ_HIP(hipStreamSynchronize(ctx->stream));
+    return PFZ_OK;
+}
+
+int pfz_pool_stats(pfz_ctx *ctx, int64_t *live_bytes, int64_t *cached_bytes)
+{
+    PFZ_REQUIRE(ctx, "pfz_pool_stats: ctx is NULL");
+    std::lock_guard<std::mutex> lk(g_pool_mu);
+    if (live_bytes) *live_bytes = (int64_t)ctx->pool_live_bytes;
+    if (cached_bytes) *cached_bytes = (int64_t)ctx->pool_cached_bytes;
     return PFZ_OK;
 }
 

@@ -136,16 +136,13 @@ static int local_allgather(pfz_comm *c, const void *send, void *recv, size_t byt
 
 template <typename T> static int local_allreduce_sum(pfz_comm *c, T *buf, size_t n)
 {
-    T *tmp = nullptr;
-    PFZ_TRY(pool_alloc(c->ctx, &tmp, (size_t)c->world * n * sizeof(T)));
-    int rc = local_allgather(c, buf, tmp, n * sizeof(T));
-    if (rc == PFZ_OK) {
-        hipLaunchKernelGGL((k_sum_ranks<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->ctx->stream, tmp, (int64_t)n,
-                           c->world, buf);
-        if (hipGetLastError() != hipSuccess) rc = PFZ_ERR_HIP;
-    }
-    pool_free(tmp);                     // stream-ordered reuse: the next user of the block is behind the kernel
-    return rc;
+    DevBuf tmp;                         // stream-ordered reuse: the next user of the block is behind the kernel
+    PFZ_TRY(tmp.alloc(c->ctx, (size_t)c->world * n * sizeof(T)));
+    PFZ_TRY(local_allgather(c, buf, tmp.p, n * sizeof(T)));
+    hipLaunchKernelGGL((k_sum_ranks<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->ctx->stream, tmp.as<T>(), (int64_t)n,
+                       c->world, buf);
+    PFZ_HIP(hipGetLastError());
+    return PFZ_OK;
 }
 
 static int rccl_fail(ncclResult_t r, const char *what, int line)
@@ -372,13 +369,10 @@ int pfz_comm_merge_to_shards(pfz_comm *c, const pfz_topn *local, int64_t to_offs
     PFZ_HIP(hipSetDevice(ctx->device));
     const size_t count = (size_t)local->n_rows * (size_t)local->ntop;
     if (count == 0) return PFZ_OK;
-    struct Buf {
-        void *p = nullptr;
-        ~Buf() { if (p) pool_free(p); }
-    } g_idx, g_val, offs;
-    PFZ_TRY(pool_alloc(ctx, &g_idx.p, (size_t)c->world * count * sizeof(int32_t)));
-    PFZ_TRY(pool_alloc(ctx, &g_val.p, (size_t)c->world * count * sizeof(float)));
-    PFZ_TRY(pool_alloc(ctx, &offs.p, (size_t)(c->world + 1) * sizeof(int64_t)));
+    DevBuf g_idx, g_val, offs;
+    PFZ_TRY(g_idx.alloc(ctx, (size_t)c->world * count * sizeof(int32_t)));
+    PFZ_TRY(g_val.alloc(ctx, (size_t)c->world * count * sizeof(float)));
+    PFZ_TRY(offs.alloc(ctx, (size_t)(c->world + 1) * sizeof(int64_t)));
     int64_t *mine = (int64_t *)offs.p + c->world;
     PFZ_TRY(copy_h2d(ctx, mine, &to_offset, sizeof(int64_t)));
     PFZ_TRY(comm_allgather_bytes(c, mine, offs.p, sizeof(int64_t)));

@@ -10,6 +10,7 @@
 #include <atomic>
 
 #include "polyfuzz_hip.h"
+#include "pfz_knobs.h"
 
 namespace pfz {
 
@@ -40,6 +41,8 @@ constexpr int kWave = 64;
 // LDS histograms with two 16-bit counters per word (index build, document frequencies): 144 KiB of the
 // CU's 160 KiB, i.e. vocabularies of up to 73 728 n-grams; larger ones fall back to global atomics
 constexpr int kHistWords = 36864;
+// "the vocabulary fits an LDS histogram" (K1's document frequencies, K3's index build: they must agree)
+inline bool lds_hist_fits(int64_t vocab) { return vocab <= 2 * (int64_t)kHistWords && !knob_set(knob::NO_LDS_HIST); }
 constexpr int kEventSlots = 64;
 
 // every CSR matrix gets a number of its own: "is this the matrix the index was built from?" (k3_symmetric.hip) must not be
@@ -260,6 +263,8 @@ int64_t csr_nnz(const pfz_csr *m);
 int index_ready(const pfz_index *ix);
 // the context's side stream (ctx->stream2) and its four events (ctx->side_events), created on first use
 int ensure_side_stream(pfz_ctx *ctx);
+// the streams and events of K3's streamed self-match (ctx->stream3, ev3, stream3x, ev3x), created on first use
+int ensure_sym_streams(pfz_ctx *ctx, int n_sides);   // n_sides: stream3 + n_sides - 1 of stream3x (<= 4)
 // event slot `slot` will be announced by a word in pinned host memory too: *flag / *value = the word and what a kernel behind the
 // event's work has to store there (system scope)
 int event_flag_next(pfz_ctx *ctx, int32_t slot, int32_t **flag, int32_t *value);
@@ -294,6 +299,33 @@ template <typename T> inline int pool_alloc(pfz_ctx *ctx, T **p, size_t bytes)
 }
 void pool_free(void *p);           // returns the block to its context's cache
 int pool_release(pfz_ctx *ctx);    // hipFree every cached block (blocks)
+
+// Owns one block of the caching allocator; the destructor (or reset()) returns it.  Stream order makes a free behind
+// enqueued work safe: whoever gets the block next enqueues on the same stream.
+struct DevBuf {
+    void *p = nullptr;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.release()) {}
+    DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { reset(); p = o.release(); } return *this; }
+    ~DevBuf() { reset(); }
+    int alloc(pfz_ctx *ctx, size_t bytes) { reset(); return pool_alloc_raw(ctx, &p, bytes > 0 ? bytes : 16); }
+    template <class T> int upload(pfz_ctx *ctx, const std::vector<T> &v)
+    {
+        PFZ_TRY(alloc(ctx, v.size() * sizeof(T)));
+        return copy_h2d(ctx, p, v.data(), v.size() * sizeof(T));
+    }
+    template <class T> T *as() const { return (T *)p; }
+    void reset() { if (p) pool_free(p); p = nullptr; }
+    void *release() { void *q = p; p = nullptr; return q; }      // (to a handle struct that frees the block itself)
+};
+// a host vector into a fresh block that a field of a handle struct owns from here on (the struct's free function returns it)
+template <class T> inline int upload_owned(pfz_ctx *ctx, T **field, const std::vector<T> &v)
+{
+    DevBuf b;
+    PFZ_TRY(b.upload(ctx, v));
+    *field = (T *)b.release();
+    return PFZ_OK;
+}
 
 // RCCL helpers (pfz_comm.hip); all enqueue on the communicator's context stream
 int comm_rank(const pfz_comm *c);

@@ -70,3 +70,20 @@ def test_shipped_library_has_no_wrong_on_purpose_knobs():
     for knob in (b"PFZ_K3_ABLATE", b"PFZ_K3_SYM_EXP", b"PFZ_K3_SYM_SOLO", b"PFZ_K7_EXP", b"PFZ_K3_EXP"):
         assert knob not in blob, knob
     assert b"PFZ_K3_SYM_MIN" in blob            # (a tuning knob that does not change results is still there: the check reads the right file)
+
+
+def test_host_code_has_one_buffer_owner_and_one_knob_reader():
+    """The environment is read by the three knob_* functions of pfz_api.hip alone, every knob's name is declared once in
+    pfz_knobs.h, and temporary device memory has one owner type, pfz::DevBuf of pfz_internal.h -- no unit re-declares either."""
+    csrc = os.path.join(REPO, "polyfuzz_amd", "csrc")
+    files = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
+    assert "pfz_knobs.h" in files and "pfz_api.hip" in files and len(files) >= 15
+    text = {f: open(os.path.join(csrc, f), encoding="utf-8").read() for f in files}
+    assert [f for f in files if "getenv(" in text[f]] == ["pfz_api.hip"]
+    assert [f for f in files if re.search(r'"PFZ_[A-Z0-9_]+"', text[f])] == ["pfz_knobs.h"]
+    names = re.findall(r'"(PFZ_[A-Z0-9_]+)"', text["pfz_knobs.h"])
+    assert len(names) >= 30 and len(names) == len(set(names)), sorted(n for n in set(names) if names.count(n) > 1)
+    idents = re.findall(r"inline constexpr const char \*(\w+)\s*=", text["pfz_knobs.h"])
+    assert len(idents) == len(names) and len(idents) == len(set(idents))
+    owners = [(f, m) for f in files for m in re.findall(r"\bstruct\s+(Tmp|Buf|Free|ShGuard|DevBuf)\b\s*\{", text[f])]
+    assert owners == [("pfz_internal.h", "DevBuf")], owners

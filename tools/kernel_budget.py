@@ -1,5 +1,6 @@
 """Registers, LDS and scratch of every gfx950 kernel in the built library (the code objects' own metadata).
 usage: python tools/kernel_budget.py [libpolyfuzz_hip.so] [name filter]
+       python tools/kernel_budget.py --digest [libpolyfuzz_hip.so]     one sha256 of the device code per translation unit
 
 Why: round 3 found K7 and K3 sitting ON occupancy steps -- 256 B of LDS more cost K7 a workgroup per CU and 5 %, K3 4.4 %
 (DESIGN.md, K7 / "What comes next") -- and nothing but this metadata says when an edit crosses one.
@@ -14,23 +15,31 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
 
 
+def code_objects(lib, d):
+    """the gfx950 code objects of the linked library, unbundled into directory d: one path per translation unit, in link order"""
+    fat = os.path.join(d, "fat.bin")
+    subprocess.check_call([f"{LLVM}/llvm-objcopy", "--dump-section", f".hip_fatbin={fat}", lib, os.path.join(d, "copy.so")])
+    blob = open(fat, "rb").read()
+    # one offload bundle per translation unit, back to back
+    starts = [m.start() for m in re.finditer(re.escape(b"__CLANG_OFFLOAD_BUNDLE__"), blob)]
+    out = []
+    for k, a in enumerate(starts):
+        piece, co = os.path.join(d, f"b{k}.bin"), os.path.join(d, f"b{k}.co")
+        with open(piece, "wb") as f:
+            f.write(blob[a:starts[k + 1] if k + 1 < len(starts) else len(blob)])
+        r = subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={piece}", f"--targets={TARGET}",
+                            f"--output={co}"], capture_output=True)
+        if r.returncode or not os.path.exists(co) or os.path.getsize(co) == 0:
+            continue
+        out.append(co)
+    return out
+
+
 def kernel_metadata(lib):
     """{mangled kernel name: {vgpr, sgpr, lds (static bytes), scratch (bytes per lane)}}"""
     out = {}
     with tempfile.TemporaryDirectory() as d:
-        fat = os.path.join(d, "fat.bin")
-        subprocess.check_call([f"{LLVM}/llvm-objcopy", "--dump-section", f".hip_fatbin={fat}", lib, os.path.join(d, "copy.so")])
-        blob = open(fat, "rb").read()
-        # one offload bundle per translation unit, back to back
-        starts = [m.start() for m in re.finditer(re.escape(b"__CLANG_OFFLOAD_BUNDLE__"), blob)]
-        for k, a in enumerate(starts):
-            piece, co = os.path.join(d, f"b{k}.bin"), os.path.join(d, f"b{k}.co")
-            with open(piece, "wb") as f:
-                f.write(blob[a:starts[k + 1] if k + 1 < len(starts) else len(blob)])
-            r = subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={piece}", f"--targets={TARGET}",
-                                f"--output={co}"], capture_output=True)
-            if r.returncode or not os.path.exists(co) or os.path.getsize(co) == 0:
-                continue
+        for co in code_objects(lib, d):
             notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], capture_output=True, text=True).stdout
             cur = {}
             for line in notes.splitlines():
@@ -50,6 +59,23 @@ def kernel_metadata(lib):
     return out
 
 
+def device_digests(lib):
+    """one sha256 per translation unit over its code object's .text, .rodata and kernel metadata (llvm-readelf --notes): a
+    change of host code alone leaves every line as it was"""
+    import hashlib
+    out = []
+    with tempfile.TemporaryDirectory() as d:
+        for co in code_objects(lib, d):
+            h = hashlib.sha256()
+            for sec in (".text", ".rodata"):
+                dump = co + sec
+                subprocess.run([f"{LLVM}/llvm-objcopy", "--dump-section", f"{sec}={dump}", co, co + ".copy"], capture_output=True)
+                h.update(open(dump, "rb").read() if os.path.exists(dump) else b"")
+            h.update(subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], capture_output=True).stdout)
+            out.append(h.hexdigest())
+    return out
+
+
 def demangled(names):
     import shutil
     exe = shutil.which("c++filt")
@@ -62,8 +88,14 @@ def demangled(names):
 if __name__ == "__main__":
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from polyfuzz_amd import _build
-    lib = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1].endswith(".so") else _build.LIB_PATH
-    flt = [a for a in sys.argv[1:] if not a.endswith(".so")]
+    args = [a for a in sys.argv[1:] if a != "--digest"]
+    lib = args[0] if args and args[0].endswith(".so") else _build.LIB_PATH
+    flt = [a for a in args if not a.endswith(".so")]
+    if "--digest" in sys.argv[1:]:
+        units = [os.path.basename(p) for p in _build.sources()]      # (link order)
+        for k, h in enumerate(device_digests(lib)):
+            print(h, units[k] if k < len(units) else f"unit{k}")
+        sys.exit(0)
     md = kernel_metadata(lib)
     names = sorted(md)
     print(f"{'vgpr':>5} {'sgpr':>5} {'lds B':>7} {'scratch':>7}  kernel")
