@@ -356,6 +356,22 @@ int pfz_dense_upload16(pfz_ctx *ctx, const void *vec, int64_t n, int64_t dim, in
                        int32_t source, pfz_dense **out);
 int pfz_dense_dtype(const pfz_dense *m, int32_t *dtype);
 
+/* 8-bit integer operands for the same operator (reference _embeddings.py:127-133 on scalar-quantised int8 embedding
+ * matrices, _utils.py:74-77,94-102): the vectors are kept as int8 values (a quarter of the fp32 footprint) and multiplied on
+ * the integer matrix cores with int32 accumulation, which is exact; the scores are the cosines (dot products) OF THE INT8
+ * VECTORS, to fp32 rounding of the final scaling.  `source` says what `vec` holds: PFZ_DENSE_SRC_SAME = n x dim int8 values
+ * (signed), copied as they are; PFZ_DENSE_SRC_F32 = n x dim float32 values, quantised on the device, symmetric per row:
+ * m = max |x| over the row, q = (int8) rintf((x / m) * 127.0f) (fp32 division and product, round to nearest even), row scale
+ * m / 127.0f; a row of zeros gives zeros and scale 0.  Non-finite input is outside the contract.  The factor of a row in the
+ * score is 1 / ||q|| with normalize != 0 (the cosine does not depend on the row scale); with normalize == 0 it is the row
+ * scale (the dot products of the dequantised vectors), or 1 for int8 given as it is (integer dot products, exact in the
+ * float result up to 2^24).  The width is padded with zeros to a multiple of the 128-value k-chunk; dim <= 131071, so that
+ * a dot product (|.| <= 16384 dim) fits its int32 sum: PFZ_ERR_UNSUPPORTED beyond.  pfz_dense_dtype reports PFZ_DENSE_I8;
+ * pfz_dense_topn takes two int8 operands (PFZ_ERR_INVALID for a mix with another type). */
+#define PFZ_DENSE_I8 3
+int pfz_dense_upload8(pfz_ctx *ctx, const void *vec, int64_t n, int64_t dim, int32_t normalize, int32_t source,
+                      pfz_dense **out);
+
 /* ---- K6: reductions on the hot path's output --------------------------------
  * precision_recall_curve (reference polyfuzz/metrics.py:12-53): for every threshold p_k
  * (ascending, n_thresholds <= 4096) count_ge[k] = #{i : sim[i] >= p_k} and sum_ge[k] = the sum of

@@ -100,6 +100,7 @@ SIGNATURES = {
                                                c_vp, c_vp]),
     "pfz_dense_upload": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, c_i32, P(c_vp)]),
     "pfz_dense_upload16": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, P(c_vp)]),
+    "pfz_dense_upload8": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, P(c_vp)]),
     "pfz_dense_dtype": (ctypes.c_int, [c_vp, P(c_i32)]),
     "pfz_dense_shape": (ctypes.c_int, [c_vp, P(c_i64), P(c_i64)]),
     "pfz_dense_free": (None, [c_vp]),
@@ -763,8 +764,29 @@ def dense_cossim_topn_host(ctx, from_vec, to_vec, ntop, lower_bound, exclude_dia
     return idx, val
 
 
+def check_precision(precision):
+    """The `precision` of the dense path, named after sentence-transformers' keyword: None (the operands `compute_dtype`
+    selects) or "int8": the vectors are kept as signed 8-bit values and multiplied on the integer matrix cores with int32
+    accumulation, which is exact -- the similarity is that of the INT8 vectors to fp32 rounding.  An np.int8 matrix is taken
+    as it is; float vectors are quantised per row (DeviceDense.upload_int8), which moves the cosines by a few 1e-3
+    (DESIGN.md section 4 has the measured figure): that is why it is opt-in.  Anything else raises ValueError."""
+    if precision is None or (isinstance(precision, str) and precision == "int8"):
+        return precision
+    raise ValueError(f'precision must be None or "int8", got {precision!r}')
+
+
+def dense_int8_topn_host(ctx, from_vec, to_vec, ntop, lower_bound, exclude_diag=False, normalize=True):
+    """dense_cossim_topn_host on int8 operands (DeviceDense.upload_int8): np.int8 arrays as they are, float arrays quantised
+    per row.  normalize=False: raw dot products -- of the integers as given, or of the dequantised rows."""
+    a = DeviceDense.upload_int8(ctx, from_vec, normalize)
+    b = a if to_vec is from_vec else DeviceDense.upload_int8(ctx, to_vec, normalize)
+    if a.dim != b.dim:
+        raise ValueError(f"dense cosine needs two 2-D arrays with equal width, got {(a.n, a.dim)} and {(b.n, b.dim)}")
+    return dense_topn(ctx, a, b, ntop, lower_bound, exclude_diag).download()
+
+
 class DeviceDense(_Handle):
-    """Device-resident row-major matrix (fp32, or float16 / bfloat16 values) + inverse row norms (K5 operand)."""
+    """Device-resident row-major matrix (fp32, float16 / bfloat16 or int8 values) + the per-row factors (K5 operand)."""
     _free = "pfz_dense_free"
 
     @classmethod
@@ -793,6 +815,30 @@ class DeviceDense(_Handle):
                                              DENSE_DTYPES[name], _DENSE_SRC_SAME if given else _DENSE_SRC_F32, ctypes.byref(h)))
         m = cls(ctx, h)
         m.n, m.dim, m.normalize, m.dtype = a.shape[0], a.shape[1], bool(normalize), name
+        return m
+
+    @classmethod
+    def upload_int8(cls, ctx, vec, normalize=True):
+        """An np.int8 array is uploaded as it is.  A float array goes up as fp32 and is quantised on the device, symmetric
+        per row: q = rint((x / max|x|) * 127), row scale max|x| / 127 (zero rows stay zero; non-finite values are outside the
+        contract).  The scores are the cosines of the int8 rows -- the cosine does not depend on a row's scale --, or with
+        normalize=False the dot products: of the integers as given, or of the dequantised rows q * scale.
+        Widths up to 131071 (an int32 dot product of int8 rows).  Any other dtype raises ValueError, uint8 among them: the
+        integer matrix cores are signed, and shifting by 128 changes the cosine."""
+        vec = np.asarray(vec)
+        if vec.ndim != 2:
+            raise ValueError(f"dense vectors must be a 2-D array, got shape {vec.shape}")
+        given = vec.dtype == np.int8
+        if not given and vec.dtype.kind != "f":
+            raise ValueError(f"int8 precision takes an int8 or a float array, got {vec.dtype}"
+                             + (" (unsigned values are not supported: shifting them by 128 changes the cosine)"
+                                if vec.dtype == np.uint8 else ""))
+        a = np.ascontiguousarray(vec) if given else np.ascontiguousarray(vec, np.float32)
+        h = c_vp()
+        check(ctx.lib.pfz_dense_upload8(ctx.h, _ptr(a) if a.size else None, a.shape[0], max(a.shape[1], 1), int(bool(normalize)),
+                                        _DENSE_SRC_SAME if given else _DENSE_SRC_F32, ctypes.byref(h)))
+        m = cls(ctx, h)
+        m.n, m.dim, m.normalize, m.dtype = a.shape[0], a.shape[1], bool(normalize), "int8"
         return m
 
 

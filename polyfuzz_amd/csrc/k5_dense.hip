@@ -17,6 +17,9 @@
 //   k5_gemm16_panel<T>  : the same panel and block maxima from float16 / bfloat16 operands (pfz_dense_upload16, opt-in):
 //                         256x256x64 tiles, 8 waves x (4x2) v_mfma_f32_32x32x16_f16 / _bf16, fp32 accumulation; with
 //                         k5_inv_norms16 (norms of the 16-bit values) and k5_round16 (float32 input, nearest even).
+//   k5_gemm8_panel      : the same tile program on int8 operands (pfz_dense_upload8, opt-in): v_mfma_i32_32x32x32_i8, a
+//                         k-chunk of 128 values, int32 accumulation (exact, order-independent); with k5_inv_norms8 (exact
+//                         integer norms) and k5_quantize8 (float32 input, symmetric per row).
 //   k5_row_topn         : wave per row; with M it selects the ntop-th largest block maximum and reads only the
 //                         blocks that reach it, without M it streams the row (float4); threshold filter, 64-bit
 //                         keys score_bits<<32 | ~col, compaction by wave-max rounds (same scheme as K3), writes
@@ -292,8 +295,14 @@ __global__ __launch_bounds__(256, 2) void k5_gemm_panel_pipe(const float *__rest
 // vectors as given the scores are as good as the fp32 kernel's.
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x16 __attribute__((ext_vector_type(16)));
 
+// An operand trait of the tile program (lp_gemm_tile): kBytes per value, the accumulator type and the MFMA that takes one
+// 16-byte fragment of each operand.
 struct f16 {
+    typedef f32x16 acc_t;
+    static constexpr int kBytes = 2;
     __device__ static inline float widen(uint16_t b) { return (float)__builtin_bit_cast(_Float16, b); }
     __device__ static inline uint16_t narrow(float x) { return __builtin_bit_cast(uint16_t, (_Float16)x); }   // round to nearest even
     __device__ static inline f32x16 mfma(const u32x4 &a, const u32x4 &b, const f32x16 &c)
@@ -302,6 +311,8 @@ struct f16 {
     }
 };
 struct bf16 {
+    typedef f32x16 acc_t;
+    static constexpr int kBytes = 2;
     __device__ static inline float widen(uint16_t b) { return __uint_as_float((uint32_t)b << 16); }
     __device__ static inline uint16_t narrow(float x)
     {
@@ -314,9 +325,22 @@ struct bf16 {
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
     }
 };
+// int8: a fragment is 16 consecutive values of a row, one MFMA covers k = 32.  Which k of the 32 a lane's 16 values stand for
+// does not matter here: A and B are read with the same assignment, so every step sums the same 32 products, and integer
+// addition has no order (tests/test_dense8_gpu.py holds the dot products bit for bit).
+struct i8 {
+    typedef i32x16 acc_t;
+    static constexpr int kBytes = 1;
+    __device__ static inline i32x16 mfma(const u32x4 &a, const u32x4 &b, const i32x16 &c)
+    {
+        return __builtin_amdgcn_mfma_i32_32x32x32_i8(__builtin_bit_cast(i32x4, a), __builtin_bit_cast(i32x4, b), c, 0, 0, 0);
+    }
+};
 
-constexpr int kTile16 = 256; // workgroup tile of the 16-bit tile program
-constexpr int kBK16 = 64;    // k-depth staged per step of the 16-bit tile program (128 B of a row, as kBK floats are)
+constexpr int kTile16 = 256; // workgroup tile of the 16-bit (and 8-bit) tile program
+constexpr int kChunkBytes = 128;   // bytes of a row it stages per step (as kBK floats are), which makes the k-depth
+constexpr int kBK16 = 64;    // 64 16-bit values
+constexpr int kBK8 = 128;    // or 128 int8 values
 
 // the norm of the 16-bit values as stored: the cosine is that of the vectors the GEMM multiplies
 template <typename T>
@@ -353,10 +377,11 @@ __global__ __launch_bounds__(256) void k5_round16(const float *__restrict__ src,
     }
 }
 
-// The tile program for 16-bit operands: v_mfma_f32_32x32x16_f16 / _bf16.  Lane (r = l & 31, h = l >> 5) holds
-// A[row r][k = 8 h .. 8 h + 7] and the same of B: both matrices are row-major [n][d] and the product is A . B^T, so every
-// fragment is eight consecutive values of one row -- one ds_read_b128, no transposed read.  A k-chunk is 64 values: the 128 B
-// of a row that 32 floats are, so the staging (8 lanes x 16 B per row), the LDS image (rows of 144 B: ds_write_b128 and
+// The tile program for 16-bit and 8-bit operands: v_mfma_f32_32x32x16_f16 / _bf16 / v_mfma_i32_32x32x32_i8.  Lane
+// (r = l & 31, h = l >> 5) holds 16 consecutive bytes of row r of A and the same of B -- for 16-bit values
+// A[row r][k = 8 h .. 8 h + 7]: both matrices are row-major [n][d] and the product is A . B^T, so every
+// fragment is one ds_read_b128, no transposed read.  A k-chunk is 128 B of a row (64 16-bit values, 128 int8 values):
+// what 32 floats are, so the staging (8 lanes x 16 B per row), the LDS image (rows of 144 B: ds_write_b128 and
 // ds_read_b128 conflict-free, see the fp32 program) and the software pipeline (chunk c + 2 into registers, chunk c + 1 into
 // the other LDS buffer, one barrier per chunk, clamped edge rows) are those of k5_gemm_panel_pipe.  What changes is the MFMA
 // count -- a fragment feeds ONE instruction instead of four -- and with it the balance: at 128 x 128 tiles with 64 x 64 per
@@ -364,20 +389,21 @@ __global__ __launch_bounds__(256) void k5_round16(const float *__restrict__ src,
 // per chunk and CU, and the program ran at 0.23 of the MFMA peak (measured).  So the tile is 256 x 256:
 // 8 waves of 128 x 64 (eight accumulators), 6 fragment reads per 8 MFMAs, half the LDS stores and global bytes per flop:
 // 0.28 - 0.29.  147 456 B of LDS and 512 threads: ONE workgroup per CU, two waves per SIMD.  The epilogue sees a wave's
-// 128 x 64 as the halves wm = 0, 64 of a 128 x 128 tile.
+// 128 x 64 as the halves wm = 0, 64 of a 128 x 128 tile.  d: the row pitch in values, a multiple of the k-chunk.
 template <typename T>
-__global__ __launch_bounds__(512, 1) void k5_gemm16_panel(const uint16_t *__restrict__ A, const uint16_t *__restrict__ B,
-                                                           const float *__restrict__ inv_a, const float *__restrict__ inv_b,
-                                                           int64_t a0, int64_t a1, int64_t n_b, int64_t d,
-                                                           float *__restrict__ S, int64_t ld, int tiles_m, int tiles_n,
-                                                           float *__restrict__ M, int64_t ldm)
+__device__ __forceinline__ void lp_gemm_tile(const void *__restrict__ A, const void *__restrict__ B,
+                                             const float *__restrict__ inv_a, const float *__restrict__ inv_b,
+                                             int64_t a0, int64_t a1, int64_t n_b, int64_t d,
+                                             float *__restrict__ S, int64_t ld, int tiles_m, int tiles_n,
+                                             float *__restrict__ M, int64_t ldm)
 {
-    constexpr int BK = kBK16, LD = 72, NP = 4;              // LD: LDS row pitch in 16-bit values (144 B)
-    __shared__ __attribute__((aligned(16))) uint16_t As[2][kTile16 * LD];
-    __shared__ __attribute__((aligned(16))) uint16_t Bs[2][kTile16 * LD];
+    constexpr int CB = kChunkBytes, LD = 144, NP = 4;       // LD: LDS row pitch in bytes
+    __shared__ __attribute__((aligned(16))) unsigned char As[2][kTile16 * LD];
+    __shared__ __attribute__((aligned(16))) unsigned char Bs[2][kTile16 * LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // workgroup -> tile: consecutive workgroup ids go round-robin over the 8 XCDs; the 32 workgroups an XCD runs at a time (one
-    // per CU) get one block of 8 x 4 tiles: 8 A + 4 B tiles (4.7 MB at d = 768) feed 32 tile products out of that XCD's L2
+    // per CU) get one block of 8 x 4 tiles: 8 A + 4 B tiles (4.7 MB at d = 768 16-bit values) feed 32 tile products out of
+    // that XCD's L2
     const int w = blockIdx.x, xcd = w & 7, idx = w >> 3, pos = idx & 31;
     const int g = (idx >> 5) * 8 + xcd, bm = (tiles_m + 7) >> 3;
     const int tm = (g % bm) * 8 + (pos & 7), tn = (g / bm) * 4 + (pos >> 3);
@@ -388,7 +414,7 @@ __global__ __launch_bounds__(512, 1) void k5_gemm16_panel(const uint16_t *__rest
     // halves wm = 0, 64 of the 128 x 128 tile (vr, vc)
     const int vr = wave >> 2, vc = (wave >> 1) & 1, wn = (wave & 1) * 64;
 
-    f32x16 acc[2][2][2];           // [half][i][j]
+    typename T::acc_t acc[2][2][2];           // [half][i][j]
 #pragma unroll
     for (int h = 0; h < 2; ++h)
 #pragma unroll
@@ -396,45 +422,48 @@ __global__ __launch_bounds__(512, 1) void k5_gemm16_panel(const uint16_t *__rest
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc[h][i][j][r] = 0.f;
+                for (int r = 0; r < 16; ++r) acc[h][i][j][r] = 0;
 
-    const int lr = tid >> 3, lk = (tid & 7) * 8;          // staging: 8 threads per tile row, 64 rows per pass
-    const __amdgpu_buffer_rsrc_t resA = __builtin_amdgcn_make_buffer_rsrc((void *)(A + row0 * d), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t resB = __builtin_amdgcn_make_buffer_rsrc((void *)(B + col0 * d), 0, 0x7fffffff, 0x00020000);
+    const int lr = tid >> 3, lb = (tid & 7) * 16;         // staging: 8 threads per tile row, 64 rows per pass
+    const int64_t pitch = d * T::kBytes;                  // bytes per operand row
+    const __amdgpu_buffer_rsrc_t resA =
+        __builtin_amdgcn_make_buffer_rsrc((void *)((const unsigned char *)A + row0 * pitch), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t resB =
+        __builtin_amdgcn_make_buffer_rsrc((void *)((const unsigned char *)B + col0 * pitch), 0, 0x7fffffff, 0x00020000);
     uint32_t offA[NP], offB[NP];
 #pragma unroll
     for (int p = 0; p < NP; ++p) {        // rows beyond the edge are clamped to the last row (their products are not stored)
-        offA[p] = (uint32_t)((min(row0 + lr + p * 64, a1 - 1) - row0) * d + lk) * 2u;
-        offB[p] = (uint32_t)((min(col0 + lr + p * 64, n_b - 1) - col0) * d + lk) * 2u;
+        offA[p] = (uint32_t)((min(row0 + lr + p * 64, a1 - 1) - row0) * pitch + lb);
+        offB[p] = (uint32_t)((min(col0 + lr + p * 64, n_b - 1) - col0) * pitch + lb);
     }
     u32x4 ra[NP], rb[NP];
-    auto load = [&](int p, int k) {
-        ra[p] = __builtin_amdgcn_raw_buffer_load_b128(resA, offA[p], k * 2, 0);
-        rb[p] = __builtin_amdgcn_raw_buffer_load_b128(resB, offB[p], k * 2, 0);
+    auto load = [&](int p, int kb) {      // kb: byte offset of the chunk in a row
+        ra[p] = __builtin_amdgcn_raw_buffer_load_b128(resA, offA[p], kb, 0);
+        rb[p] = __builtin_amdgcn_raw_buffer_load_b128(resB, offB[p], kb, 0);
     };
     auto stage = [&](int p, int buf) {
-        *(u32x4 *)(As[buf] + (lr + p * 64) * LD + lk) = ra[p];
-        *(u32x4 *)(Bs[buf] + (lr + p * 64) * LD + lk) = rb[p];
+        *(u32x4 *)(As[buf] + (lr + p * 64) * LD + lb) = ra[p];
+        *(u32x4 *)(Bs[buf] + (lr + p * 64) * LD + lb) = rb[p];
     };
 #pragma unroll
     for (int p = 0; p < NP; ++p) load(p, 0);
 #pragma unroll
     for (int p = 0; p < NP; ++p) stage(p, 0);
-    const int dk = (int)d;
+    const int dk = (int)pitch;
 #pragma unroll
-    for (int p = 0; p < NP; ++p) load(p, min(BK, dk - BK));
+    for (int p = 0; p < NP; ++p) load(p, min(CB, dk - CB));
     __syncthreads();
 
-    const int frag_off = (lane & 31) * LD + 8 * (lane >> 5);
+    const int frag_off = (lane & 31) * LD + 16 * (lane >> 5);
     int cur = 0;
-    for (int k0 = 0; k0 < dk; k0 += BK) {
-        const int k2 = min(k0 + 2 * BK, dk - BK);      // (the last two chunks re-fetch the last one: no branches in the loop)
-        const uint16_t *ap = As[cur] + vr * 128 * LD + frag_off, *bp = Bs[cur] + (vc * 128 + wn) * LD + frag_off;
-        auto frag = [&](int s, u32x4 (&a)[4], u32x4 (&b)[2]) {      // MFMA step s: k = 16 s + 8 h .. + 7
+    for (int k0 = 0; k0 < dk; k0 += CB) {
+        const int k2 = min(k0 + 2 * CB, dk - CB);      // (the last two chunks re-fetch the last one: no branches in the loop)
+        const unsigned char *ap = As[cur] + vr * 128 * LD + frag_off, *bp = Bs[cur] + (vc * 128 + wn) * LD + frag_off;
+        auto frag = [&](int s, u32x4 (&a)[4], u32x4 (&b)[2]) {      // MFMA step s: bytes 32 s + 16 h .. + 15 of the chunk
 #pragma unroll
-            for (int i = 0; i < 4; ++i) a[i] = *(const u32x4 *)(ap + i * 32 * LD + 16 * s);
+            for (int i = 0; i < 4; ++i) a[i] = *(const u32x4 *)(ap + i * 32 * LD + 32 * s);
 #pragma unroll
-            for (int j = 0; j < 2; ++j) b[j] = *(const u32x4 *)(bp + j * 32 * LD + 16 * s);
+            for (int j = 0; j < 2; ++j) b[j] = *(const u32x4 *)(bp + j * 32 * LD + 32 * s);
         };
         auto mfma4 = [&](const u32x4 (&a)[4], const u32x4 (&b)[2], int h) {
 #pragma unroll
@@ -464,8 +493,95 @@ __global__ __launch_bounds__(512, 1) void k5_gemm16_panel(const uint16_t *__rest
         cur ^= 1;
     }
 #pragma unroll
-    for (int h = 0; h < 2; ++h)
-        tile_epilogue(acc[h], inv_a, inv_b, a0, a1, n_b, S, ld, M, ldm, row0 + vr * 128, col0 + vc * 128, h * 64, wn, lane);
+    for (int h = 0; h < 2; ++h) {
+        if constexpr (T::kBytes == 1) {
+            // int32 sums -> float (exact up to 2^24, to nearest even beyond), then the common end
+            f32x16 facc[2][2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) facc[i][j] = __builtin_convertvector(acc[h][i][j], f32x16);
+            tile_epilogue(facc, inv_a, inv_b, a0, a1, n_b, S, ld, M, ldm, row0 + vr * 128, col0 + vc * 128, h * 64, wn, lane);
+        }
+        else
+            tile_epilogue(acc[h], inv_a, inv_b, a0, a1, n_b, S, ld, M, ldm, row0 + vr * 128, col0 + vc * 128, h * 64, wn, lane);
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(512, 1) void k5_gemm16_panel(const uint16_t *__restrict__ A, const uint16_t *__restrict__ B,
+                                                           const float *__restrict__ inv_a, const float *__restrict__ inv_b,
+                                                           int64_t a0, int64_t a1, int64_t n_b, int64_t d,
+                                                           float *__restrict__ S, int64_t ld, int tiles_m, int tiles_n,
+                                                           float *__restrict__ M, int64_t ldm)
+{
+    lp_gemm_tile<T>(A, B, inv_a, inv_b, a0, a1, n_b, d, S, ld, tiles_m, tiles_n, M, ldm);
+}
+
+// ---- 8-bit integer operands (scalar-quantised embeddings) -----------------------------------------------------------
+// The same tile program on int8 values: a k-chunk is 128 values, the sums are int32 and exact (|dot| <= 2^14 dim fits for
+// dim <= 131071, which pfz_dense_upload8 holds), and the epilogue scales float(sum) by the two per-row factors: 1 / ||q||
+// for the cosine; for raw dot products the row's quantisation scale, or 1 for int8 given as it is.
+template <typename T>
+__global__ __launch_bounds__(512, 1) void k5_gemm8_panel(const int8_t *__restrict__ A, const int8_t *__restrict__ B,
+                                                          const float *__restrict__ inv_a, const float *__restrict__ inv_b,
+                                                          int64_t a0, int64_t a1, int64_t n_b, int64_t d,
+                                                          float *__restrict__ S, int64_t ld, int tiles_m, int tiles_n,
+                                                          float *__restrict__ M, int64_t ldm)
+{
+    lp_gemm_tile<T>(A, B, inv_a, inv_b, a0, a1, n_b, d, S, ld, tiles_m, tiles_n, M, ldm);
+}
+
+// Exact integer norms of the int8 values as stored (the squares of a row sum to at most 2^14 ld: no rounding before the
+// square root).  normalize == 0: raw dot products are wanted -- a quantised row keeps the scale k5_quantize8 left in inv[],
+// int8 given as it is gets 1.
+__global__ __launch_bounds__(256) void k5_inv_norms8(const int8_t *__restrict__ x, int64_t n, int64_t d,
+                                                     float *__restrict__ inv, int32_t normalize, int32_t quantized)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n) return;
+    if (!normalize) {
+        if (lane == 0 && !quantized) inv[row] = 1.f;
+        return;
+    }
+    const uint32_t *p = (const uint32_t *)(x + row * d);      // d is a multiple of 128: four values per load
+    uint64_t ss = 0;
+    for (int64_t k = lane; k < d / 4; k += 64) {
+        const uint32_t v = p[k];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int q = (int8_t)(v >> (8 * b));
+            ss += (uint32_t)(q * q);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) ss += __shfl_xor(ss, o, 64);
+    if (lane == 0) inv[row] = ss > 0 ? (float)(1.0 / sqrt((double)ss)) : 0.f;
+}
+
+// fp32 [n][dim] -> int8 [n][ld], symmetric per row: m = max |x|, q = rint((x / m) * 127) -- an fp32 division and an fp32
+// product, each rounded to nearest even, then round-half-even to the integer -- and the row's scale m / 127 in scale[row];
+// a row of zeros gives zeros and scale 0, the columns beyond dim are zero.  Wave per row.  Non-finite input is outside the
+// contract (a NaN or an infinity in a row makes that row's values unspecified).
+__global__ __launch_bounds__(256) void k5_quantize8(const float *__restrict__ src, int64_t n, int64_t dim, int64_t ld,
+                                                    int8_t *__restrict__ dst, float *__restrict__ scale)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n) return;
+    const float *p = src + row * dim;
+    float m = 0.f;
+    for (int64_t k = lane; k < dim; k += 64) m = fmaxf(m, fabsf(p[k]));
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    int8_t *q = dst + row * ld;
+    for (int64_t k = lane; k < ld; k += 64) {
+        float v = 0.f;
+        if (k < dim && m > 0.f) v = rintf(__fmul_rn(__fdiv_rn(p[k], m), 127.0f));
+        q[k] = (int8_t)(int)v;
+    }
+    if (lane == 0) scale[row] = __fdiv_rn(m, 127.0f);
 }
 
 __device__ inline uint64_t wave_max_u64_5(uint64_t v)
@@ -641,17 +757,36 @@ using namespace pfz;
 struct pfz_dense {
     pfz_ctx *ctx = nullptr;
     int64_t n = 0, dim = 0;
-    int64_t ld = 0;          // dim rounded up to a multiple of 32 (the GEMM's k-chunk), the extra columns are zero
+    int64_t ld = 0;          // dim rounded up to a whole k-chunk of the type (128 B: 32 / 64 / 128 values), the extra columns zero
     int32_t normalize = 1;
     float *x = nullptr;      // device [n][ld] row-major (dtype == PFZ_DENSE_F32)
     int32_t dtype = PFZ_DENSE_F32;
-    uint16_t *x16 = nullptr; // device [n][ld] row-major float16 / bfloat16 bits, ld a multiple of 64 (the 16-bit k-chunk)
-    float *inv = nullptr;    // device [n]: 1 / ||row|| (1 when normalize == 0)
+    uint16_t *x16 = nullptr; // device [n][ld] row-major float16 / bfloat16 bits (dtype == PFZ_DENSE_F16 / _BF16)
+    int8_t *x8 = nullptr;    // device [n][ld] row-major int8 values, given or quantised per row (dtype == PFZ_DENSE_I8)
+    // device [n], the factor of a row in the epilogue: 1 / ||row|| of the stored values; with normalize == 0 it is 1, or for
+    // int8 rows quantised from float32 the row's scale max |x| / 127
+    float *inv = nullptr;
 };
 
 static const char *dense_dtype_name(int32_t dtype)
 {
-    return dtype == PFZ_DENSE_F16 ? "float16" : dtype == PFZ_DENSE_BF16 ? "bfloat16" : "float32";
+    return dtype == PFZ_DENSE_F16 ? "float16" : dtype == PFZ_DENSE_BF16 ? "bfloat16" : dtype == PFZ_DENSE_I8 ? "int8" : "float32";
+}
+
+// host [n][dim] values of `elem` bytes -> device [n][ld], the columns beyond dim zero (padded in pieces of 32 MiB)
+static int upload_rows_padded(pfz_ctx *ctx, void *dst, const void *src, int64_t n, int64_t dim, int64_t ld, int64_t elem)
+{
+    if (ld == dim) return copy_h2d(ctx, dst, src, (size_t)n * (size_t)dim * (size_t)elem);
+    const int64_t rows_per = std::max<int64_t>(1, ((int64_t)32 << 20) / (ld * elem));
+    std::vector<unsigned char> padded((size_t)std::min(rows_per, n) * (size_t)(ld * elem), (unsigned char)0);
+    const unsigned char *v = (const unsigned char *)src;
+    for (int64_t r0 = 0; r0 < n; r0 += rows_per) {
+        const int64_t rows = std::min(rows_per, n - r0);
+        for (int64_t r = 0; r < rows; ++r)
+            std::copy(v + (r0 + r) * dim * elem, v + (r0 + r + 1) * dim * elem, padded.begin() + (size_t)(r * ld * elem));
+        PFZ_TRY(copy_h2d(ctx, (unsigned char *)dst + r0 * ld * elem, padded.data(), (size_t)rows * (size_t)(ld * elem)));
+    }
+    return PFZ_OK;
 }
 
 template <typename T>
@@ -667,19 +802,8 @@ static int dense_fill16(pfz_ctx *ctx, pfz_dense *m, const void *vec, int32_t sou
         hipLaunchKernelGGL(k5_round16<T>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, (const float *)tmp.p, n, dim, ld, m->x16);
         PFZ_HIP(hipGetLastError());
     }
-    else if (ld == dim)
-        PFZ_TRY(copy_h2d(ctx, m->x16, vec, (size_t)n * (size_t)dim * sizeof(uint16_t)));
-    else {
-        const uint16_t *v = (const uint16_t *)vec;
-        const int64_t rows_per = std::max<int64_t>(1, ((int64_t)32 << 20) / (ld * (int64_t)sizeof(uint16_t)));
-        std::vector<uint16_t> padded((size_t)std::min(rows_per, n) * (size_t)ld, (uint16_t)0);
-        for (int64_t r0 = 0; r0 < n; r0 += rows_per) {
-            const int64_t rows = std::min(rows_per, n - r0);
-            for (int64_t r = 0; r < rows; ++r)
-                std::copy(v + (r0 + r) * dim, v + (r0 + r + 1) * dim, padded.begin() + (size_t)r * (size_t)ld);
-            PFZ_TRY(copy_h2d(ctx, m->x16 + r0 * ld, padded.data(), (size_t)rows * (size_t)ld * sizeof(uint16_t)));
-        }
-    }
+    else
+        PFZ_TRY(upload_rows_padded(ctx, m->x16, vec, n, dim, ld, sizeof(uint16_t)));
     hipLaunchKernelGGL(k5_inv_norms16<T>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, ctx->stream, (const uint16_t *)m->x16, n, ld,
                        m->inv, m->normalize);
     PFZ_HIP(hipGetLastError());
@@ -694,6 +818,7 @@ void pfz_dense_free(pfz_dense *m)
     if (m->ctx) (void)hipSetDevice(m->ctx->device);
     if (m->x) pool_free(m->x);
     if (m->x16) pool_free(m->x16);
+    if (m->x8) pool_free(m->x8);
     if (m->inv) pool_free(m->inv);
     delete m;
 }
@@ -719,18 +844,7 @@ int pfz_dense_upload(pfz_ctx *ctx, const float *vec, int64_t n, int64_t dim, int
     PFZ_TRY(pool_alloc(ctx, &m->x, (size_t)(n > 0 ? n : 1) * (size_t)ld * sizeof(float)));
     PFZ_TRY(pool_alloc(ctx, &m->inv, (size_t)(n > 0 ? n : 1) * sizeof(float)));
     if (n > 0) {
-        if (ld == dim)
-            PFZ_TRY(copy_h2d(ctx, m->x, vec, (size_t)n * (size_t)dim * sizeof(float)));
-        else {
-            const int64_t rows_per = std::max<int64_t>(1, ((int64_t)32 << 20) / (ld * (int64_t)sizeof(float)));
-            std::vector<float> padded((size_t)std::min(rows_per, n) * (size_t)ld, 0.f);
-            for (int64_t r0 = 0; r0 < n; r0 += rows_per) {
-                const int64_t rows = std::min(rows_per, n - r0);
-                for (int64_t r = 0; r < rows; ++r)
-                    std::copy(vec + (r0 + r) * dim, vec + (r0 + r + 1) * dim, padded.begin() + (size_t)r * (size_t)ld);
-                PFZ_TRY(copy_h2d(ctx, m->x + r0 * ld, padded.data(), (size_t)rows * (size_t)ld * sizeof(float)));
-            }
-        }
+        PFZ_TRY(upload_rows_padded(ctx, m->x, vec, n, dim, ld, sizeof(float)));
         hipLaunchKernelGGL(k5_inv_norms, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, ctx->stream, m->x, n, ld, m->inv, m->normalize);
         PFZ_HIP(hipGetLastError());
     }
@@ -762,6 +876,51 @@ int pfz_dense_upload16(pfz_ctx *ctx, const void *vec, int64_t n, int64_t dim, in
     PFZ_TRY(pool_alloc(ctx, &m->inv, (size_t)(n > 0 ? n : 1) * sizeof(float)));
     if (n > 0)
         PFZ_TRY(dtype == PFZ_DENSE_F16 ? dense_fill16<f16>(ctx, m.p, vec, source) : dense_fill16<bf16>(ctx, m.p, vec, source));
+    *out = m.release();
+    return PFZ_OK;
+}
+
+int pfz_dense_upload8(pfz_ctx *ctx, const void *vec, int64_t n, int64_t dim, int32_t normalize, int32_t source, pfz_dense **out)
+{
+    PFZ_REQUIRE(ctx && out && (n == 0 || vec), "pfz_dense_upload8: NULL argument");
+    PFZ_REQUIRE(n >= 0 && dim >= 1, "pfz_dense_upload8: bad shape %lld x %lld", (long long)n, (long long)dim);
+    PFZ_REQUIRE(source == PFZ_DENSE_SRC_SAME || source == PFZ_DENSE_SRC_F32, "pfz_dense_upload8: unknown source %d", source);
+    if (n >= ((int64_t)1 << 31) - 256) {
+        set_error("pfz_dense_upload8: %lld rows exceed the int32 result indices", (long long)n);
+        return PFZ_ERR_UNSUPPORTED;
+    }
+    constexpr int64_t kMaxDim8 = 131071;     // 128 * 128 * dim <= 2^31 - 1: a dot product of int8 rows fits its int32 sum
+    if (dim > kMaxDim8) {
+        set_error("pfz_dense_upload8: %lld columns exceed the %lld an int32 dot product of int8 rows can hold", (long long)dim,
+                  (long long)kMaxDim8);
+        return PFZ_ERR_UNSUPPORTED;
+    }
+    PFZ_HIP(hipSetDevice(ctx->device));
+    Owner<pfz_dense, pfz_dense_free> m(new pfz_dense());
+    m->ctx = ctx;
+    m->n = n;
+    m->dim = dim;
+    m->dtype = PFZ_DENSE_I8;
+    m->ld = (dim + kBK8 - 1) / kBK8 * kBK8;          // zero columns up to a whole k-chunk, as in pfz_dense_upload
+    m->normalize = normalize ? 1 : 0;
+    PFZ_TRY(pool_alloc(ctx, &m->x8, (size_t)(n > 0 ? n : 1) * (size_t)m->ld));
+    PFZ_TRY(pool_alloc(ctx, &m->inv, (size_t)(n > 0 ? n : 1) * sizeof(float)));
+    if (n > 0) {
+        const dim3 rows4((unsigned)((n + 3) / 4));
+        if (source == PFZ_DENSE_SRC_F32) {
+            // float32 values: uploaded as they are, quantised (and padded) on the device; the row scales land in inv[]
+            DevBuf tmp;      // (freed at the end of this block: stream order keeps it alive until k5_quantize8 is done)
+            PFZ_TRY(tmp.alloc(ctx, (size_t)n * (size_t)dim * sizeof(float)));
+            PFZ_TRY(copy_h2d(ctx, tmp.p, vec, (size_t)n * (size_t)dim * sizeof(float)));
+            hipLaunchKernelGGL(k5_quantize8, rows4, dim3(256), 0, ctx->stream, (const float *)tmp.p, n, dim, m->ld, m->x8, m->inv);
+            PFZ_HIP(hipGetLastError());
+        }
+        else
+            PFZ_TRY(upload_rows_padded(ctx, m->x8, vec, n, dim, m->ld, 1));
+        hipLaunchKernelGGL(k5_inv_norms8, rows4, dim3(256), 0, ctx->stream, (const int8_t *)m->x8, n, m->ld, m->inv, m->normalize,
+                           (int32_t)(source == PFZ_DENSE_SRC_F32));
+        PFZ_HIP(hipGetLastError());
+    }
     *out = m.release();
     return PFZ_OK;
 }
@@ -845,9 +1004,15 @@ int pfz_dense_topn(pfz_ctx *ctx, const pfz_dense *from, const pfz_dense *to, int
                     // 256 x 256 tiles (ld is a whole number of them), blocks of 8 x 4 tiles dealt round-robin to the XCDs
                     const int t16_m = (int)((a1 - a0 + kTile16 - 1) / kTile16), t16_n = (int)(ld / kTile16);
                     const dim3 grid16((unsigned)((((t16_m + 7) / 8) * ((t16_n + 3) / 4) + 7) / 8 * 256));
-                    auto *gemm16 = from->dtype == PFZ_DENSE_F16 ? k5_gemm16_panel<f16> : k5_gemm16_panel<bf16>;
-                    hipLaunchKernelGGL(gemm16, grid16, dim3(512), 0, ctx->stream, (const uint16_t *)from->x16, (const uint16_t *)to->x16,
-                                       from->inv, to->inv, a0, a1, n_to, dim, S, ld, t16_m, t16_n, (float *)M, ld / 64);
+                    if (from->dtype == PFZ_DENSE_I8)
+                        hipLaunchKernelGGL(k5_gemm8_panel<i8>, grid16, dim3(512), 0, ctx->stream, (const int8_t *)from->x8,
+                                           (const int8_t *)to->x8, from->inv, to->inv, a0, a1, n_to, dim, S, ld, t16_m, t16_n, (float *)M,
+                                           ld / 64);
+                    else {
+                        auto *gemm16 = from->dtype == PFZ_DENSE_F16 ? k5_gemm16_panel<f16> : k5_gemm16_panel<bf16>;
+                        hipLaunchKernelGGL(gemm16, grid16, dim3(512), 0, ctx->stream, (const uint16_t *)from->x16, (const uint16_t *)to->x16,
+                                           from->inv, to->inv, a0, a1, n_to, dim, S, ld, t16_m, t16_n, (float *)M, ld / 64);
+                    }
                 }
             }
         }

@@ -41,6 +41,17 @@ class Embeddings(BaseMatcher):
                        vectors changes the scores by about 1e-3 (float16) or 1e-2 (bfloat16) relative per element, which
                        is why this is opt-in: `m = Embeddings(...); m.compute_dtype = "float16"`.  Anything else raises
                        ValueError; it is kept through pickling, and the resident to-side is re-uploaded when it changes.
+        precision: None (default) or "int8", the keyword of sentence-transformers' quantised embeddings:
+                   `m = Embeddings(...); m.precision = "int8"`.  The embeddings are kept as signed 8-bit values on the device
+                   (a quarter of the fp32 footprint) and multiplied on the integer matrix cores with exact int32 sums.  An
+                   np.int8 array is taken as it is; float arrays -- also what an `embedding_method` returns -- are quantised
+                   per row, q = rint(x / max|x| * 127).  The score is the cosine (with cosine_method "sparse" the dot
+                   product: of the integers as given, or of the dequantised rows) OF THE INT8 VECTORS, exact to fp32
+                   rounding.  What quantising float32 embeddings costs: on 300 x 2 000 unit-Gaussian vectors of width 768
+                   the worst |cosine_int8 - cosine_fp32| is 2.1e-3 and the top-1 stays in 293 of 300 rows
+                   (tests/test_dense8_gpu.py prints the figures), which is why this is opt-in.  Signed values only (np.uint8 raises), width <= 131071.
+                   Anything else raises ValueError; with a `compute_dtype` other than None / "float32" `match` raises
+                   ValueError.  Kept through pickling; the resident to-side is re-uploaded when it changes.
     """
     def __init__(self,
                  embedding_method: Optional[Callable[[List[str]], np.ndarray]] = None,
@@ -61,7 +72,8 @@ class Embeddings(BaseMatcher):
         self._dev_to = None            # _lib.DeviceDense of the to-side
         self._dev_to_normalize = None
         self._compute_dtype = None
-        self._dev_to_dtype = None      # compute type the resident to-side was uploaded with
+        self._dev_to_dtype = None      # operand type the resident to-side was uploaded with
+        self._precision = None
 
     @property
     def compute_dtype(self) -> Optional[str]:
@@ -71,6 +83,19 @@ class Embeddings(BaseMatcher):
     def compute_dtype(self, value: Optional[str]):
         _lib.check_compute_dtype(value)
         self._compute_dtype = value
+
+    @property
+    def precision(self) -> Optional[str]:
+        return self._precision
+
+    @precision.setter
+    def precision(self, value: Optional[str]):
+        self._precision = _lib.check_precision(value)
+
+    def _upload(self, ctx, vec, normalize, dtype):
+        if dtype == "int8":
+            return _lib.DeviceDense.upload_int8(ctx, np.asarray(vec), normalize)
+        return _lib.DeviceDense.upload(ctx, np.asarray(vec), normalize, dtype)
 
     def match(self,
               from_list: List[str],
@@ -95,20 +120,25 @@ class Embeddings(BaseMatcher):
                 embeddings_to = self._embed(to_list)
         if self.cosine_method not in _METHODS:
             raise ValueError(f"cosine_method must be one of {_METHODS}")
+        dtype = _lib.check_compute_dtype(self.compute_dtype)
+        if _lib.check_precision(self.precision) == "int8":
+            if dtype != "float32":
+                raise ValueError(f'precision="int8" and compute_dtype={self.compute_dtype!r} name two operand types: '
+                                 'leave compute_dtype at None')
+            dtype = "int8"
         ctx = _lib.Context.default()
         normalize = self.cosine_method != "sparse"        # "sparse": raw dot products (reference _utils.py:74-82)
         lower = float(self.min_similarity) if self.cosine_method in ("sparse", "hip") else 0.0
         # the to-side stays in HBM: match(..., re_train=False) (PolyFuzz.transform, polyfuzz.py:234-240) uploads
         # the new from-vectors only; an explicitly passed to-side is uploaded unless it IS the resident one
         stale = explicit_to and embeddings_to is not self.embeddings_to
-        dtype = _lib.check_compute_dtype(self.compute_dtype)
         if re_train or stale or self._dev_to is None or self._dev_to_normalize != normalize or self._dev_to_dtype != dtype:
-            self._dev_to = _lib.DeviceDense.upload(ctx, np.asarray(embeddings_to), normalize, dtype)
+            self._dev_to = self._upload(ctx, embeddings_to, normalize, dtype)
             self._dev_to_normalize = normalize
             self._dev_to_dtype = dtype
         self_match = to_list is None
         same = self_match and embeddings_to is embeddings_from
-        from_dev = self._dev_to if same else _lib.DeviceDense.upload(ctx, np.asarray(embeddings_from), normalize, dtype)
+        from_dev = self._dev_to if same else self._upload(ctx, embeddings_from, normalize, dtype)
         if from_dev.dim != self._dev_to.dim:
             raise ValueError(f"dense cosine needs two 2-D arrays with equal width, got {from_dev.dim} and {self._dev_to.dim}")
         top_n = clip_top_n(self.top_n, to_list)
@@ -122,7 +152,8 @@ class Embeddings(BaseMatcher):
 
     def __setstate__(self, state):
         self.__dict__.update(state)
-        self.__dict__.setdefault("_compute_dtype", None)      # (pickled before the keyword existed)
+        self.__dict__.setdefault("_compute_dtype", None)      # (pickled before the keywords existed)
+        self.__dict__.setdefault("_precision", None)
         self._dev_to = None
 
     def _embed(self, strings: List[str]) -> np.ndarray:

@@ -289,15 +289,19 @@ class DenseMatchJob:
     all-gather of the padded per-shard top-n blocks.
     compute_dtype "float16" / "bfloat16": both operands are kept as 16-bit values and multiplied on the 16-bit matrix cores
     (_lib.check_compute_dtype): the similarity is that of the 16-bit vectors, float32 input is rounded (about 1e-3 / 1e-2
-    relative per element), so it is opt-in."""
+    relative per element), so it is opt-in.
+    from_shard / to_vectors may also be _lib.DeviceDense handles of this context: they are used as they are (resident
+    16-bit operands, or int8 ones from DeviceDense.upload_int8), and `normalize` / `compute_dtype` do not apply to them."""
 
     def __init__(self, ctx, from_shard, to_vectors, top_n=1, min_similarity=0.0, normalize=True, comm=None,
                  self_match=False, shard_offset=0, rows_per_rank=None, compute_dtype=None):
         self.ctx, self.comm = ctx, comm
         self.top_n, self.min_similarity = int(top_n), float(min_similarity)
         self.self_match, self.shard_offset = bool(self_match), int(shard_offset)
-        self.from_dev = _lib.DeviceDense.upload(ctx, from_shard, normalize, compute_dtype)
-        self.to_dev = self.from_dev if to_vectors is None else _lib.DeviceDense.upload(ctx, to_vectors, normalize, compute_dtype)
+        def resident(vec):
+            return vec if isinstance(vec, _lib.DeviceDense) else _lib.DeviceDense.upload(ctx, vec, normalize, compute_dtype)
+        self.from_dev = resident(from_shard)
+        self.to_dev = self.from_dev if to_vectors is None else resident(to_vectors)
         if to_vectors is None and (not self.self_match or self.shard_offset != 0):
             raise ValueError("to_vectors=None means a whole-matrix self-match (self_match=True, shard_offset=0)")
         self.n_from, self.n_to = self.from_dev.n, self.to_dev.n

@@ -1,4 +1,4 @@
-"""K5 with fp32, float16 and bfloat16 operands on one panel's worth of BASELINE configuration 5, in one process.
+"""K5 with fp32, float16, bfloat16 and int8 operands on one panel's worth of BASELINE configuration 5, in one process.
 
 usage: python tools/bench_dense16.py [--rows 4096] [--to 500000] [--dim 768] [--top-n 5] [--repeats 7] [--out FILE]
 
@@ -6,7 +6,9 @@ Seeded unit-norm random-normal vectors, device-resident operands (pipeline.Dense
 and then timed over `repeats` steps with device events (pfz_event_*), one pair per step; a further profiled pass
 (pfz_prof_*) gives the GEMM's and the row top-n's share.  The fp32 arm is the baseline: the fp32 tile program of the same
 build, on the same data, in the same run.  Roofline figures per arm: the fraction of the 16-bit MFMA peak (2.5 PF; the
-fp32 arm also against its own 157 TF) and the time the fp32 score panel alone takes at 6.3 TB/s.
+fp32 arm also against its own 157 TF, the int8 arm against the integer cores' 5 POPS = twice the 16-bit rate) and the time
+the fp32 score panel alone takes at 6.3 TB/s.  The int8 arm holds the same vectors quantised per row on the device
+(DeviceDense.upload_int8); its yardstick is the bfloat16 arm of the same run.
 Prints one JSON object; --out also writes it to a file.  Run it under a time limit (timeout 600 ...)."""
 import argparse
 import json
@@ -16,7 +18,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 
-PEAK16, PEAK32, HBM = 2.5e15, 157e12, 6.3e12
+PEAK16, PEAK32, PEAK8, HBM = 2.5e15, 157e12, 5.0e15, 6.3e12
 
 
 def main():
@@ -31,7 +33,7 @@ def main():
     if args.repeats < 5:
         ap.error("--repeats must be at least 5")
     import polyfuzz_amd
-    from polyfuzz_amd import pipeline
+    from polyfuzz_amd import _lib, pipeline
     ctx = polyfuzz_amd.Context.default()
 
     rng = np.random.default_rng(5)
@@ -45,8 +47,12 @@ def main():
     res = {"shape": [args.rows, args.to, args.dim], "top_n": args.top_n, "repeats": args.repeats, "device": ctx.info()["name"],
            "data": "seeded unit-norm random normal", "flop": flop, "panel_write_ms_at_6.3TB/s": panel_bytes / HBM * 1e3, "arms": {}}
     top1 = {}
-    for arm, dtype in (("fp32", None), ("f16", "float16"), ("bf16", "bfloat16")):
-        job = pipeline.DenseMatchJob(ctx, a, b, top_n=args.top_n, compute_dtype=dtype)
+    for arm, dtype in (("fp32", None), ("f16", "float16"), ("bf16", "bfloat16"), ("int8", "int8")):
+        if arm == "int8":
+            job = pipeline.DenseMatchJob(ctx, _lib.DeviceDense.upload_int8(ctx, a), _lib.DeviceDense.upload_int8(ctx, b),
+                                         top_n=args.top_n)
+        else:
+            job = pipeline.DenseMatchJob(ctx, a, b, top_n=args.top_n, compute_dtype=dtype)
         for _ in range(2):                        # warm-up: code objects, the pool's panels, clocks
             job.step()
         ctx.sync()
@@ -75,20 +81,26 @@ def main():
             "gemm_over_panel_write_time": gemm_ms / (panel_bytes / HBM * 1e3)}
         if arm == "fp32":
             res["arms"][arm]["gemm_fraction_of_fp32_peak_157TF"] = flop / (gemm_ms * 1e-3) / PEAK32
+        if arm == "int8":
+            res["arms"][arm]["gemm_fraction_of_int8_peak_5POPS"] = flop / (gemm_ms * 1e-3) / PEAK8
         del job, out
     base = res["arms"]["fp32"]
-    for arm in ("f16", "bf16"):
+    for arm in ("f16", "bf16", "int8"):
         r = res["arms"][arm]
         r["speedup_over_fp32"] = base["ms_per_step_median"] / r["ms_per_step_median"]
         # faster by more than the spread of the repeats: the slowest 16-bit step against the fastest fp32 step
         r["beats_fp32_beyond_spread"] = bool(r["ms_max"] < base["ms_min"])
         r["top1_agrees_with_fp32_rows"] = int((top1[arm] == top1["fp32"]).sum())
+    i8, bf = res["arms"]["int8"], res["arms"]["bf16"]
+    i8["step_over_bf16_step"] = i8["ms_per_step_median"] / bf["ms_per_step_median"]
+    i8["gemm_over_bf16_gemm"] = i8["gemm_ms"] / bf["gemm_ms"]
+    i8["no_slower_than_bf16"] = bool(i8["ms_per_step_median"] <= bf["ms_per_step_median"])
     print(json.dumps(res))
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(res, f, indent=1)
-    return 0 if all(res["arms"][k]["beats_fp32_beyond_spread"] for k in ("f16", "bf16")) else 1
+    return 0 if all(res["arms"][k]["beats_fp32_beyond_spread"] for k in ("f16", "bf16", "int8")) and i8["no_slower_than_bf16"] else 1
 
 
 if __name__ == "__main__":
