@@ -372,6 +372,22 @@ int pfz_dense_dtype(const pfz_dense *m, int32_t *dtype);
 int pfz_dense_upload8(pfz_ctx *ctx, const void *vec, int64_t n, int64_t dim, int32_t normalize, int32_t source,
                       pfz_dense **out);
 
+/* Exact rescoring of a coarse top-n, the companion of the 16-bit and int8 operands (reference _embeddings.py:127-133 asks for
+ * the cosines of the vectors as given; quantised embedding search keeps them by searching top_n x k candidates on the cheap
+ * operands and scoring those few against the full-precision vectors).  `candidates` is a result buffer of at least
+ * from_exact->n rows whose idx half holds, per from-row, column indices into `to_exact` -- a pfz_dense_topn result of the
+ * 16-bit / int8 uploads of the same vectors; its val half is ignored.  An index outside [0, n_to), the -1 of an empty slot
+ * among them, is skipped wherever it stands; real indices are distinct within a row (not checked).  For every candidate j of
+ * row i: score = f_from[i] * f_to[j] * sum_k x_i[k] x_j[k] with the operands' own row factors (1 / ||row||, or 1 with
+ * normalize == 0), summed in float64 in one fixed order per pair and rounded to fp32 once: equal to-rows get equal scores,
+ * and the order of a row's candidates does not change its result.  `out` (at least from_exact->n rows of ntop columns, not
+ * the candidate buffer itself) receives the candidates with score > max(lower_bound, 0) by (score descending, column
+ * ascending), the first ntop of them, then (-1, 0).  1 <= ntop <= candidates per row.  Enqueues on the context stream.
+ * PFZ_ERR_INVALID: an operand that is not PFZ_DENSE_F32, unequal widths, fewer candidate rows than from-rows, a result
+ * buffer of another shape; PFZ_ERR_UNSUPPORTED: more than 1024 candidates per row. */
+int pfz_dense_rescore_topn(pfz_ctx *ctx, const pfz_dense *from_exact, const pfz_dense *to_exact, const pfz_topn *candidates,
+                           int32_t ntop, float lower_bound, pfz_topn *out);
+
 /* ---- K6: reductions on the hot path's output --------------------------------
  * precision_recall_curve (reference polyfuzz/metrics.py:12-53): for every threshold p_k
  * (ascending, n_thresholds <= 4096) count_ge[k] = #{i : sim[i] >= p_k} and sum_ge[k] = the sum of

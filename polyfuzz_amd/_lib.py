@@ -105,6 +105,7 @@ SIGNATURES = {
     "pfz_dense_shape": (ctypes.c_int, [c_vp, P(c_i64), P(c_i64)]),
     "pfz_dense_free": (None, [c_vp]),
     "pfz_dense_topn": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_f32, c_i32, c_i64, c_vp]),
+    "pfz_dense_rescore_topn": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_f32, c_vp]),
     "pfz_pr_curve_host": (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp]),
     "pfz_linkage_top1": (ctypes.c_int, [c_vp, c_vp, c_f64, c_vp, c_vp, c_vp]),
     "pfz_comm_unique_id": (ctypes.c_int, [c_vp]),
@@ -849,6 +850,89 @@ def dense_topn(ctx, from_dev, to_dev, ntop, lower_bound, exclude_diag=False, dia
     check(ctx.lib.pfz_dense_topn(ctx.h, from_dev.h, to_dev.h, int(ntop), float(lower_bound), int(bool(exclude_diag)),
                                  int(diag_offset), out.h))
     return out
+
+
+# ---- exact rescoring of a 16-bit / int8 top-n (k5_rescore_topn) ------------------------------------------------------
+
+RESCORE_MAX_CANDIDATES = 1024          # candidates per from-row pfz_dense_rescore_topn ranks in one pass
+
+
+def check_rescore_multiplier(value):
+    """The oversampling factor of a rescored search: None (no rescoring) or an int >= 1.  The coarse search on the 16-bit /
+    int8 operands keeps top_n x value candidates per row, which are then scored against the float32 vectors.  bool, floats,
+    0 and negative values raise ValueError."""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < 1:
+        raise ValueError(f"rescore_multiplier must be None or an int >= 1, got {value!r}")
+    return int(value)
+
+
+def rescore_candidates(ntop, multiplier, n_to, exclude_diag=False):
+    """Candidates per row of a rescored search: min(ntop x multiplier, the to-rows there are -- one less in a self-match),
+    at least ntop.  More than RESCORE_MAX_CANDIDATES raise ValueError."""
+    multiplier = check_rescore_multiplier(multiplier)
+    if multiplier is None:
+        raise ValueError("a rescored search needs a rescore_multiplier (an int >= 1)")
+    m = max(int(ntop), min(int(ntop) * multiplier, int(n_to) - (1 if exclude_diag else 0)))
+    if m > RESCORE_MAX_CANDIDATES:
+        raise ValueError(f"top_n={int(ntop)} with rescore_multiplier={multiplier} asks for {m} candidates per row; the "
+                         f"rescoring kernel takes at most {RESCORE_MAX_CANDIDATES}")
+    return m
+
+
+def dense_rescore(ctx, from_exact, to_exact, candidates, ntop, lower_bound, out=None):
+    """Enqueue pfz_dense_rescore_topn: the columns in the idx half of the DeviceTopN `candidates` (-1: none), scored against
+    the float32 operands in float64 and rounded once; the ntop best with a score > max(lower_bound, 0) by (score descending,
+    column ascending).  Returns the (device-resident) DeviceTopN."""
+    if out is None:
+        out = DeviceTopN.alloc(ctx, from_exact.n, ntop)
+    check(ctx.lib.pfz_dense_rescore_topn(ctx.h, from_exact.h, to_exact.h, candidates.h, int(ntop), float(lower_bound), out.h))
+    return out
+
+
+def dense_topn_rescored(ctx, from_coarse, to_coarse, from_exact, to_exact, ntop, lower_bound, multiplier, exclude_diag=False,
+                        diag_offset=0, out=None, candidates=None):
+    """K5 on the 16-bit / int8 operands for rescore_candidates(ntop, multiplier, ...) candidates per row -- with lower bound
+    0: the user's bound belongs to the exact score, not to the rounded one --, then dense_rescore of those candidates against
+    the float32 operands of the same vectors with the user's bound.  The scores are the fp32 path's; the columns are the
+    fp32 top-n wherever that lies within the candidates.  `candidates`: a DeviceTopN of that many columns to reuse."""
+    m = rescore_candidates(ntop, multiplier, to_coarse.n, exclude_diag)          # (raises before anything is enqueued)
+    if (from_coarse.n, to_coarse.n, from_coarse.dim) != (from_exact.n, to_exact.n, from_exact.dim):
+        raise ValueError(f"the coarse operands {(from_coarse.n, to_coarse.n, from_coarse.dim)} and the exact ones "
+                         f"{(from_exact.n, to_exact.n, from_exact.dim)} are not the same vectors")
+    if candidates is None:
+        candidates = DeviceTopN.alloc(ctx, from_coarse.n, m)
+    elif candidates.ntop != m:
+        raise ValueError(f"the candidate buffer has {candidates.ntop} columns, this search needs {m}")
+    dense_topn(ctx, from_coarse, to_coarse, m, 0.0, exclude_diag, diag_offset, out=candidates)
+    return dense_rescore(ctx, from_exact, to_exact, candidates, ntop, lower_bound, out=out)
+
+
+RESCORE_COARSE = ("int8", "float16", "bfloat16")
+
+
+def dense_rescored_topn_host(ctx, from_vec, to_vec, ntop, lower_bound, coarse, multiplier, exclude_diag=False, normalize=True):
+    """One-shot dense_topn_rescored on float arrays: both are uploaded twice, as `coarse` ("int8", "float16" or "bfloat16")
+    operands and as float32 ones; (idx, val) host arrays out."""
+    if not isinstance(coarse, str) or coarse not in RESCORE_COARSE:
+        raise ValueError(f"coarse must be one of {RESCORE_COARSE}, got {coarse!r}")
+    check_rescore_multiplier(multiplier)
+    same = to_vec is from_vec
+    from_vec, to_vec = np.asarray(from_vec), np.asarray(to_vec)
+    for v in (from_vec, to_vec):
+        if v.ndim != 2 or v.dtype.kind != "f" or v.dtype.itemsize < 4:
+            raise ValueError(f"a rescored search takes 2-D float32 / float64 arrays, got {v.dtype} of shape {v.shape}")
+    if from_vec.shape[1] != to_vec.shape[1]:
+        raise ValueError(f"dense cosine needs two 2-D arrays with equal width, got {from_vec.shape} and {to_vec.shape}")
+    rescore_candidates(ntop, multiplier, to_vec.shape[0], exclude_diag)          # (raises before anything is uploaded)
+    def upload_coarse(vec):
+        return DeviceDense.upload_int8(ctx, vec, normalize) if coarse == "int8" else DeviceDense.upload(ctx, vec, normalize, coarse)
+    a_c = upload_coarse(from_vec)
+    b_c = a_c if same else upload_coarse(to_vec)
+    a_x = DeviceDense.upload(ctx, from_vec, normalize)
+    b_x = a_x if same else DeviceDense.upload(ctx, to_vec, normalize)
+    return dense_topn_rescored(ctx, a_c, b_c, a_x, b_x, ntop, lower_bound, multiplier, exclude_diag).download()
 
 
 def pr_curve(ctx, sims, thresholds):

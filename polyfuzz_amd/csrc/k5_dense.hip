@@ -24,6 +24,9 @@
 //                         blocks that reach it, without M it streams the row (float4); threshold filter, 64-bit
 //                         keys score_bits<<32 | ~col, compaction by wave-max rounds (same scheme as K3), writes
 //                         (idx, score) by (score desc, col asc).
+//   k5_rescore_topn     : the companion of the 16-bit / int8 operands (pfz_dense_rescore_topn, opt-in): workgroup per
+//                         from-row, wave per candidate column of a coarse top-m; the exact score of the fp32 vectors
+//                         (float64 sum in a fixed order, rounded once), the same keys, ranked in LDS.
 #include "pfz_internal.h"
 
 #include <algorithm>
@@ -750,6 +753,105 @@ __global__ __launch_bounds__(256) void k5_row_topn(const float *__restrict__ S, 
     if (kDeep && lane == 0) ub[row - a0] = cnt >= ntop ? cand[ntop - 1] : 0ull;
 }
 
+// ---- exact rescoring of a coarse top-m ------------------------------------------------------------------------------
+// The 16-bit and int8 operands return the ranking of the ROUNDED vectors.  This kernel takes such a result as a candidate
+// table -- cand[row][0 .. m), column indices into B, anything outside [0, n_b) (the -1 of an empty slot) skipped wherever
+// it stands, real indices distinct within a row -- and scores the candidates against the fp32 vectors:
+// score = inv_a[row] inv_b[j] sum_k A[row][k] B[j][k].  One workgroup per from-row, whose vector is shared through LDS
+// (kRowInLds: ld <= kRescoreLds floats) or re-read from L2; one wave per candidate at a time, a lane reading 16 B of every
+// 1 KiB of the to-row (ld is a multiple of 32 floats: every row starts on a 128 B line and a float4 never crosses the end).
+// The sum is float64 -- the product of two floats is exact in it -- in ONE order for a pair whichever wave or slot
+// computes it: lane l adds its elements k = 4 l + 256 c + {0, 1, 2, 3} in ascending order, then a xor butterfly over the
+// lanes (commutative steps: every lane ends with the same bits), and the product with the two factors is rounded to fp32
+// once.  So equal to-rows give equal scores and a permuted candidate list gives the same result.  Gathering m rows of
+// 4 ld bytes per from-row, the kernel is bandwidth-bound; the fp64 rate does not show.
+// Keys as in k5_row_topn (score bits << 32 | ~column; 0: dropped, scores must be > max(lower_bound, 0)) go to LDS and are
+// ranked there: a thread counts the keys above each of its own (m LDS broadcasts) and writes the key of rank r < ntop to
+// column r; the columns from the number of keys on are filled with (-1, 0).
+constexpr int kRescoreMax = 1024;      // candidates per row: 8 KiB of keys
+constexpr int kRescoreLds = 4096;      // widest from-row kept in LDS: 16 KiB
+
+template <bool kRowInLds>
+__global__ __launch_bounds__(256) void k5_rescore_topn(const float *__restrict__ A, const float *__restrict__ inv_a, int64_t n_a,
+                                                        const float *__restrict__ B, const float *__restrict__ inv_b, int64_t n_b,
+                                                        int64_t ld, const int32_t *__restrict__ cand, int32_t m, int32_t ntop,
+                                                        float lower_bound, int32_t *__restrict__ out_idx,
+                                                        float *__restrict__ out_val)
+{
+    __shared__ __attribute__((aligned(16))) uint64_t keys[kRescoreMax];
+    __shared__ __attribute__((aligned(16))) float xs[kRowInLds ? kRescoreLds : 4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int64_t row = blockIdx.x; row < n_a; row += gridDim.x) {
+        const float *xa = A + row * ld;
+        if (kRowInLds) {
+            for (int k = tid * 4; k < (int)ld; k += 1024) *(float4 *)(xs + k) = *(const float4 *)(xa + k);
+            __syncthreads();
+        }
+        const double fa = (double)inv_a[row];
+        const int32_t *c = cand + row * m;
+        for (int slot = wave; slot < m; slot += 4) {
+            const int32_t j = __builtin_amdgcn_readfirstlane(c[slot]);
+            uint64_t key = 0ull;
+            if (j >= 0 && j < n_b) {
+                const float *xb = B + (int64_t)j * ld;
+                double acc = 0.0;
+                for (int64_t k0 = 0; k0 < ld; k0 += 1024) {      // four 1 KiB loads of the to-row in flight per wave
+                    float4 a[4], b[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const int64_t k = k0 + u * 256 + lane * 4;
+                        const bool in = k < ld;
+                        b[u] = in ? *(const float4 *)(xb + k) : zero;
+                        if (kRowInLds) a[u] = in ? *(const float4 *)(xs + k) : zero;
+                        else a[u] = in ? *(const float4 *)(xa + k) : zero;
+                    }
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        acc = fma((double)a[u].x, (double)b[u].x, acc);
+                        acc = fma((double)a[u].y, (double)b[u].y, acc);
+                        acc = fma((double)a[u].z, (double)b[u].z, acc);
+                        acc = fma((double)a[u].w, (double)b[u].w, acc);
+                    }
+                }
+#pragma unroll
+                for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
+                const float s = (float)(fa * (double)inv_b[j] * acc);
+                if (s > lower_bound) key = ((uint64_t)__float_as_uint(s) << 32) | (uint32_t)(~(uint32_t)j);
+            }
+            if (lane == 0) keys[slot] = key;
+        }
+        __syncthreads();
+        uint64_t mine[kRescoreMax / 256];
+        int rank[kRescoreMax / 256];
+#pragma unroll
+        for (int u = 0; u < kRescoreMax / 256; ++u) {
+            mine[u] = tid + 256 * u < m ? keys[tid + 256 * u] : 0ull;
+            rank[u] = 0;
+        }
+        int n_keys = 0;
+        for (int q = 0; q < m; ++q) {
+            const uint64_t k = keys[q];
+            n_keys += k != 0ull;
+#pragma unroll
+            for (int u = 0; u < kRescoreMax / 256; ++u) rank[u] += k > mine[u];
+        }
+        int32_t *oi = out_idx + row * ntop;
+        float *ov = out_val + row * ntop;
+#pragma unroll
+        for (int u = 0; u < kRescoreMax / 256; ++u)
+            if (mine[u] && rank[u] < ntop) {
+                oi[rank[u]] = (int32_t)(~(uint32_t)mine[u]);
+                ov[rank[u]] = __uint_as_float((uint32_t)(mine[u] >> 32));
+            }
+        for (int r = n_keys + tid; r < ntop; r += 256) {
+            oi[r] = -1;
+            ov[r] = 0.f;
+        }
+        __syncthreads();      // the next row reuses keys and xs
+    }
+}
+
 }  // namespace pfz
 
 using namespace pfz;
@@ -1047,6 +1149,43 @@ int pfz_dense_topn(pfz_ctx *ctx, const pfz_dense *from, const pfz_dense *to, int
     }
     PFZ_HIP(hipGetLastError());
     return PFZ_OK;     // (the score panels go back to the pool: stream order keeps them alive until the kernels are done)
+}
+
+int pfz_dense_rescore_topn(pfz_ctx *ctx, const pfz_dense *from_exact, const pfz_dense *to_exact, const pfz_topn *candidates,
+                           int32_t ntop, float lower_bound, pfz_topn *out)
+{
+    PFZ_REQUIRE(ctx && from_exact && to_exact && candidates && out, "pfz_dense_rescore_topn: NULL argument");
+    PFZ_REQUIRE(from_exact->dtype == PFZ_DENSE_F32 && to_exact->dtype == PFZ_DENSE_F32,
+                "pfz_dense_rescore_topn: the exact operands must be float32, got %s from-vectors and %s to-vectors",
+                dense_dtype_name(from_exact->dtype), dense_dtype_name(to_exact->dtype));
+    PFZ_REQUIRE(from_exact->dim == to_exact->dim, "pfz_dense_rescore_topn: from-vectors have %lld columns, to-vectors %lld",
+                (long long)from_exact->dim, (long long)to_exact->dim);
+    PFZ_REQUIRE(candidates != out, "pfz_dense_rescore_topn: the candidate table and the result are one buffer");
+    PFZ_REQUIRE(candidates->n_rows >= from_exact->n, "pfz_dense_rescore_topn: the candidate table has %lld rows, the from-vectors %lld",
+                (long long)candidates->n_rows, (long long)from_exact->n);
+    const int32_t m = candidates->ntop;
+    if (m > kRescoreMax) {
+        set_error("pfz_dense_rescore_topn: %d candidates per row exceed the %d one pass ranks", m, kRescoreMax);
+        return PFZ_ERR_UNSUPPORTED;
+    }
+    PFZ_REQUIRE(ntop >= 1 && ntop <= m, "pfz_dense_rescore_topn: ntop %d is outside 1 .. %d, the candidates per row", ntop, m);
+    PFZ_REQUIRE(lower_bound == lower_bound, "pfz_dense_rescore_topn: lower_bound is NaN");
+    PFZ_REQUIRE(out->n_rows >= from_exact->n && out->ntop == ntop, "pfz_dense_rescore_topn: result buffer is %lldx%d, need %lldx%d",
+                (long long)out->n_rows, out->ntop, (long long)from_exact->n, ntop);
+    const int64_t n_from = from_exact->n;
+    if (n_from == 0) return PFZ_OK;
+    PFZ_HIP(hipSetDevice(ctx->device));
+    if (lower_bound < 0.f) lower_bound = 0.f;   // non-positive similarities are "no match" (_utils.py:122-123)
+    {
+        ProfScope ps(ctx, "k5_rescore_topn");
+        auto *kernel = from_exact->ld <= kRescoreLds ? k5_rescore_topn<true> : k5_rescore_topn<false>;
+        const dim3 grid((unsigned)std::min<int64_t>(n_from, (int64_t)1 << 20));
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, ctx->stream, (const float *)from_exact->x, (const float *)from_exact->inv, n_from,
+                           (const float *)to_exact->x, (const float *)to_exact->inv, to_exact->n, from_exact->ld,
+                           (const int32_t *)candidates->idx, m, ntop, lower_bound, out->idx, out->val);
+    }
+    PFZ_HIP(hipGetLastError());
+    return PFZ_OK;
 }
 
 static int dense_topn_host(pfz_ctx *ctx, const float *from_vec, int64_t n_from, const float *to_vec, int64_t n_to,

@@ -52,6 +52,21 @@ class Embeddings(BaseMatcher):
                    (tests/test_dense8_gpu.py prints the figures), which is why this is opt-in.  Signed values only (np.uint8 raises), width <= 131071.
                    Anything else raises ValueError; with a `compute_dtype` other than None / "float32" `match` raises
                    ValueError.  Kept through pickling; the resident to-side is re-uploaded when it changes.
+        rescore_multiplier: None (default: `match` is exactly as above) or an int >= 1, for the 16-bit and int8 operand types:
+                   `m.precision = "int8"; m.rescore_multiplier = 4`.  The search on the cheap operands then keeps
+                   top_n x rescore_multiplier candidates per row (clipped to the to-strings there are; at most 1024), and
+                   those few are scored against the float32 vectors, which are kept on the device beside the cheap ones
+                   (k5_rescore_topn: float64 sums, rounded once).  What is exact: every Similarity is the fp32 path's score
+                   of the ORIGINAL vectors (1e-5), `min_similarity` cuts on that score, and the order is that of those
+                   scores.  What is not: the set of columns is the fp32 top-n only where that lies within the coarse
+                   candidates.  Measured on 300 x 2 000 unit-Gaussian vectors of width 768, top-5
+                   (tests/test_dense_rescore_gpu.py prints the figures): plain int8 returns other columns than the float64 oracle in 75 of 300 rows and plain bfloat16 in 15; of the 1 500 exact top-5 entries the int8 candidates
+                   miss 26 at a multiplier of 1 and none at 2 or 4 (bfloat16: 2 and none), and with rescore_multiplier = 4 both types agree
+                   with the oracle in all 300 rows.  A guarantee it is not: data whose coarse ranking is off by more than
+                   the multiplier's margin loses those columns.
+                   `match` raises ValueError when it is set and the operands are float32 (nothing to rescore), or when
+                   the embeddings handed in are np.int8 / np.float16 / raw bfloat16 (np.uint16) arrays: there are no
+                   full-precision vectors to rescore against.  Kept through pickling; changing it alone re-uploads nothing.
     """
     def __init__(self,
                  embedding_method: Optional[Callable[[List[str]], np.ndarray]] = None,
@@ -74,6 +89,8 @@ class Embeddings(BaseMatcher):
         self._compute_dtype = None
         self._dev_to_dtype = None      # operand type the resident to-side was uploaded with
         self._precision = None
+        self._rescore_multiplier = None
+        self._dev_to_exact = None      # float32 DeviceDense of the to-side, beside _dev_to, while rescoring is on
 
     @property
     def compute_dtype(self) -> Optional[str]:
@@ -91,6 +108,14 @@ class Embeddings(BaseMatcher):
     @precision.setter
     def precision(self, value: Optional[str]):
         self._precision = _lib.check_precision(value)
+
+    @property
+    def rescore_multiplier(self) -> Optional[int]:
+        return self._rescore_multiplier
+
+    @rescore_multiplier.setter
+    def rescore_multiplier(self, value: Optional[int]):
+        self._rescore_multiplier = _lib.check_rescore_multiplier(value)
 
     def _upload(self, ctx, vec, normalize, dtype):
         if dtype == "int8":
@@ -126,6 +151,15 @@ class Embeddings(BaseMatcher):
                 raise ValueError(f'precision="int8" and compute_dtype={self.compute_dtype!r} name two operand types: '
                                  'leave compute_dtype at None')
             dtype = "int8"
+        multiplier = _lib.check_rescore_multiplier(self.rescore_multiplier)
+        if multiplier is not None:
+            if dtype == "float32":
+                raise ValueError("rescore_multiplier is set but the operands are float32: there is nothing to rescore "
+                                 '(set precision="int8" or a 16-bit compute_dtype, or leave rescore_multiplier at None)')
+            for side, vec in (("embeddings_from", embeddings_from), ("embeddings_to", embeddings_to)):
+                if np.asarray(vec).dtype in (np.int8, np.float16, np.uint16):
+                    raise ValueError(f"rescore_multiplier is set but {side} is already a {np.asarray(vec).dtype} array: "
+                                     "there are no full-precision vectors to rescore against (pass float32 embeddings)")
         ctx = _lib.Context.default()
         normalize = self.cosine_method != "sparse"        # "sparse": raw dot products (reference _utils.py:74-82)
         lower = float(self.min_similarity) if self.cosine_method in ("sparse", "hip") else 0.0
@@ -136,25 +170,35 @@ class Embeddings(BaseMatcher):
             self._dev_to = self._upload(ctx, embeddings_to, normalize, dtype)
             self._dev_to_normalize = normalize
             self._dev_to_dtype = dtype
+            self._dev_to_exact = None
+        if multiplier is not None and self._dev_to_exact is None:      # (follows every re-upload of the coarse to-side)
+            self._dev_to_exact = self._upload(ctx, embeddings_to, normalize, "float32")
         self_match = to_list is None
         same = self_match and embeddings_to is embeddings_from
         from_dev = self._dev_to if same else self._upload(ctx, embeddings_from, normalize, dtype)
         if from_dev.dim != self._dev_to.dim:
             raise ValueError(f"dense cosine needs two 2-D arrays with equal width, got {from_dev.dim} and {self._dev_to.dim}")
         top_n = clip_top_n(self.top_n, to_list)
-        idx, val = _lib.dense_topn(ctx, from_dev, self._dev_to, max(top_n, 1), lower, exclude_diag=self_match).download()
+        if multiplier is not None:
+            from_exact = self._dev_to_exact if same else self._upload(ctx, embeddings_from, normalize, "float32")
+            idx, val = _lib.dense_topn_rescored(ctx, from_dev, self._dev_to, from_exact, self._dev_to_exact, max(top_n, 1), lower,
+                                                multiplier, exclude_diag=self_match).download()
+        else:
+            idx, val = _lib.dense_topn(ctx, from_dev, self._dev_to, max(top_n, 1), lower, exclude_diag=self_match).download()
         self.embeddings_to = embeddings_to
         return topn_to_frame(idx, val, from_list, from_list if self_match else to_list, top_n)
 
     # a matcher is pickled by joblib (reference polyfuzz.py:429-457): the device copy stays behind
     def __getstate__(self):
-        return {k: v for k, v in self.__dict__.items() if k not in ("_dev_to",)}
+        return {k: v for k, v in self.__dict__.items() if k not in ("_dev_to", "_dev_to_exact")}
 
     def __setstate__(self, state):
         self.__dict__.update(state)
         self.__dict__.setdefault("_compute_dtype", None)      # (pickled before the keywords existed)
         self.__dict__.setdefault("_precision", None)
+        self.__dict__.setdefault("_rescore_multiplier", None)
         self._dev_to = None
+        self._dev_to_exact = None
 
     def _embed(self, strings: List[str]) -> np.ndarray:
         """ Embed with the user's callable and L2-normalise the rows (reference _embeddings.py:136-145) """

@@ -291,10 +291,16 @@ class DenseMatchJob:
     (_lib.check_compute_dtype): the similarity is that of the 16-bit vectors, float32 input is rounded (about 1e-3 / 1e-2
     relative per element), so it is opt-in.
     from_shard / to_vectors may also be _lib.DeviceDense handles of this context: they are used as they are (resident
-    16-bit operands, or int8 ones from DeviceDense.upload_int8), and `normalize` / `compute_dtype` do not apply to them."""
+    16-bit operands, or int8 ones from DeviceDense.upload_int8), and `normalize` / `compute_dtype` do not apply to them.
+    rescore_multiplier (an int >= 1, with 16-bit or int8 operands): a step searches top_n x rescore_multiplier candidates per
+    row on those operands and scores them against the float32 form of the same vectors, rescore_from / rescore_to -- arrays
+    (uploaded here with `normalize`) or float32 DeviceDense handles of this context; rescore_to=None with to_vectors=None
+    is the from-side again (_lib.dense_topn_rescored).  The scores and `min_similarity` are then the fp32 path's; the
+    candidate buffer is allocated here, once."""
 
     def __init__(self, ctx, from_shard, to_vectors, top_n=1, min_similarity=0.0, normalize=True, comm=None,
-                 self_match=False, shard_offset=0, rows_per_rank=None, compute_dtype=None):
+                 self_match=False, shard_offset=0, rows_per_rank=None, rescore_from=None, rescore_to=None,
+                 rescore_multiplier=None, compute_dtype=None):
         self.ctx, self.comm = ctx, comm
         self.top_n, self.min_similarity = int(top_n), float(min_similarity)
         self.self_match, self.shard_offset = bool(self_match), int(shard_offset)
@@ -305,6 +311,26 @@ class DenseMatchJob:
         if to_vectors is None and (not self.self_match or self.shard_offset != 0):
             raise ValueError("to_vectors=None means a whole-matrix self-match (self_match=True, shard_offset=0)")
         self.n_from, self.n_to = self.from_dev.n, self.to_dev.n
+        self.rescore_multiplier = _lib.check_rescore_multiplier(rescore_multiplier)
+        self.from_exact = self.to_exact = self.candidates = None
+        if self.rescore_multiplier is None:
+            if rescore_from is not None or rescore_to is not None:
+                raise ValueError("rescore_from / rescore_to are given without a rescore_multiplier")
+        else:
+            if self.from_dev.dtype == "float32" or self.to_dev.dtype == "float32":
+                raise ValueError("rescore_multiplier is set but the operands are float32: there is nothing to rescore")
+            if rescore_from is None or (rescore_to is None and to_vectors is not None):
+                raise ValueError("rescore_multiplier needs the float32 vectors of both sides: rescore_from and rescore_to")
+            def exact(vec):
+                return vec if isinstance(vec, _lib.DeviceDense) else _lib.DeviceDense.upload(ctx, vec, normalize)
+            self.from_exact = exact(rescore_from)
+            self.to_exact = self.from_exact if rescore_to is None else exact(rescore_to)
+            for coarse, fine in ((self.from_dev, self.from_exact), (self.to_dev, self.to_exact)):
+                if fine.dtype != "float32" or (fine.n, fine.dim) != (coarse.n, coarse.dim):
+                    raise ValueError(f"the rescoring operand is {fine.dtype} {(fine.n, fine.dim)}; it must be the float32 form "
+                                     f"of the {(coarse.n, coarse.dim)} vectors that are searched")
+            m = _lib.rescore_candidates(self.top_n, self.rescore_multiplier, self.n_to, self.self_match)
+            self.candidates = _lib.DeviceTopN.alloc(ctx, self.n_from, m)
         self.rows_per_rank = self.n_from if rows_per_rank is None else int(rows_per_rank)
         if self.rows_per_rank < self.n_from:
             raise ValueError("rows_per_rank is smaller than this rank's shard")
@@ -315,8 +341,13 @@ class DenseMatchJob:
             self.gathered = _lib.DeviceTopN.alloc(ctx, self.rows_per_rank * comm.world, self.top_n)
 
     def step(self):
-        _lib.dense_topn(self.ctx, self.from_dev, self.to_dev, self.top_n, self.min_similarity,
-                        exclude_diag=self.self_match, diag_offset=self.shard_offset, out=self.local)
+        if self.candidates is not None:
+            _lib.dense_topn_rescored(self.ctx, self.from_dev, self.to_dev, self.from_exact, self.to_exact, self.top_n,
+                                     self.min_similarity, self.rescore_multiplier, exclude_diag=self.self_match,
+                                     diag_offset=self.shard_offset, out=self.local, candidates=self.candidates)
+        else:
+            _lib.dense_topn(self.ctx, self.from_dev, self.to_dev, self.top_n, self.min_similarity,
+                            exclude_diag=self.self_match, diag_offset=self.shard_offset, out=self.local)
         if self.gathered is not None:
             self.comm.allgather_topn(self.local, self.gathered)
         return self.gathered if self.gathered is not None else self.local
