@@ -729,6 +729,8 @@ def indel_matrix(ctx, from_dev, to_dev, begin=0, end=None):
 # compute_dtype of the dense path -> PFZ_DENSE_* (include/polyfuzz_hip.h)
 DENSE_DTYPES = {"float32": 0, "float16": 1, "bfloat16": 2}
 _DENSE_SRC_SAME, _DENSE_SRC_F32 = 0, 1
+# every operand type of the dense path: what the two public keywords, `compute_dtype` and `precision`, choose between
+OPERAND_TYPES = ("float32", "float16", "bfloat16", "int8")
 
 
 def check_compute_dtype(compute_dtype):
@@ -747,12 +749,9 @@ def dense_cossim_topn_host(ctx, from_vec, to_vec, ntop, lower_bound, exclude_dia
     """normalize=False: raw dot products (the reference's "sparse" back-end on dense input).
     compute_dtype: see check_compute_dtype -- with "float16" / "bfloat16" the scores are those of the 16-bit vectors
     (float32 input is rounded: about 1e-3 / 1e-2 relative per element), so it is opt-in; None / "float32" is the fp32 path."""
-    if check_compute_dtype(compute_dtype) != "float32":
-        a = DeviceDense.upload(ctx, from_vec, normalize, compute_dtype)
-        b = a if to_vec is from_vec else DeviceDense.upload(ctx, to_vec, normalize, compute_dtype)
-        if a.dim != b.dim:
-            raise ValueError(f"dense cosine needs two 2-D arrays with equal width, got {(a.n, a.dim)} and {(b.n, b.dim)}")
-        return dense_topn(ctx, a, b, ntop, lower_bound, exclude_diag).download()
+    operand = check_compute_dtype(compute_dtype)
+    if operand != "float32":
+        return _dense_topn_host(ctx, from_vec, to_vec, ntop, lower_bound, exclude_diag, normalize, operand)
     a = np.ascontiguousarray(from_vec, np.float32)
     b = np.ascontiguousarray(to_vec, np.float32)
     if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1]:
@@ -776,19 +775,76 @@ def check_precision(precision):
     raise ValueError(f'precision must be None or "int8", got {precision!r}')
 
 
+def operand_type(compute_dtype=None, precision=None):
+    """The one of OPERAND_TYPES the two keywords name together; ValueError when either is invalid or both name a type."""
+    name = check_compute_dtype(compute_dtype)
+    if check_precision(precision) is None:
+        return name
+    if name != "float32":
+        raise ValueError(f'precision="int8" and compute_dtype={compute_dtype!r} name two operand types: '
+                         'leave compute_dtype at None')
+    return "int8"
+
+
+def _dense_topn_host(ctx, from_vec, to_vec, ntop, lower_bound, exclude_diag, normalize, operand, multiplier=None):
+    """The one-shots' common body: upload both sides as `operand` (one handle when to_vec is from_vec), run K5 -- with a
+    `multiplier` rescored against float32 uploads of the same arrays -- and download (idx, val)."""
+    same = to_vec is from_vec
+    a = DeviceDense.upload_as(ctx, from_vec, operand, normalize)
+    b = a if same else DeviceDense.upload_as(ctx, to_vec, operand, normalize)
+    if a.dim != b.dim:
+        raise ValueError(f"dense cosine needs two 2-D arrays with equal width, got {(a.n, a.dim)} and {(b.n, b.dim)}")
+    if multiplier is None:
+        return dense_topn(ctx, a, b, ntop, lower_bound, exclude_diag).download()
+    a_x = DeviceDense.upload_as(ctx, from_vec, "float32", normalize)
+    b_x = a_x if same else DeviceDense.upload_as(ctx, to_vec, "float32", normalize)
+    return dense_topn_rescored(ctx, a, b, a_x, b_x, ntop, lower_bound, multiplier, exclude_diag).download()
+
+
 def dense_int8_topn_host(ctx, from_vec, to_vec, ntop, lower_bound, exclude_diag=False, normalize=True):
     """dense_cossim_topn_host on int8 operands (DeviceDense.upload_int8): np.int8 arrays as they are, float arrays quantised
     per row.  normalize=False: raw dot products -- of the integers as given, or of the dequantised rows."""
-    a = DeviceDense.upload_int8(ctx, from_vec, normalize)
-    b = a if to_vec is from_vec else DeviceDense.upload_int8(ctx, to_vec, normalize)
-    if a.dim != b.dim:
-        raise ValueError(f"dense cosine needs two 2-D arrays with equal width, got {(a.n, a.dim)} and {(b.n, b.dim)}")
-    return dense_topn(ctx, a, b, ntop, lower_bound, exclude_diag).download()
+    return _dense_topn_host(ctx, from_vec, to_vec, ntop, lower_bound, exclude_diag, normalize, "int8")
+
+
+# operand type -> (the numpy dtype that is uploaded as it is -- any other float array goes up as float32 and is converted on
+# the device; None: everything is widened to float32 --, what the refusal of any other dtype says, the C entry point and its
+# arguments between `normalize` and the handle)
+_OPERANDS = {
+    "float32": (None, None, "pfz_dense_upload", lambda source: ()),
+    "float16": (np.float16, "compute_dtype='float16' takes a float array",
+                "pfz_dense_upload16", lambda source: (DENSE_DTYPES["float16"], source)),
+    "bfloat16": (np.uint16, "compute_dtype='bfloat16' takes a float array or raw bfloat16 bits as uint16",
+                 "pfz_dense_upload16", lambda source: (DENSE_DTYPES["bfloat16"], source)),
+    "int8": (np.int8, "int8 precision takes an int8 or a float array", "pfz_dense_upload8", lambda source: (source,)),
+}
 
 
 class DeviceDense(_Handle):
     """Device-resident row-major matrix (fp32, float16 / bfloat16 or int8 values) + the per-row factors (K5 operand)."""
     _free = "pfz_dense_free"
+
+    @classmethod
+    def upload_as(cls, ctx, vec, operand, normalize=True):
+        """The one upload: `vec` as `operand`, one of OPERAND_TYPES (see upload and upload_int8 for what each takes)."""
+        if not isinstance(operand, str) or operand not in _OPERANDS:
+            raise ValueError(f"operand must be one of {OPERAND_TYPES}, got {operand!r}")
+        as_given, takes, entry, extra = _OPERANDS[operand]
+        vec = np.asarray(vec)
+        if vec.ndim != 2:
+            raise ValueError(f"dense vectors must be a 2-D array, got shape {vec.shape}")
+        given = as_given is not None and vec.dtype == as_given
+        if takes is not None and not given and vec.dtype.kind != "f":
+            raise ValueError(f"{takes}, got {vec.dtype}"
+                             + (" (unsigned values are not supported: shifting them by 128 changes the cosine)"
+                                if operand == "int8" and vec.dtype == np.uint8 else ""))
+        a = np.ascontiguousarray(vec) if given else np.ascontiguousarray(vec, np.float32)
+        h = c_vp()
+        check(getattr(ctx.lib, entry)(ctx.h, _ptr(a) if a.size else None, a.shape[0], max(a.shape[1], 1), int(bool(normalize)),
+                                      *extra(_DENSE_SRC_SAME if given else _DENSE_SRC_F32), ctypes.byref(h)))
+        m = cls(ctx, h)
+        m.n, m.dim, m.normalize, m.dtype = a.shape[0], a.shape[1], bool(normalize), operand
+        return m
 
     @classmethod
     def upload(cls, ctx, vec, normalize=True, compute_dtype=None):
@@ -797,26 +853,7 @@ class DeviceDense(_Handle):
         the device.  "bfloat16": a np.uint16 array is taken as raw bfloat16 bits (numpy has no such dtype), a float array is
         rounded on the device.  The similarity is then that of the 16-bit vectors: rounding float32 vectors changes the
         scores by about 1e-3 (float16) or 1e-2 (bfloat16) relative per element, which is why this is opt-in."""
-        name = check_compute_dtype(compute_dtype)
-        vec = np.asarray(vec)
-        if vec.ndim != 2:
-            raise ValueError(f"dense vectors must be a 2-D array, got shape {vec.shape}")
-        h = c_vp()
-        if name == "float32":
-            a = np.ascontiguousarray(vec, np.float32)
-            check(ctx.lib.pfz_dense_upload(ctx.h, _ptr(a) if a.size else None, a.shape[0], max(a.shape[1], 1), int(bool(normalize)),
-                                           ctypes.byref(h)))
-        else:
-            given = vec.dtype == (np.float16 if name == "float16" else np.uint16)
-            if not given and vec.dtype.kind != "f":
-                raise ValueError(f"compute_dtype={name!r} takes a float array"
-                                 + (" or raw bfloat16 bits as uint16" if name == "bfloat16" else "") + f", got {vec.dtype}")
-            a = np.ascontiguousarray(vec) if given else np.ascontiguousarray(vec, np.float32)
-            check(ctx.lib.pfz_dense_upload16(ctx.h, _ptr(a) if a.size else None, a.shape[0], max(a.shape[1], 1), int(bool(normalize)),
-                                             DENSE_DTYPES[name], _DENSE_SRC_SAME if given else _DENSE_SRC_F32, ctypes.byref(h)))
-        m = cls(ctx, h)
-        m.n, m.dim, m.normalize, m.dtype = a.shape[0], a.shape[1], bool(normalize), name
-        return m
+        return cls.upload_as(ctx, vec, check_compute_dtype(compute_dtype), normalize)
 
     @classmethod
     def upload_int8(cls, ctx, vec, normalize=True):
@@ -826,21 +863,7 @@ class DeviceDense(_Handle):
         normalize=False the dot products: of the integers as given, or of the dequantised rows q * scale.
         Widths up to 131071 (an int32 dot product of int8 rows).  Any other dtype raises ValueError, uint8 among them: the
         integer matrix cores are signed, and shifting by 128 changes the cosine."""
-        vec = np.asarray(vec)
-        if vec.ndim != 2:
-            raise ValueError(f"dense vectors must be a 2-D array, got shape {vec.shape}")
-        given = vec.dtype == np.int8
-        if not given and vec.dtype.kind != "f":
-            raise ValueError(f"int8 precision takes an int8 or a float array, got {vec.dtype}"
-                             + (" (unsigned values are not supported: shifting them by 128 changes the cosine)"
-                                if vec.dtype == np.uint8 else ""))
-        a = np.ascontiguousarray(vec) if given else np.ascontiguousarray(vec, np.float32)
-        h = c_vp()
-        check(ctx.lib.pfz_dense_upload8(ctx.h, _ptr(a) if a.size else None, a.shape[0], max(a.shape[1], 1), int(bool(normalize)),
-                                        _DENSE_SRC_SAME if given else _DENSE_SRC_F32, ctypes.byref(h)))
-        m = cls(ctx, h)
-        m.n, m.dim, m.normalize, m.dtype = a.shape[0], a.shape[1], bool(normalize), "int8"
-        return m
+        return cls.upload_as(ctx, vec, "int8", normalize)
 
 
 def dense_topn(ctx, from_dev, to_dev, ntop, lower_bound, exclude_diag=False, diag_offset=0, out=None):
@@ -926,13 +949,7 @@ def dense_rescored_topn_host(ctx, from_vec, to_vec, ntop, lower_bound, coarse, m
     if from_vec.shape[1] != to_vec.shape[1]:
         raise ValueError(f"dense cosine needs two 2-D arrays with equal width, got {from_vec.shape} and {to_vec.shape}")
     rescore_candidates(ntop, multiplier, to_vec.shape[0], exclude_diag)          # (raises before anything is uploaded)
-    def upload_coarse(vec):
-        return DeviceDense.upload_int8(ctx, vec, normalize) if coarse == "int8" else DeviceDense.upload(ctx, vec, normalize, coarse)
-    a_c = upload_coarse(from_vec)
-    b_c = a_c if same else upload_coarse(to_vec)
-    a_x = DeviceDense.upload(ctx, from_vec, normalize)
-    b_x = a_x if same else DeviceDense.upload(ctx, to_vec, normalize)
-    return dense_topn_rescored(ctx, a_c, b_c, a_x, b_x, ntop, lower_bound, multiplier, exclude_diag).download()
+    return _dense_topn_host(ctx, from_vec, from_vec if same else to_vec, ntop, lower_bound, exclude_diag, normalize, coarse, multiplier)
 
 
 def pr_curve(ctx, sims, thresholds):

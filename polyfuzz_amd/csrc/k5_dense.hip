@@ -7,7 +7,7 @@
 // diagonal excluded for self-match.
 //
 // Plan:
-//   k5_inv_norms        : 1/||row|| for both matrices (wave per row).
+//   k5_inv_norms<T>     : 1/||row|| of the stored values, for every operand type T (wave per row).
 //   k5_gemm_panel_pipe  : S[P x n_to] = A_panel . B^T scaled by both inverse norms (matrices are stored with their
 //                         width padded to a multiple of 32); 128x128x32 workgroup tiles, 4 waves x (2x2)
 //                         v_mfma_f32_32x32x2_f32 -- exact fp32 products at the fp32 peak rate -- software-pipelined
@@ -16,10 +16,10 @@
 //                         4 B per 1536 flops, far below the machine balance.
 //   k5_gemm16_panel<T>  : the same panel and block maxima from float16 / bfloat16 operands (pfz_dense_upload16, opt-in):
 //                         256x256x64 tiles, 8 waves x (4x2) v_mfma_f32_32x32x16_f16 / _bf16, fp32 accumulation; with
-//                         k5_inv_norms16 (norms of the 16-bit values) and k5_round16 (float32 input, nearest even).
+//                         k5_round16 (float32 input, nearest even).
 //   k5_gemm8_panel      : the same tile program on int8 operands (pfz_dense_upload8, opt-in): v_mfma_i32_32x32x32_i8, a
-//                         k-chunk of 128 values, int32 accumulation (exact, order-independent); with k5_inv_norms8 (exact
-//                         integer norms) and k5_quantize8 (float32 input, symmetric per row).
+//                         k-chunk of 128 values, int32 accumulation (exact, order-independent); with k5_quantize8
+//                         (float32 input, symmetric per row).
 //   k5_row_topn         : wave per row; with M it selects the ntop-th largest block maximum and reads only the
 //                         blocks that reach it, without M it streams the row (float4); threshold filter, 64-bit
 //                         keys score_bits<<32 | ~col, compaction by wave-max rounds (same scheme as K3), writes
@@ -39,26 +39,6 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kTile = 128;   // workgroup tile (rows of A x rows of B)
-constexpr int kBK = 32;      // k-depth staged per step
-
-// normalize == 0: raw dot products are wanted, every scale factor is 1
-__global__ __launch_bounds__(256) void k5_inv_norms(const float *__restrict__ x, int64_t n, int64_t d,
-                                                     float *__restrict__ inv, int32_t normalize)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= n) return;
-    if (!normalize) {
-        if (lane == 0) inv[row] = 1.f;
-        return;
-    }
-    const float *p = x + row * d;
-    double ss = 0.0;
-    for (int64_t k = lane; k < d; k += 64) ss += (double)p[k] * (double)p[k];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) ss += __shfl_xor(ss, o, 64);
-    if (lane == 0) inv[row] = ss > 0.0 ? (float)(1.0 / sqrt(ss)) : 0.f;   // zero rows stay zero (sklearn normalize)
-}
 
 // Row maxima of a wave's 64 x 64 corner.  x[q] (q = 16 i + r) is the lane's maximum over its two columns of
 // accumulator row-slot q; the maximum over the 32 lanes of a half-wave is wanted for all 32 slots.  Halving
@@ -182,7 +162,7 @@ __device__ __forceinline__ void tile_epilogue(f32x16 (&acc)[2][2], const float *
 //    per group of eight MFMAs (eight loads issued back to back kept the wave out of the matrix pipe for ~300 cycles
 //    per chunk: 8 % of the GEMM, with L2-hot loads just the same); addresses are a wave-uniform base + a 32-bit lane
 //    offset, so a load costs no vector ALU work.
-__global__ __launch_bounds__(256, 2) void k5_gemm_panel_pipe(const float *__restrict__ A, const float *__restrict__ B,
+__global__ __launch_bounds__(256, 2) void k5_gemm_panel_pipe(const void *__restrict__ A, const void *__restrict__ B,
                                                               const float *__restrict__ inv_a, const float *__restrict__ inv_b,
                                                               int64_t a0, int64_t a1, int64_t n_b, int64_t d,
                                                               float *__restrict__ S, int64_t ld, int tiles_m, int tiles_n,
@@ -214,8 +194,8 @@ __global__ __launch_bounds__(256, 2) void k5_gemm_panel_pipe(const float *__rest
 
     const int lr = tid >> 3, lk = (tid & 7) * 4;          // staging: 8 threads per tile row, 32 rows per pass
     // buffer loads: descriptor = the tile's first operand row (wave-uniform), 32-bit lane offset, scalar k offset
-    const __amdgpu_buffer_rsrc_t resA = __builtin_amdgcn_make_buffer_rsrc((void *)(A + row0 * d), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t resB = __builtin_amdgcn_make_buffer_rsrc((void *)(B + col0 * d), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t resA = __builtin_amdgcn_make_buffer_rsrc((void *)((const float *)A + row0 * d), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t resB = __builtin_amdgcn_make_buffer_rsrc((void *)((const float *)B + col0 * d), 0, 0x7fffffff, 0x00020000);
     uint32_t offA[NP], offB[NP];
 #pragma unroll
     for (int p = 0; p < NP; ++p) {        // rows beyond the edge are clamped to the last row (their products are not stored)
@@ -301,9 +281,15 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x16 __attribute__((ext_vector_type(16)));
 
-// An operand trait of the tile program (lp_gemm_tile): kBytes per value, the accumulator type and the MFMA that takes one
-// 16-byte fragment of each operand.
+// An operand trait: the stored value (store_t, kBytes) and how it widens; for the tile program (lp_gemm_tile) also the
+// accumulator type and the MFMA that takes one 16-byte fragment of each operand.  f32 has the fp32 tile program of its own.
+struct f32 {
+    typedef float store_t;
+    static constexpr int kBytes = 4;
+    __device__ static inline float widen(float v) { return v; }
+};
 struct f16 {
+    typedef uint16_t store_t;
     typedef f32x16 acc_t;
     static constexpr int kBytes = 2;
     __device__ static inline float widen(uint16_t b) { return (float)__builtin_bit_cast(_Float16, b); }
@@ -314,6 +300,7 @@ struct f16 {
     }
 };
 struct bf16 {
+    typedef uint16_t store_t;
     typedef f32x16 acc_t;
     static constexpr int kBytes = 2;
     __device__ static inline float widen(uint16_t b) { return __uint_as_float((uint32_t)b << 16); }
@@ -332,8 +319,10 @@ struct bf16 {
 // does not matter here: A and B are read with the same assignment, so every step sums the same 32 products, and integer
 // addition has no order (tests/test_dense8_gpu.py holds the dot products bit for bit).
 struct i8 {
+    typedef int8_t store_t;
     typedef i32x16 acc_t;
     static constexpr int kBytes = 1;
+    __device__ static inline float widen(int8_t q) { return (float)q; }
     __device__ static inline i32x16 mfma(const u32x4 &a, const u32x4 &b, const i32x16 &c)
     {
         return __builtin_amdgcn_mfma_i32_32x32x32_i8(__builtin_bit_cast(i32x4, a), __builtin_bit_cast(i32x4, b), c, 0, 0, 0);
@@ -341,23 +330,24 @@ struct i8 {
 };
 
 constexpr int kTile16 = 256; // workgroup tile of the 16-bit (and 8-bit) tile program
-constexpr int kChunkBytes = 128;   // bytes of a row it stages per step (as kBK floats are), which makes the k-depth
-constexpr int kBK16 = 64;    // 64 16-bit values
-constexpr int kBK8 = 128;    // or 128 int8 values
+constexpr int kChunkBytes = 128;   // bytes of a row a tile program stages per step: 32 floats, 64 16-bit or 128 int8 values
 
-// the norm of the 16-bit values as stored: the cosine is that of the vectors the GEMM multiplies
+// The norm of the values as stored: the cosine is that of the vectors the GEMM multiplies.  The sum is float64 (for int8
+// exact: integer squares, at most 2^14 ld), zero rows stay zero (sklearn normalize).  normalize == 0: raw dot products are
+// wanted and every factor is 1 -- unless keep_scale: an int8 row quantised from float32 keeps the scale k5_quantize8 left
+// in inv[].
 template <typename T>
-__global__ __launch_bounds__(256) void k5_inv_norms16(const uint16_t *__restrict__ x, int64_t n, int64_t d,
-                                                       float *__restrict__ inv, int32_t normalize)
+__global__ __launch_bounds__(256) void k5_inv_norms(const void *__restrict__ x, int64_t n, int64_t d, float *__restrict__ inv,
+                                                     int32_t normalize, int32_t keep_scale)
 {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= n) return;
     if (!normalize) {
-        if (lane == 0) inv[row] = 1.f;
+        if (lane == 0 && !keep_scale) inv[row] = 1.f;
         return;
     }
-    const uint16_t *p = x + row * d;
+    const typename T::store_t *p = (const typename T::store_t *)x + row * d;
     double ss = 0.0;
     for (int64_t k = lane; k < d; k += 64) {
         const double v = (double)T::widen(p[k]);
@@ -512,7 +502,7 @@ __device__ __forceinline__ void lp_gemm_tile(const void *__restrict__ A, const v
 }
 
 template <typename T>
-__global__ __launch_bounds__(512, 1) void k5_gemm16_panel(const uint16_t *__restrict__ A, const uint16_t *__restrict__ B,
+__global__ __launch_bounds__(512, 1) void k5_gemm16_panel(const void *__restrict__ A, const void *__restrict__ B,
                                                            const float *__restrict__ inv_a, const float *__restrict__ inv_b,
                                                            int64_t a0, int64_t a1, int64_t n_b, int64_t d,
                                                            float *__restrict__ S, int64_t ld, int tiles_m, int tiles_n,
@@ -523,44 +513,16 @@ __global__ __launch_bounds__(512, 1) void k5_gemm16_panel(const uint16_t *__rest
 
 // ---- 8-bit integer operands (scalar-quantised embeddings) -----------------------------------------------------------
 // The same tile program on int8 values: a k-chunk is 128 values, the sums are int32 and exact (|dot| <= 2^14 dim fits for
-// dim <= 131071, which pfz_dense_upload8 holds), and the epilogue scales float(sum) by the two per-row factors: 1 / ||q||
+// dim <= 131071, which dense_create holds), and the epilogue scales float(sum) by the two per-row factors: 1 / ||q||
 // for the cosine; for raw dot products the row's quantisation scale, or 1 for int8 given as it is.
 template <typename T>
-__global__ __launch_bounds__(512, 1) void k5_gemm8_panel(const int8_t *__restrict__ A, const int8_t *__restrict__ B,
+__global__ __launch_bounds__(512, 1) void k5_gemm8_panel(const void *__restrict__ A, const void *__restrict__ B,
                                                           const float *__restrict__ inv_a, const float *__restrict__ inv_b,
                                                           int64_t a0, int64_t a1, int64_t n_b, int64_t d,
                                                           float *__restrict__ S, int64_t ld, int tiles_m, int tiles_n,
                                                           float *__restrict__ M, int64_t ldm)
 {
     lp_gemm_tile<T>(A, B, inv_a, inv_b, a0, a1, n_b, d, S, ld, tiles_m, tiles_n, M, ldm);
-}
-
-// Exact integer norms of the int8 values as stored (the squares of a row sum to at most 2^14 ld: no rounding before the
-// square root).  normalize == 0: raw dot products are wanted -- a quantised row keeps the scale k5_quantize8 left in inv[],
-// int8 given as it is gets 1.
-__global__ __launch_bounds__(256) void k5_inv_norms8(const int8_t *__restrict__ x, int64_t n, int64_t d,
-                                                     float *__restrict__ inv, int32_t normalize, int32_t quantized)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= n) return;
-    if (!normalize) {
-        if (lane == 0 && !quantized) inv[row] = 1.f;
-        return;
-    }
-    const uint32_t *p = (const uint32_t *)(x + row * d);      // d is a multiple of 128: four values per load
-    uint64_t ss = 0;
-    for (int64_t k = lane; k < d / 4; k += 64) {
-        const uint32_t v = p[k];
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const int q = (int8_t)(v >> (8 * b));
-            ss += (uint32_t)(q * q);
-        }
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) ss += __shfl_xor(ss, o, 64);
-    if (lane == 0) inv[row] = ss > 0 ? (float)(1.0 / sqrt((double)ss)) : 0.f;
 }
 
 // fp32 [n][dim] -> int8 [n][ld], symmetric per row: m = max |x|, q = rint((x / m) * 127) -- an fp32 division and an fp32
@@ -861,10 +823,9 @@ struct pfz_dense {
     int64_t n = 0, dim = 0;
     int64_t ld = 0;          // dim rounded up to a whole k-chunk of the type (128 B: 32 / 64 / 128 values), the extra columns zero
     int32_t normalize = 1;
-    float *x = nullptr;      // device [n][ld] row-major (dtype == PFZ_DENSE_F32)
     int32_t dtype = PFZ_DENSE_F32;
-    uint16_t *x16 = nullptr; // device [n][ld] row-major float16 / bfloat16 bits (dtype == PFZ_DENSE_F16 / _BF16)
-    int8_t *x8 = nullptr;    // device [n][ld] row-major int8 values, given or quantised per row (dtype == PFZ_DENSE_I8)
+    // device [n][ld] row-major values of `dtype`: float, float16 / bfloat16 bits, or int8 (given or quantised per row)
+    void *x = nullptr;
     // device [n], the factor of a row in the epilogue: 1 / ||row|| of the stored values; with normalize == 0 it is 1, or for
     // int8 rows quantised from float32 the row's scale max |x| / 127
     float *inv = nullptr;
@@ -873,6 +834,11 @@ struct pfz_dense {
 static const char *dense_dtype_name(int32_t dtype)
 {
     return dtype == PFZ_DENSE_F16 ? "float16" : dtype == PFZ_DENSE_BF16 ? "bfloat16" : dtype == PFZ_DENSE_I8 ? "int8" : "float32";
+}
+
+static int64_t dense_dtype_bytes(int32_t dtype)
+{
+    return dtype == PFZ_DENSE_F32 ? f32::kBytes : dtype == PFZ_DENSE_I8 ? i8::kBytes : f16::kBytes;
 }
 
 // host [n][dim] values of `elem` bytes -> device [n][ld], the columns beyond dim zero (padded in pieces of 32 MiB)
@@ -891,25 +857,83 @@ static int upload_rows_padded(pfz_ctx *ctx, void *dst, const void *src, int64_t 
     return PFZ_OK;
 }
 
-template <typename T>
-static int dense_fill16(pfz_ctx *ctx, pfz_dense *m, const void *vec, int32_t source)
+// The one constructor of a K5 operand: `vec` holds values of `dtype` (PFZ_DENSE_SRC_SAME) or float32 values that are rounded
+// / quantised to it on the device (PFZ_DENSE_SRC_F32).  `who`: the entry point, for the messages.
+static int dense_create(pfz_ctx *ctx, const char *who, const void *vec, int64_t n, int64_t dim, int32_t normalize, int32_t dtype,
+                        int32_t source, pfz_dense **out)
 {
-    const int64_t n = m->n, dim = m->dim, ld = m->ld;
-    if (source == PFZ_DENSE_SRC_F32) {
-        // float32 values: uploaded as they are, rounded (and padded) on the device
-        DevBuf tmp;      // (freed at the end of this block: stream order keeps it alive until k5_round16 is done)
-        PFZ_TRY(tmp.alloc(ctx, (size_t)n * (size_t)dim * sizeof(float)));
-        PFZ_TRY(copy_h2d(ctx, tmp.p, vec, (size_t)n * (size_t)dim * sizeof(float)));
-        const int64_t blocks = std::min<int64_t>((n * ld + 255) / 256, 65536);
-        hipLaunchKernelGGL(k5_round16<T>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, (const float *)tmp.p, n, dim, ld, m->x16);
+    PFZ_REQUIRE(ctx && out && (n == 0 || vec), "%s: NULL argument", who);
+    PFZ_REQUIRE(n >= 0 && dim >= 1, "%s: bad shape %lld x %lld", who, (long long)n, (long long)dim);
+    PFZ_REQUIRE(source == PFZ_DENSE_SRC_SAME || source == PFZ_DENSE_SRC_F32, "%s: unknown source %d", who, source);
+    if (n >= ((int64_t)1 << 31) - 256) {
+        set_error("%s: %lld rows exceed the int32 result indices", who, (long long)n);
+        return PFZ_ERR_UNSUPPORTED;
+    }
+    constexpr int64_t kMaxDim8 = 131071;     // 128 * 128 * dim <= 2^31 - 1: a dot product of int8 rows fits its int32 sum
+    if (dtype == PFZ_DENSE_I8 && dim > kMaxDim8) {
+        set_error("%s: %lld columns exceed the %lld an int32 dot product of int8 rows can hold", who, (long long)dim,
+                  (long long)kMaxDim8);
+        return PFZ_ERR_UNSUPPORTED;
+    }
+    PFZ_HIP(hipSetDevice(ctx->device));
+    Owner<pfz_dense, pfz_dense_free> m(new pfz_dense());
+    m->ctx = ctx;
+    m->n = n;
+    m->dim = dim;
+    m->dtype = dtype;
+    // Widths that are not a multiple of the GEMM's k-chunk (300-d word vectors) are padded with zero columns on the device:
+    // dot products and norms do not change and every width takes the pipelined tile program.
+    const int64_t bytes = dense_dtype_bytes(dtype), chunk = kChunkBytes / bytes;
+    const int64_t ld = m->ld = (dim + chunk - 1) / chunk * chunk;
+    m->normalize = normalize ? 1 : 0;
+    PFZ_TRY(pool_alloc(ctx, &m->x, (size_t)(n > 0 ? n : 1) * (size_t)ld * (size_t)bytes));
+    PFZ_TRY(pool_alloc(ctx, &m->inv, (size_t)(n > 0 ? n : 1) * sizeof(float)));
+    if (n > 0) {
+        const dim3 rows4((unsigned)((n + 3) / 4));
+        const bool convert = source == PFZ_DENSE_SRC_F32 && dtype != PFZ_DENSE_F32;
+        if (convert) {
+            // float32 values: uploaded as they are, rounded or quantised (and padded) on the device; the row scales of
+            // k5_quantize8 land in inv[]
+            DevBuf tmp;      // (freed at the end of this block: stream order keeps it alive until the kernel is done)
+            PFZ_TRY(tmp.alloc(ctx, (size_t)n * (size_t)dim * sizeof(float)));
+            PFZ_TRY(copy_h2d(ctx, tmp.p, vec, (size_t)n * (size_t)dim * sizeof(float)));
+            if (dtype == PFZ_DENSE_I8)
+                hipLaunchKernelGGL(k5_quantize8, rows4, dim3(256), 0, ctx->stream, (const float *)tmp.p, n, dim, ld, (int8_t *)m->x, m->inv);
+            else {
+                const int64_t blocks = std::min<int64_t>((n * ld + 255) / 256, 65536);
+                hipLaunchKernelGGL(dtype == PFZ_DENSE_F16 ? k5_round16<f16> : k5_round16<bf16>, dim3((unsigned)blocks), dim3(256), 0,
+                                   ctx->stream, (const float *)tmp.p, n, dim, ld, (uint16_t *)m->x);
+            }
+            PFZ_HIP(hipGetLastError());
+        }
+        else
+            PFZ_TRY(upload_rows_padded(ctx, m->x, vec, n, dim, ld, bytes));
+        auto *norms = dtype == PFZ_DENSE_F16 ? k5_inv_norms<f16> : dtype == PFZ_DENSE_BF16 ? k5_inv_norms<bf16>
+                      : dtype == PFZ_DENSE_I8 ? k5_inv_norms<i8> : k5_inv_norms<f32>;
+        hipLaunchKernelGGL(norms, rows4, dim3(256), 0, ctx->stream, (const void *)m->x, n, ld, m->inv, m->normalize,
+                           (int32_t)(convert && dtype == PFZ_DENSE_I8));
         PFZ_HIP(hipGetLastError());
     }
-    else
-        PFZ_TRY(upload_rows_padded(ctx, m->x16, vec, n, dim, ld, sizeof(uint16_t)));
-    hipLaunchKernelGGL(k5_inv_norms16<T>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, ctx->stream, (const uint16_t *)m->x16, n, ld,
-                       m->inv, m->normalize);
-    PFZ_HIP(hipGetLastError());
+    *out = m.release();
     return PFZ_OK;
+}
+
+// The tile program of an operand type: its kernel, the edge of its square workgroup tile, its workgroup size and how many
+// tile columns the 8-row block has that one XCD works on at a time.
+typedef void (*gemm_fn)(const void *, const void *, const float *, const float *, int64_t, int64_t, int64_t, int64_t, float *, int64_t,
+                        int, int, float *, int64_t);
+struct GemmPlan {
+    gemm_fn kernel;
+    int tile, threads, block_n;
+};
+static GemmPlan gemm_plan(int32_t dtype)
+{
+    switch (dtype) {
+    case PFZ_DENSE_F16: return {k5_gemm16_panel<f16>, kTile16, 512, 4};
+    case PFZ_DENSE_BF16: return {k5_gemm16_panel<bf16>, kTile16, 512, 4};
+    case PFZ_DENSE_I8: return {k5_gemm8_panel<i8>, kTile16, 512, 4};
+    default: return {k5_gemm_panel_pipe, kTile, 256, 8};
+    }
 }
 
 extern "C" {
@@ -919,112 +943,26 @@ void pfz_dense_free(pfz_dense *m)
     if (!m) return;
     if (m->ctx) (void)hipSetDevice(m->ctx->device);
     if (m->x) pool_free(m->x);
-    if (m->x16) pool_free(m->x16);
-    if (m->x8) pool_free(m->x8);
     if (m->inv) pool_free(m->inv);
     delete m;
 }
 
 int pfz_dense_upload(pfz_ctx *ctx, const float *vec, int64_t n, int64_t dim, int32_t normalize, pfz_dense **out)
 {
-    PFZ_REQUIRE(ctx && out && (n == 0 || vec), "pfz_dense_upload: NULL argument");
-    PFZ_REQUIRE(n >= 0 && dim >= 1, "pfz_dense_upload: bad shape %lld x %lld", (long long)n, (long long)dim);
-    if (n >= ((int64_t)1 << 31) - 256) {
-        set_error("pfz_dense_upload: %lld rows exceed the int32 result indices", (long long)n);
-        return PFZ_ERR_UNSUPPORTED;
-    }
-    PFZ_HIP(hipSetDevice(ctx->device));
-    Owner<pfz_dense, pfz_dense_free> m(new pfz_dense());
-    m->ctx = ctx;
-    m->n = n;
-    m->dim = dim;
-    // Widths that are not a multiple of the GEMM's 32-column k-chunk (300-d word vectors) are padded with zero columns
-    // on the device: dot products and norms do not change and every width takes the pipelined tile program.
-    const int64_t ld = (dim + kBK - 1) / kBK * kBK;
-    m->ld = ld;
-    m->normalize = normalize ? 1 : 0;
-    PFZ_TRY(pool_alloc(ctx, &m->x, (size_t)(n > 0 ? n : 1) * (size_t)ld * sizeof(float)));
-    PFZ_TRY(pool_alloc(ctx, &m->inv, (size_t)(n > 0 ? n : 1) * sizeof(float)));
-    if (n > 0) {
-        PFZ_TRY(upload_rows_padded(ctx, m->x, vec, n, dim, ld, sizeof(float)));
-        hipLaunchKernelGGL(k5_inv_norms, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, ctx->stream, m->x, n, ld, m->inv, m->normalize);
-        PFZ_HIP(hipGetLastError());
-    }
-    *out = m.release();
-    return PFZ_OK;
+    return dense_create(ctx, "pfz_dense_upload", vec, n, dim, normalize, PFZ_DENSE_F32, PFZ_DENSE_SRC_SAME, out);
 }
 
 int pfz_dense_upload16(pfz_ctx *ctx, const void *vec, int64_t n, int64_t dim, int32_t normalize, int32_t dtype, int32_t source,
                        pfz_dense **out)
 {
-    PFZ_REQUIRE(ctx && out && (n == 0 || vec), "pfz_dense_upload16: NULL argument");
-    PFZ_REQUIRE(n >= 0 && dim >= 1, "pfz_dense_upload16: bad shape %lld x %lld", (long long)n, (long long)dim);
     PFZ_REQUIRE(dtype == PFZ_DENSE_F16 || dtype == PFZ_DENSE_BF16, "pfz_dense_upload16: dtype %d is neither PFZ_DENSE_F16 nor PFZ_DENSE_BF16",
                 dtype);
-    PFZ_REQUIRE(source == PFZ_DENSE_SRC_SAME || source == PFZ_DENSE_SRC_F32, "pfz_dense_upload16: unknown source %d", source);
-    if (n >= ((int64_t)1 << 31) - 256) {
-        set_error("pfz_dense_upload16: %lld rows exceed the int32 result indices", (long long)n);
-        return PFZ_ERR_UNSUPPORTED;
-    }
-    PFZ_HIP(hipSetDevice(ctx->device));
-    Owner<pfz_dense, pfz_dense_free> m(new pfz_dense());
-    m->ctx = ctx;
-    m->n = n;
-    m->dim = dim;
-    m->dtype = dtype;
-    m->ld = (dim + kBK16 - 1) / kBK16 * kBK16;      // zero columns up to a whole k-chunk, as in pfz_dense_upload
-    m->normalize = normalize ? 1 : 0;
-    PFZ_TRY(pool_alloc(ctx, &m->x16, (size_t)(n > 0 ? n : 1) * (size_t)m->ld * sizeof(uint16_t)));
-    PFZ_TRY(pool_alloc(ctx, &m->inv, (size_t)(n > 0 ? n : 1) * sizeof(float)));
-    if (n > 0)
-        PFZ_TRY(dtype == PFZ_DENSE_F16 ? dense_fill16<f16>(ctx, m.p, vec, source) : dense_fill16<bf16>(ctx, m.p, vec, source));
-    *out = m.release();
-    return PFZ_OK;
+    return dense_create(ctx, "pfz_dense_upload16", vec, n, dim, normalize, dtype, source, out);
 }
 
 int pfz_dense_upload8(pfz_ctx *ctx, const void *vec, int64_t n, int64_t dim, int32_t normalize, int32_t source, pfz_dense **out)
 {
-    PFZ_REQUIRE(ctx && out && (n == 0 || vec), "pfz_dense_upload8: NULL argument");
-    PFZ_REQUIRE(n >= 0 && dim >= 1, "pfz_dense_upload8: bad shape %lld x %lld", (long long)n, (long long)dim);
-    PFZ_REQUIRE(source == PFZ_DENSE_SRC_SAME || source == PFZ_DENSE_SRC_F32, "pfz_dense_upload8: unknown source %d", source);
-    if (n >= ((int64_t)1 << 31) - 256) {
-        set_error("pfz_dense_upload8: %lld rows exceed the int32 result indices", (long long)n);
-        return PFZ_ERR_UNSUPPORTED;
-    }
-    constexpr int64_t kMaxDim8 = 131071;     // 128 * 128 * dim <= 2^31 - 1: a dot product of int8 rows fits its int32 sum
-    if (dim > kMaxDim8) {
-        set_error("pfz_dense_upload8: %lld columns exceed the %lld an int32 dot product of int8 rows can hold", (long long)dim,
-                  (long long)kMaxDim8);
-        return PFZ_ERR_UNSUPPORTED;
-    }
-    PFZ_HIP(hipSetDevice(ctx->device));
-    Owner<pfz_dense, pfz_dense_free> m(new pfz_dense());
-    m->ctx = ctx;
-    m->n = n;
-    m->dim = dim;
-    m->dtype = PFZ_DENSE_I8;
-    m->ld = (dim + kBK8 - 1) / kBK8 * kBK8;          // zero columns up to a whole k-chunk, as in pfz_dense_upload
-    m->normalize = normalize ? 1 : 0;
-    PFZ_TRY(pool_alloc(ctx, &m->x8, (size_t)(n > 0 ? n : 1) * (size_t)m->ld));
-    PFZ_TRY(pool_alloc(ctx, &m->inv, (size_t)(n > 0 ? n : 1) * sizeof(float)));
-    if (n > 0) {
-        const dim3 rows4((unsigned)((n + 3) / 4));
-        if (source == PFZ_DENSE_SRC_F32) {
-            // float32 values: uploaded as they are, quantised (and padded) on the device; the row scales land in inv[]
-            DevBuf tmp;      // (freed at the end of this block: stream order keeps it alive until k5_quantize8 is done)
-            PFZ_TRY(tmp.alloc(ctx, (size_t)n * (size_t)dim * sizeof(float)));
-            PFZ_TRY(copy_h2d(ctx, tmp.p, vec, (size_t)n * (size_t)dim * sizeof(float)));
-            hipLaunchKernelGGL(k5_quantize8, rows4, dim3(256), 0, ctx->stream, (const float *)tmp.p, n, dim, m->ld, m->x8, m->inv);
-            PFZ_HIP(hipGetLastError());
-        }
-        else
-            PFZ_TRY(upload_rows_padded(ctx, m->x8, vec, n, dim, m->ld, 1));
-        hipLaunchKernelGGL(k5_inv_norms8, rows4, dim3(256), 0, ctx->stream, (const int8_t *)m->x8, n, m->ld, m->inv, m->normalize,
-                           (int32_t)(source == PFZ_DENSE_SRC_F32));
-        PFZ_HIP(hipGetLastError());
-    }
-    *out = m.release();
-    return PFZ_OK;
+    return dense_create(ctx, "pfz_dense_upload8", vec, n, dim, normalize, PFZ_DENSE_I8, source, out);
 }
 
 int pfz_dense_dtype(const pfz_dense *m, int32_t *dtype)
@@ -1059,6 +997,7 @@ int pfz_dense_topn(pfz_ctx *ctx, const pfz_dense *from, const pfz_dense *to, int
     if (n_from == 0) return PFZ_OK;
     PFZ_HIP(hipSetDevice(ctx->device));
     if (lower_bound < 0.f) lower_bound = 0.f;   // non-positive similarities are "no match" (_utils.py:122-123)
+    const GemmPlan gp = gemm_plan(from->dtype);
     DevBuf dS[2], dM[2], dU[2];
     const int64_t ld = ((n_to + 255) / 256) * 256;                      // whole float4 x 64-lane steps
     // Two score panels of <= 4 GiB.  At 500 000 to-vectors that is 2048 rows: each B tile
@@ -1094,28 +1033,16 @@ int pfz_dense_topn(pfz_ctx *ctx, const pfz_dense *from, const pfz_dense *to, int
         if (two && pi >= 2) PFZ_HIP(hipStreamWaitEvent(ctx->stream, consumed[buf], 0));   // the top-n of panel pi - 2 read this buffer
         if (ld > 0) {
             ProfScope ps(ctx, "k5_gemm_panel");
-            const int tiles_m = (int)((a1 - a0 + kTile - 1) / kTile), tiles_n = (int)(ld / kTile);
             if (n_to > 0) {
-                // 1-D grid of 8 x 8 tile blocks dealt round-robin to the XCDs (see the kernel)
-                const dim3 grid_p((unsigned)((((tiles_m + 7) / 8) * ((tiles_n + 7) / 8) + 7) / 8 * 512));
+                // 1-D grid of 8 x block_n tile blocks dealt round-robin to the 8 XCDs (see the kernels; ld is a whole number
+                // of tiles of either edge)
+                const int tiles_m = (int)((a1 - a0 + gp.tile - 1) / gp.tile), tiles_n = (int)(ld / gp.tile);
+                const int blocks = ((tiles_m + 7) / 8) * ((tiles_n + gp.block_n - 1) / gp.block_n);
+                const dim3 grid((unsigned)((blocks + 7) / 8 * 8 * 8 * gp.block_n));
                 M = knob_set(knob::K5_NO_BLOCK_MAX) ? nullptr : (const float *)dM[buf].p;      // A/B knob, tests
-                if (from->dtype == PFZ_DENSE_F32)
-                    hipLaunchKernelGGL(k5_gemm_panel_pipe, grid_p, dim3(256), 0, ctx->stream, from->x, to->x, from->inv, to->inv, a0, a1,
-                                       n_to, dim, S, ld, tiles_m, tiles_n, (float *)M, ld / 64);
-                else {
-                    // 256 x 256 tiles (ld is a whole number of them), blocks of 8 x 4 tiles dealt round-robin to the XCDs
-                    const int t16_m = (int)((a1 - a0 + kTile16 - 1) / kTile16), t16_n = (int)(ld / kTile16);
-                    const dim3 grid16((unsigned)((((t16_m + 7) / 8) * ((t16_n + 3) / 4) + 7) / 8 * 256));
-                    if (from->dtype == PFZ_DENSE_I8)
-                        hipLaunchKernelGGL(k5_gemm8_panel<i8>, grid16, dim3(512), 0, ctx->stream, (const int8_t *)from->x8,
-                                           (const int8_t *)to->x8, from->inv, to->inv, a0, a1, n_to, dim, S, ld, t16_m, t16_n, (float *)M,
-                                           ld / 64);
-                    else {
-                        auto *gemm16 = from->dtype == PFZ_DENSE_F16 ? k5_gemm16_panel<f16> : k5_gemm16_panel<bf16>;
-                        hipLaunchKernelGGL(gemm16, grid16, dim3(512), 0, ctx->stream, (const uint16_t *)from->x16, (const uint16_t *)to->x16,
-                                           from->inv, to->inv, a0, a1, n_to, dim, S, ld, t16_m, t16_n, (float *)M, ld / 64);
-                    }
-                }
+                hipLaunchKernelGGL(gp.kernel, grid, dim3(gp.threads), 0, ctx->stream, (const void *)from->x, (const void *)to->x,
+                                   (const float *)from->inv, (const float *)to->inv, a0, a1, n_to, dim, S, ld, tiles_m, tiles_n,
+                                   (float *)M, ld / 64);
             }
         }
         hipStream_t ts = two ? ctx->stream2 : ctx->stream;

@@ -117,11 +117,6 @@ class Embeddings(BaseMatcher):
     def rescore_multiplier(self, value: Optional[int]):
         self._rescore_multiplier = _lib.check_rescore_multiplier(value)
 
-    def _upload(self, ctx, vec, normalize, dtype):
-        if dtype == "int8":
-            return _lib.DeviceDense.upload_int8(ctx, np.asarray(vec), normalize)
-        return _lib.DeviceDense.upload(ctx, np.asarray(vec), normalize, dtype)
-
     def match(self,
               from_list: List[str],
               to_list: List[str] = None,
@@ -145,12 +140,7 @@ class Embeddings(BaseMatcher):
                 embeddings_to = self._embed(to_list)
         if self.cosine_method not in _METHODS:
             raise ValueError(f"cosine_method must be one of {_METHODS}")
-        dtype = _lib.check_compute_dtype(self.compute_dtype)
-        if _lib.check_precision(self.precision) == "int8":
-            if dtype != "float32":
-                raise ValueError(f'precision="int8" and compute_dtype={self.compute_dtype!r} name two operand types: '
-                                 'leave compute_dtype at None')
-            dtype = "int8"
+        dtype = _lib.operand_type(self.compute_dtype, self.precision)
         multiplier = _lib.check_rescore_multiplier(self.rescore_multiplier)
         if multiplier is not None:
             if dtype == "float32":
@@ -167,20 +157,20 @@ class Embeddings(BaseMatcher):
         # the new from-vectors only; an explicitly passed to-side is uploaded unless it IS the resident one
         stale = explicit_to and embeddings_to is not self.embeddings_to
         if re_train or stale or self._dev_to is None or self._dev_to_normalize != normalize or self._dev_to_dtype != dtype:
-            self._dev_to = self._upload(ctx, embeddings_to, normalize, dtype)
+            self._dev_to = _lib.DeviceDense.upload_as(ctx, embeddings_to, dtype, normalize)
             self._dev_to_normalize = normalize
             self._dev_to_dtype = dtype
             self._dev_to_exact = None
         if multiplier is not None and self._dev_to_exact is None:      # (follows every re-upload of the coarse to-side)
-            self._dev_to_exact = self._upload(ctx, embeddings_to, normalize, "float32")
+            self._dev_to_exact = _lib.DeviceDense.upload_as(ctx, embeddings_to, "float32", normalize)
         self_match = to_list is None
         same = self_match and embeddings_to is embeddings_from
-        from_dev = self._dev_to if same else self._upload(ctx, embeddings_from, normalize, dtype)
+        from_dev = self._dev_to if same else _lib.DeviceDense.upload_as(ctx, embeddings_from, dtype, normalize)
         if from_dev.dim != self._dev_to.dim:
             raise ValueError(f"dense cosine needs two 2-D arrays with equal width, got {from_dev.dim} and {self._dev_to.dim}")
         top_n = clip_top_n(self.top_n, to_list)
         if multiplier is not None:
-            from_exact = self._dev_to_exact if same else self._upload(ctx, embeddings_from, normalize, "float32")
+            from_exact = self._dev_to_exact if same else _lib.DeviceDense.upload_as(ctx, embeddings_from, "float32", normalize)
             idx, val = _lib.dense_topn_rescored(ctx, from_dev, self._dev_to, from_exact, self._dev_to_exact, max(top_n, 1), lower,
                                                 multiplier, exclude_diag=self_match).download()
         else:

@@ -305,7 +305,7 @@ class DenseMatchJob:
         self.top_n, self.min_similarity = int(top_n), float(min_similarity)
         self.self_match, self.shard_offset = bool(self_match), int(shard_offset)
         def resident(vec):
-            return vec if isinstance(vec, _lib.DeviceDense) else _lib.DeviceDense.upload(ctx, vec, normalize, compute_dtype)
+            return vec if isinstance(vec, _lib.DeviceDense) else _lib.DeviceDense.upload_as(ctx, vec, _lib.operand_type(compute_dtype), normalize)
         self.from_dev = resident(from_shard)
         self.to_dev = self.from_dev if to_vectors is None else resident(to_vectors)
         if to_vectors is None and (not self.self_match or self.shard_offset != 0):
@@ -322,7 +322,7 @@ class DenseMatchJob:
             if rescore_from is None or (rescore_to is None and to_vectors is not None):
                 raise ValueError("rescore_multiplier needs the float32 vectors of both sides: rescore_from and rescore_to")
             def exact(vec):
-                return vec if isinstance(vec, _lib.DeviceDense) else _lib.DeviceDense.upload(ctx, vec, normalize)
+                return vec if isinstance(vec, _lib.DeviceDense) else _lib.DeviceDense.upload_as(ctx, vec, "float32", normalize)
             self.from_exact = exact(rescore_from)
             self.to_exact = self.from_exact if rescore_to is None else exact(rescore_to)
             for coarse, fine in ((self.from_dev, self.from_exact), (self.to_dev, self.to_exact)):

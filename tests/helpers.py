@@ -79,6 +79,20 @@ def assert_topn_parity(idx, val, exp_idx, exp_val, oracle, a3, b3, n_col, exclud
                 f"{exp_idx[i, r]} (score {exp_val[i, r]!r})"
 
 
+def assert_dense_topn(idx, val, e_idx, e_val, dense, tol=1e-5):
+    """The dense (K5) tests' acceptance rule, e_idx / e_val / dense being the float64 oracle's top-n and score matrix: scores
+    within `tol` absolute; an index may differ from the oracle's only where the oracle's score of the chosen column is within
+    4e-6 of the expected one (only float64 near-ties may swap); such rows are at most max(1, n / 100)"""
+    np.testing.assert_allclose(val, e_val, rtol=0, atol=tol)
+    bad = np.nonzero((idx != e_idx).any(axis=1))[0]
+    for i in bad:
+        for r in range(idx.shape[1]):
+            if idx[i, r] != e_idx[i, r]:
+                s = dense[i, idx[i, r]] if idx[i, r] >= 0 else 0.0
+                assert abs(s - e_val[i, r]) < 4e-6, (i, r, idx[i], e_idx[i])
+    assert len(bad) <= max(1, len(idx) // 100)
+
+
 # ---- the headline held to the REFERENCE's own run (tests/golden/headline_knn_golden_*.npz, make_golden_headline.py) ---------
 
 HEADLINE_GOLDEN_PARTS = 4          # consecutive row blocks of 25 000 rows: each file stays well below 1 MiB

@@ -7,6 +7,8 @@ import pickle
 import numpy as np
 import pytest
 
+from tests.helpers import assert_dense_topn as _check
+
 pytestmark = pytest.mark.gpu
 
 DTYPES = ("float16", "bfloat16")
@@ -25,19 +27,6 @@ def _rounded(a, dtype):
         return g, g.astype(np.float64)
     g = _bf16_bits(a)
     return g, (g.astype(np.uint32) << 16).view(np.float32).astype(np.float64)
-
-
-def _check(idx, val, e_idx, e_val, dense, tol=1e-5):
-    """tests/test_dense_gpu.py::_check: scores within 1e-5 absolute; an index may differ from the oracle's only where the
-    oracle's score of the chosen column is within 4e-6 of the expected one; such rows are at most max(1, n / 100)"""
-    np.testing.assert_allclose(val, e_val, rtol=0, atol=tol)
-    bad = np.nonzero((idx != e_idx).any(axis=1))[0]
-    for i in bad:
-        for r in range(idx.shape[1]):
-            if idx[i, r] != e_idx[i, r]:
-                s = dense[i, idx[i, r]] if idx[i, r] >= 0 else 0.0
-                assert abs(s - e_val[i, r]) < 4e-6, (i, r, idx[i], e_idx[i])
-    assert len(bad) <= max(1, len(idx) // 100)
 
 
 PARITY = [(1, 1, 1, 1),            # width far below one k-chunk; one tile, mostly clamped rows

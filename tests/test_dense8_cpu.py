@@ -97,3 +97,43 @@ def test_one_gemm8_instance_at_one_workgroup_per_cu():
     assert k["vgpr"] <= 256, k
     assert k["lds"] <= 160 * 1024, k
     assert len([p for p in pretty.values() if "k5_gemm16_panel" in p]) == 2
+
+
+def test_one_operand_vocabulary_behind_both_keywords():
+    """_lib.operand_type over the whole grid of the two public keywords, and DeviceDense.upload_as refusing what each door
+    refuses, in the same words, before any device call (ctx=None: a device call would fail with AttributeError)."""
+    from polyfuzz_amd import _lib
+    assert _lib.OPERAND_TYPES == ("float32", "float16", "bfloat16", "int8")
+    got = {}
+    for cd in (None, "float32", "float16", "bfloat16"):
+        for pr in (None, "int8"):
+            try:
+                got[cd, pr] = _lib.operand_type(cd, pr)
+            except ValueError as e:
+                got[cd, pr] = e
+    assert [got[cd, None] for cd in (None, "float32", "float16", "bfloat16")] == ["float32", "float32", "float16", "bfloat16"]
+    assert got[None, "int8"] == got["float32", "int8"] == "int8"
+    for cd in ("float16", "bfloat16"):
+        assert str(got[cd, "int8"]) == f'precision="int8" and compute_dtype={cd!r} name two operand types: leave compute_dtype at None'
+    assert _lib.operand_type() == "float32"
+    with pytest.raises(ValueError, match="compute_dtype must be None or one of"):
+        _lib.operand_type("int8", None)
+    with pytest.raises(ValueError, match='precision must be None or "int8"'):
+        _lib.operand_type(None, "uint8")
+
+    def refusal(f, *args):
+        with pytest.raises(ValueError) as e:
+            f(None, *args)
+        return str(e.value)
+    D = _lib.DeviceDense
+    for bad in (np.zeros((2, 2), np.uint8), np.zeros((2, 2), np.int16), np.zeros(4, np.float32)):
+        assert refusal(D.upload_as, bad, "int8") == refusal(D.upload_int8, bad)
+        for name in ("float16", "bfloat16"):
+            assert refusal(D.upload_as, bad, name) == refusal(D.upload, bad, True, name)
+    assert "unsigned" in refusal(D.upload_as, np.zeros((2, 2), np.uint8), "int8")
+    assert "raw bfloat16 bits as uint16, got int16" in refusal(D.upload_as, np.zeros((2, 2), np.int16), "bfloat16")
+    assert refusal(D.upload_as, np.zeros(4, np.float32), "float32") == refusal(D.upload, np.zeros(4, np.float32)) \
+        == "dense vectors must be a 2-D array, got shape (4,)"
+    for unknown in ("fp8", "half", None, np.int8, 8):
+        with pytest.raises(ValueError, match="operand must be one of"):
+            D.upload_as(None, np.zeros((2, 2), np.float32), unknown)

@@ -1,6 +1,6 @@
 """GPU parity of K5's int8 path (k5_gemm8_panel: int8 vectors on the integer matrix cores, int32 accumulation) against the
 float64 oracle ON THE INT8 VECTORS widened to float64 -- which is exact: an integer dot product has no rounding and no order.
-Cosines are held by the rule of the fp32 and 16-bit paths (tests/test_dense16_gpu.py::_check), raw dot products bit for bit.
+Cosines are held by the rule of the fp32 and 16-bit paths (tests/helpers.py::assert_dense_topn), raw dot products bit for bit.
 The bit-exact cases are also the check of the MFMA's operand lane map that its guide asks for ("with exact integer data")."""
 import concurrent.futures as cf
 import pickle
@@ -8,20 +8,9 @@ import pickle
 import numpy as np
 import pytest
 
+from tests.helpers import assert_dense_topn as _check
+
 pytestmark = pytest.mark.gpu
-
-
-def _check(idx, val, e_idx, e_val, dense, tol=1e-5):
-    """tests/test_dense16_gpu.py::_check: scores within 1e-5 absolute; an index may differ from the oracle's only where the
-    oracle's score of the chosen column is within 4e-6 of the expected one; such rows are at most max(1, n / 100)"""
-    np.testing.assert_allclose(val, e_val, rtol=0, atol=tol)
-    bad = np.nonzero((idx != e_idx).any(axis=1))[0]
-    for i in bad:
-        for r in range(idx.shape[1]):
-            if idx[i, r] != e_idx[i, r]:
-                s = dense[i, idx[i, r]] if idx[i, r] >= 0 else 0.0
-                assert abs(s - e_val[i, r]) < 4e-6, (i, r, idx[i], e_idx[i])
-    assert len(bad) <= max(1, len(idx) // 100)
 
 
 def _int8(rng, shape):

@@ -6,19 +6,10 @@ import os
 import numpy as np
 import pytest
 
+from tests.helpers import assert_dense_topn as _check
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def _check(idx, val, e_idx, e_val, dense, tol=1e-5):
-    np.testing.assert_allclose(val, e_val, rtol=0, atol=tol)
-    bad = np.nonzero((idx != e_idx).any(axis=1))[0]
-    for i in bad:                       # only float64 near-ties may swap
-        for r in range(idx.shape[1]):
-            if idx[i, r] != e_idx[i, r]:
-                s = dense[i, idx[i, r]] if idx[i, r] >= 0 else 0.0
-                assert abs(s - e_val[i, r]) < 4e-6, (i, r, idx[i], e_idx[i])
-    assert len(bad) <= max(1, len(idx) // 100)
 
 
 @pytest.mark.parametrize("n_a,n_b,d,ntop", [(6, 3, 300, 2), (1, 1, 1, 1), (130, 257, 768, 5), (300, 1000, 33, 10),

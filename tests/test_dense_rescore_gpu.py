@@ -1,7 +1,7 @@
 """GPU tests of the exact rescoring of a 16-bit / int8 top-n (k5_rescore_topn, pfz_dense_rescore_topn and the doors above it).
 The expected result of a candidate-restricted search is built here from the float64 oracle: the row's candidate columns,
 lexsorted by (score descending, column ascending), strict > on the bound.  Scores are held by the rule of the other dense
-tests (tests/test_dense16_gpu.py::_check): 1e-5 absolute; an index may differ only where the oracle's score of the chosen
+tests (tests/helpers.py::assert_dense_topn): 1e-5 absolute; an index may differ only where the oracle's score of the chosen
 column is within 4e-6 of the expected one, in at most max(1, n / 100) rows."""
 import concurrent.futures as cf
 import pickle
@@ -9,19 +9,9 @@ import pickle
 import numpy as np
 import pytest
 
+from tests.helpers import assert_dense_topn as _check
+
 pytestmark = pytest.mark.gpu
-
-
-def _check(idx, val, e_idx, e_val, dense, tol=1e-5):
-    """tests/test_dense16_gpu.py::_check"""
-    np.testing.assert_allclose(val, e_val, rtol=0, atol=tol)
-    bad = np.nonzero((idx != e_idx).any(axis=1))[0]
-    for i in bad:
-        for r in range(idx.shape[1]):
-            if idx[i, r] != e_idx[i, r]:
-                s = dense[i, idx[i, r]] if idx[i, r] >= 0 else 0.0
-                assert abs(s - e_val[i, r]) < 4e-6, (i, r, idx[i], e_idx[i])
-    assert len(bad) <= max(1, len(idx) // 100)
 
 
 def _restricted(dense, cand, ntop, lower_bound):

@@ -8,7 +8,7 @@ and then timed over `repeats` steps with device events (pfz_event_*), one pair p
 build, on the same data, in the same run.  Roofline figures per arm: the fraction of the 16-bit MFMA peak (2.5 PF; the
 fp32 arm also against its own 157 TF, the int8 arm against the integer cores' 5 POPS = twice the 16-bit rate) and the time
 the fp32 score panel alone takes at 6.3 TB/s.  The int8 arm holds the same vectors quantised per row on the device
-(DeviceDense.upload_int8); its yardstick is the bfloat16 arm of the same run.
+(DeviceDense.upload_as); its yardstick is the bfloat16 arm of the same run.
 Prints one JSON object; --out also writes it to a file.  Run it under a time limit (timeout 600 ...)."""
 import argparse
 import json
@@ -47,12 +47,9 @@ def main():
     res = {"shape": [args.rows, args.to, args.dim], "top_n": args.top_n, "repeats": args.repeats, "device": ctx.info()["name"],
            "data": "seeded unit-norm random normal", "flop": flop, "panel_write_ms_at_6.3TB/s": panel_bytes / HBM * 1e3, "arms": {}}
     top1 = {}
-    for arm, dtype in (("fp32", None), ("f16", "float16"), ("bf16", "bfloat16"), ("int8", "int8")):
-        if arm == "int8":
-            job = pipeline.DenseMatchJob(ctx, _lib.DeviceDense.upload_int8(ctx, a), _lib.DeviceDense.upload_int8(ctx, b),
-                                         top_n=args.top_n)
-        else:
-            job = pipeline.DenseMatchJob(ctx, a, b, top_n=args.top_n, compute_dtype=dtype)
+    for arm, operand in (("fp32", "float32"), ("f16", "float16"), ("bf16", "bfloat16"), ("int8", "int8")):
+        job = pipeline.DenseMatchJob(ctx, _lib.DeviceDense.upload_as(ctx, a, operand), _lib.DeviceDense.upload_as(ctx, b, operand),
+                                     top_n=args.top_n)
         for _ in range(2):                        # warm-up: code objects, the pool's panels, clocks
             job.step()
         ctx.sync()

@@ -48,9 +48,10 @@ def main():
     ld = (args.dim + 31) // 32 * 32
     res = {"shape": [args.rows, args.to, args.dim], "top_n": args.top_n, "repeats": args.repeats, "device": ctx.info()["name"],
            "data": "seeded unit-norm random normal", "hbm_bytes_per_s": HBM, "arms": {}}
-    exact = {"a": _lib.DeviceDense.upload(ctx, a), "b": _lib.DeviceDense.upload(ctx, b)}       # shared by every rescored arm
-    coarse = {"int8": (_lib.DeviceDense.upload_int8(ctx, a), _lib.DeviceDense.upload_int8(ctx, b)),
-              "bf16": (_lib.DeviceDense.upload(ctx, a, True, "bfloat16"), _lib.DeviceDense.upload(ctx, b, True, "bfloat16"))}
+    def both(operand):
+        return _lib.DeviceDense.upload_as(ctx, a, operand), _lib.DeviceDense.upload_as(ctx, b, operand)
+    exact = dict(zip("ab", both("float32")))       # shared by every rescored arm
+    coarse = {"int8": both("int8"), "bf16": both("bfloat16")}
     arms = [("fp32", None, None)] + [(k, k, None) for k in coarse] + [(f"{k}_x{m}", k, m) for k in coarse for m in MULTIPLIERS]
     topn = {}
     for arm, kind, mult in arms:
