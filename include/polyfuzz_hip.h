@@ -372,7 +372,24 @@ int pfz_dense_dtype(const pfz_dense *m, int32_t *dtype);
 int pfz_dense_upload8(pfz_ctx *ctx, const void *vec, int64_t n, int64_t dim, int32_t normalize, int32_t source,
                       pfz_dense **out);
 
-/* Exact rescoring of a coarse top-n, the companion of the 16-bit and int8 operands (reference _embeddings.py:127-133 asks for
+/* 1-bit operands for the same operator: binary embeddings (sentence-transformers' precision="ubinary", np.packbits(x > 0)),
+ * 1/32 of the fp32 footprint.  A row is dim_bits bits in np.packbits order -- bit k of the row is bit 7 - k % 8 of byte k / 8 --
+ * in (dim_bits + 7) / 8 bytes, the bits of the last byte beyond dim_bits zero (not checked).  `source` says what `vec` holds:
+ * PFZ_DENSE_SRC_SAME = n such rows, copied as they are; PFZ_DENSE_SRC_F32 = n x dim_bits float32 values, packed on the device,
+ * bit = x > 0 (NaN and +-0 give 0).  There is no matrix instruction for XOR / popcount: the tile program (k5_hamming_panel) runs
+ * on the vector ALU and fills the same score panel and block maxima as the others, so the top-n, its deep passes and the
+ * rescoring are shared.  With h = the number of differing bits of two rows, the score is that of the +-1 vectors the bits stand
+ * for: normalize != 0 their cosine, float(dim_bits - 2 h) / float(dim_bits) as ONE correctly rounded fp32 division; normalize
+ * == 0 their dot product float(dim_bits - 2 h).  Both are exact functions of h for dim_bits < 2^24: PFZ_ERR_UNSUPPORTED
+ * beyond.  Scores take only dim_bits + 1 values, so ties are the normal case: the order (score descending, column ascending)
+ * carries the result.  pfz_dense_dtype reports PFZ_DENSE_B1 and pfz_dense_shape dim_bits; pfz_dense_topn takes two such
+ * operands of equal dim_bits and equal `normalize` (PFZ_ERR_INVALID otherwise, also for a mix with another type), and a result
+ * of it is a candidate table for pfz_dense_rescore_topn like any other. */
+#define PFZ_DENSE_B1 4
+int pfz_dense_upload1(pfz_ctx *ctx, const void *vec, int64_t n, int64_t dim_bits, int32_t normalize, int32_t source,
+                      pfz_dense **out);
+
+/* Exact rescoring of a coarse top-n, the companion of the 16-bit, int8 and 1-bit operands (reference _embeddings.py:127-133 asks for
  * the cosines of the vectors as given; quantised embedding search keeps them by searching top_n x k candidates on the cheap
  * operands and scoring those few against the full-precision vectors).  `candidates` is a result buffer of at least
  * from_exact->n rows whose idx half holds, per from-row, column indices into `to_exact` -- a pfz_dense_topn result of the

@@ -101,6 +101,7 @@ SIGNATURES = {
     "pfz_dense_upload": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, c_i32, P(c_vp)]),
     "pfz_dense_upload16": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, P(c_vp)]),
     "pfz_dense_upload8": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, P(c_vp)]),
+    "pfz_dense_upload1": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, P(c_vp)]),
     "pfz_dense_dtype": (ctypes.c_int, [c_vp, P(c_i32)]),
     "pfz_dense_shape": (ctypes.c_int, [c_vp, P(c_i64), P(c_i64)]),
     "pfz_dense_free": (None, [c_vp]),
@@ -787,13 +788,16 @@ def operand_type(compute_dtype=None, precision=None):
 
 
 def _dense_topn_host(ctx, from_vec, to_vec, ntop, lower_bound, exclude_diag, normalize, operand, multiplier=None):
-    """The one-shots' common body: upload both sides as `operand` (one handle when to_vec is from_vec), run K5 -- with a
-    `multiplier` rescored against float32 uploads of the same arrays -- and download (idx, val)."""
+    """The one-shots' common body: upload both sides as `operand` (one of OPERAND_TYPES, or BINARY through its own door; one
+    handle when to_vec is from_vec), run K5 -- with a `multiplier` rescored against float32 uploads of the same arrays -- and
+    download (idx, val)."""
     same = to_vec is from_vec
-    a = DeviceDense.upload_as(ctx, from_vec, operand, normalize)
-    b = a if same else DeviceDense.upload_as(ctx, to_vec, operand, normalize)
+    upload = DeviceDense.upload_bits if operand == BINARY else (lambda c, v, nrm: DeviceDense.upload_as(c, v, operand, nrm))
+    a = upload(ctx, from_vec, normalize)
+    b = a if same else upload(ctx, to_vec, normalize)
     if a.dim != b.dim:
-        raise ValueError(f"dense cosine needs two 2-D arrays with equal width, got {(a.n, a.dim)} and {(b.n, b.dim)}")
+        raise ValueError(f"dense cosine needs two 2-D arrays with equal width, got {(a.n, a.dim)} and {(b.n, b.dim)}"
+                         + (BITS_WIDTH_HINT if operand == BINARY else ""))
     if multiplier is None:
         return dense_topn(ctx, a, b, ntop, lower_bound, exclude_diag).download()
     a_x = DeviceDense.upload_as(ctx, from_vec, "float32", normalize)
@@ -805,6 +809,41 @@ def dense_int8_topn_host(ctx, from_vec, to_vec, ntop, lower_bound, exclude_diag=
     """dense_cossim_topn_host on int8 operands (DeviceDense.upload_int8): np.int8 arrays as they are, float arrays quantised
     per row.  normalize=False: raw dot products -- of the integers as given, or of the dequantised rows."""
     return _dense_topn_host(ctx, from_vec, to_vec, ntop, lower_bound, exclude_diag, normalize, "int8")
+
+
+def dense_hamming_topn_host(ctx, from_vec, to_vec, ntop, lower_bound, exclude_diag=False, normalize=True):
+    """dense_cossim_topn_host on 1-bit operands (DeviceDense.upload_bits): np.uint8 / np.int8 packed rows, or float arrays
+    packed on the device.  The score of a pair with h differing bits of d is the cosine of the +-1 vectors, float32(d - 2 h) /
+    float32(d); normalize=False: their dot product d - 2 h."""
+    return _dense_topn_host(ctx, from_vec, to_vec, ntop, lower_bound, exclude_diag, normalize, BINARY)
+
+
+# ---- 1-bit operands: a door of their own (`precision`, `compute_dtype` and OPERAND_TYPES do not know them) -----------------
+BINARY = "binary"                              # DeviceDense.dtype of a bit handle
+BINARY_FORMS = ("binary", "ubinary")           # sentence-transformers' two spellings of packed sign bits: one device path
+BITS_WIDTH_HINT = (" (packed rows count 8 bits per byte: float vectors whose width is not a multiple of 8 cannot be paired "
+                   "with rows packed on the host -- pack both sides the same way)")
+
+
+def check_binary(value):
+    """`Embeddings.binary`: None (the dense operands of `compute_dtype` / `precision`) or "binary" / "ubinary", the names
+    sentence-transformers gives packed sign bits (np.packbits(x > 0), as uint8 = "ubinary" or shifted by -128 as int8 =
+    "binary").  Both select the same device path -- what is uploaded decides how it is read (DeviceDense.upload_bits).
+    Anything else raises ValueError."""
+    if value is None or (isinstance(value, str) and value in BINARY_FORMS):
+        return value
+    raise ValueError(f"binary must be None or one of {BINARY_FORMS}, got {value!r}")
+
+
+def ubinary_rows(vec):
+    """Packed rows as the device holds them: np.uint8 ("ubinary") as they are; np.int8 ("binary" = ubinary - 128) is the
+    same bytes with bit 7 flipped."""
+    vec = np.ascontiguousarray(vec)
+    if vec.dtype == np.uint8:
+        return vec
+    if vec.dtype == np.int8:
+        return vec.view(np.uint8) ^ np.uint8(0x80)
+    raise ValueError(f"packed binary rows are a uint8 or an int8 array, got {vec.dtype}")
 
 
 # operand type -> (the numpy dtype that is uploaded as it is -- any other float array goes up as float32 and is converted on
@@ -821,7 +860,8 @@ _OPERANDS = {
 
 
 class DeviceDense(_Handle):
-    """Device-resident row-major matrix (fp32, float16 / bfloat16 or int8 values) + the per-row factors (K5 operand)."""
+    """Device-resident row-major matrix (fp32, float16 / bfloat16 or int8 values, or packed bits) + the per-row factors (K5
+    operand)."""
     _free = "pfz_dense_free"
 
     @classmethod
@@ -854,6 +894,30 @@ class DeviceDense(_Handle):
         rounded on the device.  The similarity is then that of the 16-bit vectors: rounding float32 vectors changes the
         scores by about 1e-3 (float16) or 1e-2 (bfloat16) relative per element, which is why this is opt-in."""
         return cls.upload_as(ctx, vec, check_compute_dtype(compute_dtype), normalize)
+
+    @classmethod
+    def upload_bits(cls, ctx, vec, normalize=True):
+        """1-bit rows (K5's Hamming tile program).  An np.uint8 array [n, B] is "ubinary": d = 8 B bits in np.packbits order,
+        uploaded as it is.  An np.int8 array is "binary" (ubinary - 128) and brought to that form first (ubinary_rows): on
+        the device the two are one.  A float array [n, dim] goes up as float32 and is packed on the device, d = dim, bit =
+        x > 0 (NaN and +-0 give 0): the bytes of np.packbits(x > 0, axis=1).  The score of two rows with h differing bits
+        is float32(d - 2 h) / float32(d), or with normalize=False d - 2 h; d < 2**24.  Other dtypes and arrays that are not
+        2-D raise ValueError.  The handle has dtype "binary" and dim = d."""
+        vec = np.asarray(vec)
+        if vec.ndim != 2:
+            raise ValueError(f"dense vectors must be a 2-D array, got shape {vec.shape}")
+        if vec.dtype in (np.uint8, np.int8):
+            a, bits, source = ubinary_rows(vec), 8 * vec.shape[1], _DENSE_SRC_SAME
+        elif vec.dtype.kind == "f":
+            a, bits, source = np.ascontiguousarray(vec, np.float32), vec.shape[1], _DENSE_SRC_F32
+        else:
+            raise ValueError(f"binary vectors are packed uint8 / int8 rows or a float array, got {vec.dtype}")
+        h = c_vp()
+        check(ctx.lib.pfz_dense_upload1(ctx.h, _ptr(a) if a.size else None, a.shape[0], max(bits, 1), int(bool(normalize)),
+                                        source, ctypes.byref(h)))
+        m = cls(ctx, h)
+        m.n, m.dim, m.normalize, m.dtype = a.shape[0], bits, bool(normalize), BINARY
+        return m
 
     @classmethod
     def upload_int8(cls, ctx, vec, normalize=True):
@@ -916,7 +980,7 @@ def dense_rescore(ctx, from_exact, to_exact, candidates, ntop, lower_bound, out=
 
 def dense_topn_rescored(ctx, from_coarse, to_coarse, from_exact, to_exact, ntop, lower_bound, multiplier, exclude_diag=False,
                         diag_offset=0, out=None, candidates=None):
-    """K5 on the 16-bit / int8 operands for rescore_candidates(ntop, multiplier, ...) candidates per row -- with lower bound
+    """K5 on the 16-bit / int8 / 1-bit operands for rescore_candidates(ntop, multiplier, ...) candidates per row -- with lower bound
     0: the user's bound belongs to the exact score, not to the rounded one --, then dense_rescore of those candidates against
     the float32 operands of the same vectors with the user's bound.  The scores are the fp32 path's; the columns are the
     fp32 top-n wherever that lies within the candidates.  `candidates`: a DeviceTopN of that many columns to reuse."""
@@ -932,12 +996,12 @@ def dense_topn_rescored(ctx, from_coarse, to_coarse, from_exact, to_exact, ntop,
     return dense_rescore(ctx, from_exact, to_exact, candidates, ntop, lower_bound, out=out)
 
 
-RESCORE_COARSE = ("int8", "float16", "bfloat16")
+RESCORE_COARSE = ("int8", "float16", "bfloat16", BINARY)
 
 
 def dense_rescored_topn_host(ctx, from_vec, to_vec, ntop, lower_bound, coarse, multiplier, exclude_diag=False, normalize=True):
-    """One-shot dense_topn_rescored on float arrays: both are uploaded twice, as `coarse` ("int8", "float16" or "bfloat16")
-    operands and as float32 ones; (idx, val) host arrays out."""
+    """One-shot dense_topn_rescored on float arrays: both are uploaded twice, as `coarse` ("int8", "float16", "bfloat16", or
+    "binary": sign bits packed on the device, a Hamming search) operands and as float32 ones; (idx, val) host arrays out."""
     if not isinstance(coarse, str) or coarse not in RESCORE_COARSE:
         raise ValueError(f"coarse must be one of {RESCORE_COARSE}, got {coarse!r}")
     check_rescore_multiplier(multiplier)

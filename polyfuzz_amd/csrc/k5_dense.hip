@@ -20,11 +20,15 @@
 //   k5_gemm8_panel      : the same tile program on int8 operands (pfz_dense_upload8, opt-in): v_mfma_i32_32x32x32_i8, a
 //                         k-chunk of 128 values, int32 accumulation (exact, order-independent); with k5_quantize8
 //                         (float32 input, symmetric per row).
+//   k5_hamming_panel    : the same panel and block maxima from 1-bit operands (pfz_dense_upload1, opt-in: binary embeddings,
+//                         np.packbits(x > 0)): no matrix instruction does XOR / popcount, so 128x128 tiles on the vector ALU,
+//                         16 x 4 running bit counts per lane; score float(d - 2 h) / float(d), exact; with k5_pack_signs
+//                         (float32 input, one ballot per 64 values).
 //   k5_row_topn         : wave per row; with M it selects the ntop-th largest block maximum and reads only the
 //                         blocks that reach it, without M it streams the row (float4); threshold filter, 64-bit
 //                         keys score_bits<<32 | ~col, compaction by wave-max rounds (same scheme as K3), writes
 //                         (idx, score) by (score desc, col asc).
-//   k5_rescore_topn     : the companion of the 16-bit / int8 operands (pfz_dense_rescore_topn, opt-in): workgroup per
+//   k5_rescore_topn     : the companion of the 16-bit / int8 / 1-bit operands (pfz_dense_rescore_topn, opt-in): workgroup per
 //                         from-row, wave per candidate column of a coarse top-m; the exact score of the fp32 vectors
 //                         (float64 sum in a fixed order, rounded once), the same keys, ranked in LDS.
 #include "pfz_internal.h"
@@ -549,6 +553,146 @@ __global__ __launch_bounds__(256) void k5_quantize8(const float *__restrict__ sr
     if (lane == 0) scale[row] = __fdiv_rn(m, 127.0f);
 }
 
+// ---- 1-bit operands (binary embeddings: np.packbits(x > 0)) ---------------------------------------------------------
+// A row is dim bits in np.packbits order (bit k of the row = bit 7 - k % 8 of byte k / 8), stored with a pitch of whole
+// 16-byte pieces, the bits beyond dim zero: padding adds no distance.  h = the number of differing bits of two rows; the
+// score is that of the +-1 vectors the bits stand for: their dot product dim - 2 h, or -- normalised -- their cosine
+// float(dim - 2 h) / float(dim), ONE correctly rounded fp32 division.  dim < 2^24: both are exact functions of h.
+constexpr int kB1PitchBits = 128;          // a row's pitch: whole 16-byte pieces
+constexpr int64_t kB1MaxBits = (int64_t)1 << 24;
+
+// fp32 [n][dim] -> packed rows [n][pitch bytes], bit = x > 0 (NaN and +-0 give 0).  The test is made on the value's bits --
+// positive as an integer and not beyond infinity's -- so that a denormal counts as what it is under any denormal mode.
+// Wave per row, one ballot per 64 values: bit l of the ballot is value k0 + l, so byte b of the eight is the bit-reversed b-th
+// byte of the mask; lanes 0..7 write it.
+__global__ __launch_bounds__(256) void k5_pack_signs(const float *__restrict__ src, int64_t n, int64_t dim, int64_t pitch,
+                                                     unsigned char *__restrict__ dst)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n) return;
+    const float *p = src + row * dim;
+    unsigned char *q = dst + row * pitch;
+    for (int64_t k0 = 0; k0 < pitch * 8; k0 += 64) {      // (pitch * 8 is a multiple of 128: the eight bytes are inside the row)
+        const int64_t k = k0 + lane;
+        const int32_t v = k < dim ? __float_as_int(p[k]) : 0;
+        const uint64_t mask = __ballot(v > 0 && v <= 0x7f800000);
+        if (lane < 8) q[(k0 >> 3) + lane] = (unsigned char)(__brev((uint32_t)(mask >> (8 * lane)) & 0xffu) >> 24);
+    }
+}
+
+// What k5_hamming_panel gets in the tile programs' `d` argument: the bit count, and bit 32 set for the normalised score.
+__host__ __device__ inline int64_t b1_arg(int64_t dim_bits, int32_t normalize) { return dim_bits | ((int64_t)(normalize ? 1 : 0) << 32); }
+
+// The tile program of two 1-bit operands: there is no matrix instruction for XOR / popcount, so this one runs on the vector
+// ALU.  A workgroup of 256 threads owns a 128 x 128 tile.  Both row sets are staged in LDS as 32-bit words, a chunk of 128 B
+// of every row at a time (a whole row at dim <= 1024), rows of 36 words (ds_write_b128 / ds_read_b128, see the fp32 program);
+// edge rows are clamped to the last row (their counts are not stored).  Thread (tx = tid & 31, ty = tid >> 5) keeps the 16 x 4
+// counts of rows ty + 8 i and columns tx + 32 j: per 16 bytes of k it reads four B pieces, and for each of its 16 rows one A
+// piece (two addresses per wave: a broadcast) that meets all four -- 20 LDS reads for 256 XORs and 256 v_bcnt_u32_b32, which
+// add the bit count into the running count.  The words of a row are XORed in whatever order they lie in: both sides lie the
+// same way.  The epilogue turns a count into the score (see above; columns beyond n_b score 0, as in tile_epilogue), stores
+// it -- lanes 0..31 of a store cover one 128-B line of a row -- and leaves the block maxima M[row][col / 64] through the same
+// halving exchange as the matrix programs: slot q = 2 i + (j >> 1) of lane (tx, .) is the maximum of row ty + 8 i over the
+// thread's two columns of that 64-column block.
+__global__ __launch_bounds__(256, 2) void k5_hamming_panel(const void *__restrict__ A, const void *__restrict__ B,
+                                                            const float *__restrict__, const float *__restrict__,
+                                                            int64_t a0, int64_t a1, int64_t n_b, int64_t d,
+                                                            float *__restrict__ S, int64_t ld, int tiles_m, int tiles_n,
+                                                            float *__restrict__ M, int64_t ldm)
+{
+    constexpr int LD = 36, NP = 4;                       // LDS row pitch in words; staging passes of 32 rows
+    __shared__ __attribute__((aligned(16))) uint32_t As[kTile * LD];
+    __shared__ __attribute__((aligned(16))) uint32_t Bs[kTile * LD];
+    const int tid = threadIdx.x, lane = tid & 63;
+    // workgroup -> tile: as k5_gemm_panel_pipe (8 x 8 tile blocks dealt round-robin to the XCDs)
+    const int w = blockIdx.x, xcd = w & 7, idx = w >> 3, pos = idx & 63;
+    const int g = (idx >> 6) * 8 + xcd, bm = (tiles_m + 7) >> 3;
+    const int tm = (g % bm) * 8 + (pos & 7), tn = (g / bm) * 8 + (pos >> 3);
+    if (tm >= tiles_m || tn >= tiles_n) return;
+    const int64_t row0 = a0 + (int64_t)tm * kTile;
+    const int64_t col0 = (int64_t)tn * kTile;
+    const int32_t bits = (int32_t)(d & 0xffffffff);
+    const bool normalize = (d >> 32) & 1;
+    const int64_t pitch = ((int64_t)bits + kB1PitchBits - 1) / kB1PitchBits * (kB1PitchBits / 8);      // bytes per operand row
+    const int tx = tid & 31, ty = tid >> 5;
+
+    int h[16][4];
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) h[i][j] = 0;
+
+    const int lr = tid >> 3, lb = (tid & 7) * 16;         // staging: 8 threads per tile row, 32 rows per pass
+    const unsigned char *pa[NP], *pb[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {        // rows beyond the edge are clamped to the last row (their counts are not stored)
+        pa[p] = (const unsigned char *)A + min(row0 + lr + p * 32, a1 - 1) * pitch + lb;
+        pb[p] = (const unsigned char *)B + min(col0 + lr + p * 32, n_b - 1) * pitch + lb;
+    }
+    const u32x4 zero4 = {0u, 0u, 0u, 0u};
+    for (int64_t kb = 0; kb < pitch; kb += kChunkBytes) {
+        const bool in = kb + lb < pitch;                  // (a 16-byte piece is inside the row or beyond it: pitch is whole pieces)
+        u32x4 ra[NP], rb[NP];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            ra[p] = in ? *(const u32x4 *)(pa[p] + kb) : zero4;
+            rb[p] = in ? *(const u32x4 *)(pb[p] + kb) : zero4;
+        }
+        if (kb) __syncthreads();                          // the chunk before has been counted
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            *(u32x4 *)(As + (lr + p * 32) * LD + lb / 4) = ra[p];
+            *(u32x4 *)(Bs + (lr + p * 32) * LD + lb / 4) = rb[p];
+        }
+        __syncthreads();
+        const int pieces = (int)(min((int64_t)kChunkBytes, pitch - kb) / 16);
+        for (int q = 0; q < pieces; ++q) {
+            u32x4 b[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) b[j] = *(const u32x4 *)(Bs + (tx + 32 * j) * LD + 4 * q);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const u32x4 a = *(const u32x4 *)(As + (ty + 8 * i) * LD + 4 * q);
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    h[i][j] += __builtin_popcount(a.x ^ b[j].x) + __builtin_popcount(a.y ^ b[j].y) +
+                               __builtin_popcount(a.z ^ b[j].z) + __builtin_popcount(a.w ^ b[j].w);
+            }
+        }
+    }
+
+    const float fd = (float)bits;
+    bool col_ok[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) col_ok[j] = col0 + tx + 32 * j < n_b;
+    float x[32];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int64_t row = row0 + ty + 8 * i;
+        const bool ok = row < a1;
+        float v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float dot = (float)(bits - 2 * h[i][j]);
+            v[j] = col_ok[j] ? (normalize ? __fdiv_rn(dot, fd) : dot) : 0.f;
+        }
+        if (ok) {
+            float *rowp = S + (row - a0) * ld + col0 + tx;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) rowp[32 * j] = v[j];
+        }
+        x[2 * i] = ok ? fmaxf(v[0], v[1]) : 0.f;
+        x[2 * i + 1] = ok ? fmaxf(v[2], v[3]) : 0.f;
+    }
+    if (M) {
+        const float m = block_row_max(x, lane);
+        const int q = block_row_slot(lane);
+        const int64_t row = row0 + ty + 8 * (q >> 1);
+        if (row < a1) M[(row - a0) * ldm + (col0 >> 6) + (q & 1)] = m;
+    }
+}
+
 __device__ inline uint64_t wave_max_u64_5(uint64_t v)
 {
 #pragma unroll
@@ -821,19 +965,23 @@ using namespace pfz;
 struct pfz_dense {
     pfz_ctx *ctx = nullptr;
     int64_t n = 0, dim = 0;
-    int64_t ld = 0;          // dim rounded up to a whole k-chunk of the type (128 B: 32 / 64 / 128 values), the extra columns zero
+    // dim rounded up to a whole k-chunk of the type (128 B: 32 / 64 / 128 values), the extra columns zero; 1-bit rows: dim (bits)
+    // rounded up to whole 16-byte pieces, in bits
+    int64_t ld = 0;
     int32_t normalize = 1;
     int32_t dtype = PFZ_DENSE_F32;
-    // device [n][ld] row-major values of `dtype`: float, float16 / bfloat16 bits, or int8 (given or quantised per row)
+    // device [n][ld] row-major values of `dtype`: float, float16 / bfloat16 bits, int8 (given or quantised per row), or bits in
+    // np.packbits order (given or packed from the signs of float32 values)
     void *x = nullptr;
     // device [n], the factor of a row in the epilogue: 1 / ||row|| of the stored values; with normalize == 0 it is 1, or for
-    // int8 rows quantised from float32 the row's scale max |x| / 127
+    // int8 rows quantised from float32 the row's scale max |x| / 127; 1-bit rows: 1 (the Hamming score has no row factor)
     float *inv = nullptr;
 };
 
 static const char *dense_dtype_name(int32_t dtype)
 {
-    return dtype == PFZ_DENSE_F16 ? "float16" : dtype == PFZ_DENSE_BF16 ? "bfloat16" : dtype == PFZ_DENSE_I8 ? "int8" : "float32";
+    return dtype == PFZ_DENSE_F16 ? "float16" : dtype == PFZ_DENSE_BF16 ? "bfloat16" : dtype == PFZ_DENSE_I8 ? "int8"
+           : dtype == PFZ_DENSE_B1 ? "binary" : "float32";
 }
 
 static int64_t dense_dtype_bytes(int32_t dtype)
@@ -875,12 +1023,40 @@ static int dense_create(pfz_ctx *ctx, const char *who, const void *vec, int64_t 
                   (long long)kMaxDim8);
         return PFZ_ERR_UNSUPPORTED;
     }
+    if (dtype == PFZ_DENSE_B1 && dim >= kB1MaxBits) {
+        set_error("%s: %lld bits exceed the %lld up to which dim - 2 h is exact in float32", who, (long long)dim, (long long)kB1MaxBits - 1);
+        return PFZ_ERR_UNSUPPORTED;
+    }
     PFZ_HIP(hipSetDevice(ctx->device));
     Owner<pfz_dense, pfz_dense_free> m(new pfz_dense());
     m->ctx = ctx;
     m->n = n;
     m->dim = dim;
     m->dtype = dtype;
+    if (dtype == PFZ_DENSE_B1) {
+        // 1-bit rows: no k-chunk padding and no norms.  Packed rows of (dim + 7) / 8 bytes go up as they are, float32 rows are
+        // packed on the device; either way the pitch is whole 16-byte pieces and the bits beyond dim are zero.
+        const int64_t ld = m->ld = (dim + kB1PitchBits - 1) / kB1PitchBits * kB1PitchBits, pitch = ld / 8;
+        m->normalize = normalize ? 1 : 0;
+        PFZ_TRY(pool_alloc(ctx, &m->x, (size_t)(n > 0 ? n : 1) * (size_t)pitch));
+        PFZ_TRY(pool_alloc(ctx, &m->inv, (size_t)(n > 0 ? n : 1) * sizeof(float)));
+        if (n > 0) {
+            const dim3 rows4((unsigned)((n + 3) / 4));
+            if (source == PFZ_DENSE_SRC_F32) {
+                DevBuf tmp;      // (freed at the end of this block: stream order keeps it alive until the kernel is done)
+                PFZ_TRY(tmp.alloc(ctx, (size_t)n * (size_t)dim * sizeof(float)));
+                PFZ_TRY(copy_h2d(ctx, tmp.p, vec, (size_t)n * (size_t)dim * sizeof(float)));
+                hipLaunchKernelGGL(k5_pack_signs, rows4, dim3(256), 0, ctx->stream, (const float *)tmp.p, n, dim, pitch, (unsigned char *)m->x);
+                PFZ_HIP(hipGetLastError());
+            }
+            else
+                PFZ_TRY(upload_rows_padded(ctx, m->x, vec, n, (dim + 7) / 8, pitch, 1));
+            hipLaunchKernelGGL(k5_inv_norms<f32>, rows4, dim3(256), 0, ctx->stream, (const void *)m->x, n, (int64_t)0, m->inv, 0, 0);
+            PFZ_HIP(hipGetLastError());
+        }
+        *out = m.release();
+        return PFZ_OK;
+    }
     // Widths that are not a multiple of the GEMM's k-chunk (300-d word vectors) are padded with zero columns on the device:
     // dot products and norms do not change and every width takes the pipelined tile program.
     const int64_t bytes = dense_dtype_bytes(dtype), chunk = kChunkBytes / bytes;
@@ -932,6 +1108,7 @@ static GemmPlan gemm_plan(int32_t dtype)
     case PFZ_DENSE_F16: return {k5_gemm16_panel<f16>, kTile16, 512, 4};
     case PFZ_DENSE_BF16: return {k5_gemm16_panel<bf16>, kTile16, 512, 4};
     case PFZ_DENSE_I8: return {k5_gemm8_panel<i8>, kTile16, 512, 4};
+    case PFZ_DENSE_B1: return {k5_hamming_panel, kTile, 256, 8};
     default: return {k5_gemm_panel_pipe, kTile, 256, 8};
     }
 }
@@ -965,6 +1142,11 @@ int pfz_dense_upload8(pfz_ctx *ctx, const void *vec, int64_t n, int64_t dim, int
     return dense_create(ctx, "pfz_dense_upload8", vec, n, dim, normalize, PFZ_DENSE_I8, source, out);
 }
 
+int pfz_dense_upload1(pfz_ctx *ctx, const void *vec, int64_t n, int64_t dim_bits, int32_t normalize, int32_t source, pfz_dense **out)
+{
+    return dense_create(ctx, "pfz_dense_upload1", vec, n, dim_bits, normalize, PFZ_DENSE_B1, source, out);
+}
+
 int pfz_dense_dtype(const pfz_dense *m, int32_t *dtype)
 {
     PFZ_REQUIRE(m && dtype, "pfz_dense_dtype: NULL argument");
@@ -984,6 +1166,10 @@ int pfz_dense_topn(pfz_ctx *ctx, const pfz_dense *from, const pfz_dense *to, int
                    int32_t exclude_diag, int64_t diag_offset, pfz_topn *out)
 {
     PFZ_REQUIRE(ctx && from && to && out, "pfz_dense_topn: NULL argument");
+    PFZ_REQUIRE(from->dtype != PFZ_DENSE_B1 || to->dtype != PFZ_DENSE_B1 || from->dim == to->dim,
+                "pfz_dense_topn: from-vectors have %lld bits, to-vectors %lld (rows packed on the host count 8 bits per byte: float "
+                "vectors whose width is not a multiple of 8 cannot be paired with them -- pack both sides the same way)",
+                (long long)from->dim, (long long)to->dim);
     PFZ_REQUIRE(from->dim == to->dim, "pfz_dense_topn: from-vectors have %lld columns, to-vectors %lld", (long long)from->dim,
                 (long long)to->dim);
     PFZ_REQUIRE(from->dtype == to->dtype, "pfz_dense_topn: from-vectors are %s, to-vectors %s: upload both with one compute type",
@@ -993,7 +1179,10 @@ int pfz_dense_topn(pfz_ctx *ctx, const pfz_dense *from, const pfz_dense *to, int
     constexpr int32_t kDeepPass = 1024;      // keys one pass keeps (k5_row_topn<1152>)
     PFZ_REQUIRE(out->n_rows >= from->n && out->ntop == ntop, "pfz_dense_topn: result buffer is %lldx%d, need %lldx%d",
                 (long long)out->n_rows, out->ntop, (long long)from->n, ntop);
-    const int64_t n_from = from->n, n_to = to->n, dim = from->ld;        // the padded width: a multiple of the type's k-chunk
+    PFZ_REQUIRE(from->dtype != PFZ_DENSE_B1 || from->normalize == to->normalize,
+                "pfz_dense_topn: one binary operand was uploaded with normalize, the other without: the score is one or the other");
+    // the padded width: a multiple of the type's k-chunk; 1-bit operands: the bit count and which score (b1_arg)
+    const int64_t n_from = from->n, n_to = to->n, dim = from->dtype == PFZ_DENSE_B1 ? b1_arg(from->dim, from->normalize) : from->ld;
     if (n_from == 0) return PFZ_OK;
     PFZ_HIP(hipSetDevice(ctx->device));
     if (lower_bound < 0.f) lower_bound = 0.f;   // non-positive similarities are "no match" (_utils.py:122-123)

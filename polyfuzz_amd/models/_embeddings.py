@@ -67,6 +67,19 @@ class Embeddings(BaseMatcher):
                    `match` raises ValueError when it is set and the operands are float32 (nothing to rescore), or when
                    the embeddings handed in are np.int8 / np.float16 / raw bfloat16 (np.uint16) arrays: there are no
                    full-precision vectors to rescore against.  Kept through pickling; changing it alone re-uploads nothing.
+        binary: None (default: `match` is exactly as above) or "binary" / "ubinary", sentence-transformers' names for packed
+                   sign bits, np.packbits(x > 0): `m = Embeddings(...); m.binary = "ubinary"`.  Both names select the same
+                   device path; what is handed in decides how it is read: an np.uint8 array [n, B] is "ubinary" rows of
+                   d = 8 B bits, an np.int8 array is "binary" (ubinary - 128, brought to the same bytes), and float arrays
+                   -- also what an `embedding_method` returns -- are packed on the device, bit = x > 0, d = their width.  The
+                   device keeps 1/32 of the fp32 footprint.  The Similarity of two rows with h differing bits is the cosine of
+                   the +-1 vectors the bits stand for, float32(d - 2 h) / float32(d) (cosine_method "sparse": their dot
+                   product d - 2 h), exact and full of ties, which the column order resolves.  Both sides need the same d: a
+                   float side whose width is not a multiple of 8 cannot be paired with packed rows.  `rescore_multiplier`
+                   works with it as with the other cheap operands -- the usual way to use such embeddings -- and raises
+                   for packed uint8 / int8 arrays (no full-precision vectors).  `match` raises ValueError when it is set
+                   together with `precision` or a `compute_dtype` other than None / "float32".  Anything else raises
+                   ValueError; kept through pickling; the resident to-side is re-uploaded when it changes.
     """
     def __init__(self,
                  embedding_method: Optional[Callable[[List[str]], np.ndarray]] = None,
@@ -91,6 +104,7 @@ class Embeddings(BaseMatcher):
         self._precision = None
         self._rescore_multiplier = None
         self._dev_to_exact = None      # float32 DeviceDense of the to-side, beside _dev_to, while rescoring is on
+        self._binary = None
 
     @property
     def compute_dtype(self) -> Optional[str]:
@@ -117,6 +131,14 @@ class Embeddings(BaseMatcher):
     def rescore_multiplier(self, value: Optional[int]):
         self._rescore_multiplier = _lib.check_rescore_multiplier(value)
 
+    @property
+    def binary(self) -> Optional[str]:
+        return self._binary
+
+    @binary.setter
+    def binary(self, value: Optional[str]):
+        self._binary = _lib.check_binary(value)
+
     def match(self,
               from_list: List[str],
               to_list: List[str] = None,
@@ -140,14 +162,26 @@ class Embeddings(BaseMatcher):
                 embeddings_to = self._embed(to_list)
         if self.cosine_method not in _METHODS:
             raise ValueError(f"cosine_method must be one of {_METHODS}")
-        dtype = _lib.operand_type(self.compute_dtype, self.precision)
+        bits = _lib.check_binary(self.binary) is not None
+        if bits:
+            if self.precision is not None or _lib.check_compute_dtype(self.compute_dtype) != "float32":
+                raise ValueError(f"binary={self.binary!r} is set together with precision={self.precision!r} / "
+                                 f"compute_dtype={self.compute_dtype!r}: they name two operand types, leave those at None")
+            dtype = _lib.BINARY
+
+            def upload(ctx, vec, operand, normalize):
+                return _lib.DeviceDense.upload_bits(ctx, vec, normalize) if operand == _lib.BINARY \
+                    else _lib.DeviceDense.upload_as(ctx, vec, operand, normalize)
+        else:
+            dtype = _lib.operand_type(self.compute_dtype, self.precision)
+            upload = _lib.DeviceDense.upload_as
         multiplier = _lib.check_rescore_multiplier(self.rescore_multiplier)
         if multiplier is not None:
             if dtype == "float32":
                 raise ValueError("rescore_multiplier is set but the operands are float32: there is nothing to rescore "
                                  '(set precision="int8" or a 16-bit compute_dtype, or leave rescore_multiplier at None)')
             for side, vec in (("embeddings_from", embeddings_from), ("embeddings_to", embeddings_to)):
-                if np.asarray(vec).dtype in (np.int8, np.float16, np.uint16):
+                if np.asarray(vec).dtype in (np.int8, np.float16, np.uint16) + ((np.uint8,) if bits else ()):
                     raise ValueError(f"rescore_multiplier is set but {side} is already a {np.asarray(vec).dtype} array: "
                                      "there are no full-precision vectors to rescore against (pass float32 embeddings)")
         ctx = _lib.Context.default()
@@ -157,20 +191,21 @@ class Embeddings(BaseMatcher):
         # the new from-vectors only; an explicitly passed to-side is uploaded unless it IS the resident one
         stale = explicit_to and embeddings_to is not self.embeddings_to
         if re_train or stale or self._dev_to is None or self._dev_to_normalize != normalize or self._dev_to_dtype != dtype:
-            self._dev_to = _lib.DeviceDense.upload_as(ctx, embeddings_to, dtype, normalize)
+            self._dev_to = upload(ctx, embeddings_to, dtype, normalize)
             self._dev_to_normalize = normalize
             self._dev_to_dtype = dtype
             self._dev_to_exact = None
         if multiplier is not None and self._dev_to_exact is None:      # (follows every re-upload of the coarse to-side)
-            self._dev_to_exact = _lib.DeviceDense.upload_as(ctx, embeddings_to, "float32", normalize)
+            self._dev_to_exact = upload(ctx, embeddings_to, "float32", normalize)
         self_match = to_list is None
         same = self_match and embeddings_to is embeddings_from
-        from_dev = self._dev_to if same else _lib.DeviceDense.upload_as(ctx, embeddings_from, dtype, normalize)
+        from_dev = self._dev_to if same else upload(ctx, embeddings_from, dtype, normalize)
         if from_dev.dim != self._dev_to.dim:
-            raise ValueError(f"dense cosine needs two 2-D arrays with equal width, got {from_dev.dim} and {self._dev_to.dim}")
+            raise ValueError(f"dense cosine needs two 2-D arrays with equal width, got {from_dev.dim} and {self._dev_to.dim}"
+                             + (_lib.BITS_WIDTH_HINT if bits else ""))
         top_n = clip_top_n(self.top_n, to_list)
         if multiplier is not None:
-            from_exact = self._dev_to_exact if same else _lib.DeviceDense.upload_as(ctx, embeddings_from, "float32", normalize)
+            from_exact = self._dev_to_exact if same else upload(ctx, embeddings_from, "float32", normalize)
             idx, val = _lib.dense_topn_rescored(ctx, from_dev, self._dev_to, from_exact, self._dev_to_exact, max(top_n, 1), lower,
                                                 multiplier, exclude_diag=self_match).download()
         else:
@@ -187,6 +222,7 @@ class Embeddings(BaseMatcher):
         self.__dict__.setdefault("_compute_dtype", None)      # (pickled before the keywords existed)
         self.__dict__.setdefault("_precision", None)
         self.__dict__.setdefault("_rescore_multiplier", None)
+        self.__dict__.setdefault("_binary", None)
         self._dev_to = None
         self._dev_to_exact = None
 

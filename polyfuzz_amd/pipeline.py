@@ -291,8 +291,9 @@ class DenseMatchJob:
     (_lib.check_compute_dtype): the similarity is that of the 16-bit vectors, float32 input is rounded (about 1e-3 / 1e-2
     relative per element), so it is opt-in.
     from_shard / to_vectors may also be _lib.DeviceDense handles of this context: they are used as they are (resident
-    16-bit operands, or int8 ones from DeviceDense.upload_int8), and `normalize` / `compute_dtype` do not apply to them.
-    rescore_multiplier (an int >= 1, with 16-bit or int8 operands): a step searches top_n x rescore_multiplier candidates per
+    16-bit operands, int8 ones from DeviceDense.upload_int8, or 1-bit ones from DeviceDense.upload_bits), and `normalize` /
+    `compute_dtype` do not apply to them.
+    rescore_multiplier (an int >= 1, with 16-bit, int8 or 1-bit operands): a step searches top_n x rescore_multiplier candidates per
     row on those operands and scores them against the float32 form of the same vectors, rescore_from / rescore_to -- arrays
     (uploaded here with `normalize`) or float32 DeviceDense handles of this context; rescore_to=None with to_vectors=None
     is the from-side again (_lib.dense_topn_rescored).  The scores and `min_similarity` are then the fp32 path's; the

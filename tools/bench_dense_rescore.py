@@ -1,9 +1,11 @@
-"""K5 with exact rescoring of the int8 / bfloat16 top-n on one panel's worth of BASELINE configuration 5, in one process.
+"""K5 with exact rescoring of the int8 / bfloat16 / 1-bit top-n on one panel's worth of BASELINE configuration 5, in one process.
 
 usage: python tools/bench_dense_rescore.py [--rows 4096] [--to 500000] [--dim 768] [--top-n 5] [--repeats 7] [--out FILE]
 
 Seeded unit-norm random-normal vectors, device-resident operands (pipeline.DenseMatchJob), top-5, as tools/bench_dense16.py.
-Arms, all in this run: fp32; int8 and bfloat16 plain; int8 and bfloat16 with rescore_multiplier 2, 4 and 8 (the coarse search
+Arms, all in this run: fp32; int8 and bfloat16 plain; int8 and bfloat16 with rescore_multiplier 2, 4 and 8; the sign bits of
+the same vectors (DeviceDense.upload_bits, a Hamming search) plain and with rescore_multiplier 4, 16 and 64 -- a 1-bit search
+is used with a large oversampling -- which are reported, not gated (the coarse search
 keeps top_n x multiplier candidates per row, k5_rescore_topn scores them against the fp32 vectors).  Every arm is warmed up
 and then timed over `repeats` steps with device events (pfz_event_*), one pair per step; a further profiled pass
 (pfz_prof_*) gives the GEMM's, the row top-n's and the rescoring kernel's own time.  For the rescoring kernel: the bytes it
@@ -22,6 +24,7 @@ import numpy as np
 
 HBM = 6.3e12
 MULTIPLIERS = (2, 4, 8)
+BINARY_MULTIPLIERS = (4, 16, 64)
 
 
 def main():
@@ -53,6 +56,8 @@ def main():
     exact = dict(zip("ab", both("float32")))       # shared by every rescored arm
     coarse = {"int8": both("int8"), "bf16": both("bfloat16")}
     arms = [("fp32", None, None)] + [(k, k, None) for k in coarse] + [(f"{k}_x{m}", k, m) for k in coarse for m in MULTIPLIERS]
+    coarse["binary"] = (_lib.DeviceDense.upload_bits(ctx, a), _lib.DeviceDense.upload_bits(ctx, b))
+    arms += [("binary", "binary", None)] + [(f"binary_x{m}", "binary", m) for m in BINARY_MULTIPLIERS]
     topn = {}
     for arm, kind, mult in arms:
         if kind is None:
