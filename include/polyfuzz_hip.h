@@ -405,6 +405,26 @@ int pfz_dense_upload1(pfz_ctx *ctx, const void *vec, int64_t n, int64_t dim_bits
 int pfz_dense_rescore_topn(pfz_ctx *ctx, const pfz_dense *from_exact, const pfz_dense *to_exact, const pfz_topn *candidates,
                            int32_t ntop, float lower_bound, pfz_topn *out);
 
+/* Mixed rescoring: the float32 from-vectors against a to-side that is kept ONLY in its quantised form (reference
+ * _embeddings.py:127-133 scores the vectors as given; sentence-transformers' quantised search keeps the corpus as int8 or packed
+ * bits alone and rescores the float32 queries against that corpus itself, "binary search, int8 rescoring").  The contract is
+ * pfz_dense_rescore_topn's -- candidate table, skipped indices, bound, order, (-1, 0) fill, one summation order per pair, so equal
+ * to-rows get equal scores and the order of a row's candidates does not change its result -- except for `to_coarse`, a
+ * PFZ_DENSE_I8 or PFZ_DENSE_B1 operand of the same width (typically the operand the candidates were searched on, or an int8
+ * operand beside a 1-bit one); no float32 to-side exists.  For candidate j of row i, float64 sums rounded to fp32 once:
+ *   int8: f_from[i] * f_to[j] * sum_k x_i[k] q_j[k] with the handle's own factor f_to -- 1 / ||q_j|| (normalize != 0: the cosine
+ *         of the float vector and the int8 vector), the row's quantisation scale (normalize == 0, quantised from float32: the
+ *         dot product with the dequantised row) or 1 (normalize == 0, int8 given as it is).
+ *   bits: with s_j[k] = +1 / -1 for a set / clear bit, f_from[i] * sum_k x_i[k] s_j[k] / sqrt(dim_bits) (normalize != 0: the cosine
+ *         of the float vector and the +-1 vector, the vectors the Hamming score speaks of), or the sum itself (normalize == 0).
+ * The columns are the float32 top-n only as far as the quantised to-side ranks them so.  Enqueues on the context stream.
+ * PFZ_ERR_INVALID: from-vectors that are not PFZ_DENSE_F32, to-vectors that are neither PFZ_DENSE_I8 nor PFZ_DENSE_B1, unequal
+ * widths, a 1-bit to-side whose `normalize` differs from the from-side's, candidates == out, fewer candidate rows than
+ * from-rows, ntop outside 1 .. candidates per row, a NaN bound, a result buffer of another shape; PFZ_ERR_UNSUPPORTED: more than
+ * 1024 candidates per row.  No from-rows: PFZ_OK, nothing is done. */
+int pfz_dense_rescore_topn_mixed(pfz_ctx *ctx, const pfz_dense *from_exact, const pfz_dense *to_coarse, const pfz_topn *candidates,
+                                 int32_t ntop, float lower_bound, pfz_topn *out);
+
 /* ---- K6: reductions on the hot path's output --------------------------------
  * precision_recall_curve (reference polyfuzz/metrics.py:12-53): for every threshold p_k
  * (ascending, n_thresholds <= 4096) count_ge[k] = #{i : sim[i] >= p_k} and sum_ge[k] = the sum of

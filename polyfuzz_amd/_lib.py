@@ -107,6 +107,7 @@ SIGNATURES = {
     "pfz_dense_free": (None, [c_vp]),
     "pfz_dense_topn": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_f32, c_i32, c_i64, c_vp]),
     "pfz_dense_rescore_topn": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_f32, c_vp]),
+    "pfz_dense_rescore_topn_mixed": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_f32, c_vp]),
     "pfz_pr_curve_host": (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp]),
     "pfz_linkage_top1": (ctypes.c_int, [c_vp, c_vp, c_f64, c_vp, c_vp, c_vp]),
     "pfz_comm_unique_id": (ctypes.c_int, [c_vp]),
@@ -787,12 +788,14 @@ def operand_type(compute_dtype=None, precision=None):
     return "int8"
 
 
-def _dense_topn_host(ctx, from_vec, to_vec, ntop, lower_bound, exclude_diag, normalize, operand, multiplier=None):
+def _dense_topn_host(ctx, from_vec, to_vec, ntop, lower_bound, exclude_diag, normalize, operand, multiplier=None, rescore_to=None):
     """The one-shots' common body: upload both sides as `operand` (one of OPERAND_TYPES, or BINARY through its own door; one
-    handle when to_vec is from_vec), run K5 -- with a `multiplier` rescored against float32 uploads of the same arrays -- and
-    download (idx, val)."""
+    handle when to_vec is from_vec), run K5 -- with a `multiplier` rescored against float32 uploads of the same arrays, or with
+    `rescore_to` ("int8" / BINARY) the float32 from-side against the to-side in that form, which is `operand`'s handle when the
+    two are equal: no float32 to-side is made -- and download (idx, val)."""
     same = to_vec is from_vec
-    upload = DeviceDense.upload_bits if operand == BINARY else (lambda c, v, nrm: DeviceDense.upload_as(c, v, operand, nrm))
+    def upload(c, v, nrm, form=operand):
+        return DeviceDense.upload_bits(c, v, nrm) if form == BINARY else DeviceDense.upload_as(c, v, form, nrm)
     a = upload(ctx, from_vec, normalize)
     b = a if same else upload(ctx, to_vec, normalize)
     if a.dim != b.dim:
@@ -801,7 +804,10 @@ def _dense_topn_host(ctx, from_vec, to_vec, ntop, lower_bound, exclude_diag, nor
     if multiplier is None:
         return dense_topn(ctx, a, b, ntop, lower_bound, exclude_diag).download()
     a_x = DeviceDense.upload_as(ctx, from_vec, "float32", normalize)
-    b_x = a_x if same else DeviceDense.upload_as(ctx, to_vec, "float32", normalize)
+    if rescore_to is not None:
+        b_x = b if rescore_to == operand else upload(ctx, to_vec, normalize, rescore_to)
+    else:
+        b_x = a_x if same else DeviceDense.upload_as(ctx, to_vec, "float32", normalize)
     return dense_topn_rescored(ctx, a, b, a_x, b_x, ntop, lower_bound, multiplier, exclude_diag).download()
 
 
@@ -978,12 +984,29 @@ def dense_rescore(ctx, from_exact, to_exact, candidates, ntop, lower_bound, out=
     return out
 
 
+MIXED_RESCORE_TO = ("int8", BINARY)     # the to-operands pfz_dense_rescore_topn_mixed scores float32 from-vectors against
+
+
+def dense_rescore_mixed(ctx, from_exact, to_coarse, candidates, ntop, lower_bound, out=None):
+    """Enqueue pfz_dense_rescore_topn_mixed: dense_rescore with the float32 from-operand against an int8 or 1-bit to-operand
+    itself (k5_mixed_rescore) -- the cosine (normalize=False: the dot product) of the float vector and the int8 vector, or of
+    the float vector and the +-1 vector the bits stand for; float64 sums, rounded once.  No float32 to-side is needed.
+    Returns the (device-resident) DeviceTopN."""
+    if out is None:
+        out = DeviceTopN.alloc(ctx, from_exact.n, ntop)
+    check(ctx.lib.pfz_dense_rescore_topn_mixed(ctx.h, from_exact.h, to_coarse.h, candidates.h, int(ntop), float(lower_bound), out.h))
+    return out
+
+
 def dense_topn_rescored(ctx, from_coarse, to_coarse, from_exact, to_exact, ntop, lower_bound, multiplier, exclude_diag=False,
                         diag_offset=0, out=None, candidates=None):
     """K5 on the 16-bit / int8 / 1-bit operands for rescore_candidates(ntop, multiplier, ...) candidates per row -- with lower bound
     0: the user's bound belongs to the exact score, not to the rounded one --, then dense_rescore of those candidates against
     the float32 operands of the same vectors with the user's bound.  The scores are the fp32 path's; the columns are the
-    fp32 top-n wherever that lies within the candidates.  `candidates`: a DeviceTopN of that many columns to reuse."""
+    fp32 top-n wherever that lies within the candidates.  `candidates`: a DeviceTopN of that many columns to reuse.
+    A `to_exact` of dtype "int8" or "binary" -- to_coarse itself, or an int8 handle beside a 1-bit to_coarse -- is scored by
+    dense_rescore_mixed instead: from_exact stays float32, the scores are those of the float from-vectors and the QUANTISED
+    to-vectors, and the columns are the fp32 top-n only as far as that to-side ranks them so."""
     m = rescore_candidates(ntop, multiplier, to_coarse.n, exclude_diag)          # (raises before anything is enqueued)
     if (from_coarse.n, to_coarse.n, from_coarse.dim) != (from_exact.n, to_exact.n, from_exact.dim):
         raise ValueError(f"the coarse operands {(from_coarse.n, to_coarse.n, from_coarse.dim)} and the exact ones "
@@ -993,27 +1016,66 @@ def dense_topn_rescored(ctx, from_coarse, to_coarse, from_exact, to_exact, ntop,
     elif candidates.ntop != m:
         raise ValueError(f"the candidate buffer has {candidates.ntop} columns, this search needs {m}")
     dense_topn(ctx, from_coarse, to_coarse, m, 0.0, exclude_diag, diag_offset, out=candidates)
-    return dense_rescore(ctx, from_exact, to_exact, candidates, ntop, lower_bound, out=out)
+    rescore = dense_rescore_mixed if getattr(to_exact, "dtype", None) in MIXED_RESCORE_TO else dense_rescore
+    return rescore(ctx, from_exact, to_exact, candidates, ntop, lower_bound, out=out)
 
 
 RESCORE_COARSE = ("int8", "float16", "bfloat16", BINARY)
 
 
-def dense_rescored_topn_host(ctx, from_vec, to_vec, ntop, lower_bound, coarse, multiplier, exclude_diag=False, normalize=True):
+# (coarse, rescore_to) of a search whose to-side is never float32: equal forms share one handle
+MIXED_RESCORE_PAIRS = (("int8", "int8"), (BINARY, BINARY), (BINARY, "int8"))
+
+
+def check_rescore_to(value):
+    """`rescore_to` of the doors above the C ABI: None (rescoring reads the float32 to-side) or "int8" / "binary" / "ubinary":
+    the float32 from-vectors are rescored against the to-side in that form and no float32 to-side is kept.  Returns None, "int8"
+    or BINARY ("ubinary" is the same device form); anything else raises ValueError."""
+    if value is None:
+        return None
+    if isinstance(value, str) and (value == "int8" or value in BINARY_FORMS):
+        return BINARY if value in BINARY_FORMS else value
+    raise ValueError(f'rescore_to must be None, "int8" or one of {BINARY_FORMS}, got {value!r}')
+
+
+def check_mixed_pair(coarse, rescore_to):
+    """ValueError unless (coarse operand type, checked rescore_to) is one of MIXED_RESCORE_PAIRS."""
+    if (coarse, rescore_to) not in MIXED_RESCORE_PAIRS:
+        raise ValueError(f"rescore_to={rescore_to!r} cannot follow a {coarse} search: the pairs are "
+                         + ", ".join(f"{c} -> {r}" for c, r in MIXED_RESCORE_PAIRS))
+
+
+def dense_rescored_topn_host(ctx, from_vec, to_vec, ntop, lower_bound, coarse, multiplier, exclude_diag=False, normalize=True,
+                             rescore_to=None):
     """One-shot dense_topn_rescored on float arrays: both are uploaded twice, as `coarse` ("int8", "float16", "bfloat16", or
-    "binary": sign bits packed on the device, a Hamming search) operands and as float32 ones; (idx, val) host arrays out."""
+    "binary": sign bits packed on the device, a Hamming search) operands and as float32 ones; (idx, val) host arrays out.
+    rescore_to "int8" / "binary" (MIXED_RESCORE_PAIRS: int8 after int8, binary or int8 after binary): the to-side goes up as
+    `coarse` and in that form -- once when the two are equal -- and never as float32; the float32 from-vectors are scored against
+    it (dense_rescore_mixed).  to_vec is then a float array, or an array already in the `rescore_to` form, which must also be
+    `coarse`: np.int8 for "int8", packed np.uint8 / np.int8 rows for "binary"."""
     if not isinstance(coarse, str) or coarse not in RESCORE_COARSE:
         raise ValueError(f"coarse must be one of {RESCORE_COARSE}, got {coarse!r}")
     check_rescore_multiplier(multiplier)
+    rescore_to = check_rescore_to(rescore_to)
     same = to_vec is from_vec
     from_vec, to_vec = np.asarray(from_vec), np.asarray(to_vec)
-    for v in (from_vec, to_vec):
+    given = False          # to_vec is already in the rescore_to form
+    if rescore_to is not None:
+        check_mixed_pair(coarse, rescore_to)
+        given = to_vec.ndim == 2 and to_vec.dtype in ((np.int8,) if rescore_to == "int8" else (np.uint8, np.int8))
+        if given and coarse != rescore_to:
+            raise ValueError(f"a {to_vec.dtype} to-side is given in the {rescore_to} form: the search needs coarse={rescore_to!r}, "
+                             f"got {coarse!r} (pass float vectors to have both forms made on the device)")
+    for v in (from_vec,) if given else (from_vec, to_vec):
         if v.ndim != 2 or v.dtype.kind != "f" or v.dtype.itemsize < 4:
             raise ValueError(f"a rescored search takes 2-D float32 / float64 arrays, got {v.dtype} of shape {v.shape}")
-    if from_vec.shape[1] != to_vec.shape[1]:
-        raise ValueError(f"dense cosine needs two 2-D arrays with equal width, got {from_vec.shape} and {to_vec.shape}")
+    width = 8 * to_vec.shape[1] if given and rescore_to == BINARY else to_vec.shape[1]
+    if from_vec.shape[1] != width:
+        raise ValueError(f"dense cosine needs two 2-D arrays with equal width, got {from_vec.shape} and {(to_vec.shape[0], width)}"
+                         + (BITS_WIDTH_HINT if given and rescore_to == BINARY else ""))
     rescore_candidates(ntop, multiplier, to_vec.shape[0], exclude_diag)          # (raises before anything is uploaded)
-    return _dense_topn_host(ctx, from_vec, from_vec if same else to_vec, ntop, lower_bound, exclude_diag, normalize, coarse, multiplier)
+    return _dense_topn_host(ctx, from_vec, from_vec if same else to_vec, ntop, lower_bound, exclude_diag, normalize, coarse, multiplier,
+                            rescore_to)
 
 
 def pr_curve(ctx, sims, thresholds):

@@ -31,6 +31,8 @@
 //   k5_rescore_topn     : the companion of the 16-bit / int8 / 1-bit operands (pfz_dense_rescore_topn, opt-in): workgroup per
 //                         from-row, wave per candidate column of a coarse top-m; the exact score of the fp32 vectors
 //                         (float64 sum in a fixed order, rounded once), the same keys, ranked in LDS.
+//   k5_mixed_rescore    : its sibling for a to-side kept only as int8 values or bits (pfz_dense_rescore_topn_mixed, opt-in):
+//                         the float32 from-row against the quantised to-rows themselves, four candidates per wave.
 #include "pfz_internal.h"
 
 #include <algorithm>
@@ -958,6 +960,155 @@ __global__ __launch_bounds__(256) void k5_rescore_topn(const float *__restrict__
     }
 }
 
+// ---- rescoring float32 from-vectors against the int8 / 1-bit to-operand itself --------------------------------------------
+// The sibling of k5_rescore_topn for a to-side that exists only in its quantised form (pfz_dense_rescore_topn_mixed): the
+// same candidate table, keys, bound, ranking and result, one workgroup per from-row whose float32 vector is shared through LDS
+// (kRowInLds) or re-read from L2 -- but the to-row of a candidate is int8 values or packed sign bits, 768 or 96 bytes at
+// d = 768 where the float32 row has 3 072.  A wave per candidate would leave most lanes without a byte to read, so a wave
+// scores FOUR candidates at a time, 16 lanes each; lane g of a group reads one piece per step and the steps follow each other
+// along the row:
+//   int8: a piece is 16 B = values k = 256 c + 16 g + 0 .. 15 (a step is 256 B of the row: two 128 B lines per candidate);
+//         term a[k] * q[k], an fma in float64 -- the product of a float and an int8 is exact in it.
+//   bits: a piece is  8 B = bits   k = 1024 c + 64 g + 0 .. 63 (a step is 128 B: one line; a 96-byte row fills 12 of the 16
+//         lanes); term a[k] or -a[k] as the bit says, exact: the sum is the dot product with the +-1 vector the Hamming
+//         score speaks of.
+// The three pitches differ: the float32 row ends at ld_a (a multiple of 32 values), the int8 row at a multiple of 128 values,
+// the bit row at a multiple of 128 bits; a piece is read only when it starts inside the to-row's pitch, a float4 of the
+// from-row only inside ld_a, and what lies between dim and either end is zero in the from-row, so it adds +-0.
+// A lane takes the float4s of its piece in the order (t + r) mod n, r = g (bits: n = 16) or g / 4 (int8: n = 4): the 16 lanes
+// of a group then read 16 different bank quads of LDS in every step instead of one.  The order of a pair's sum is therefore a
+// function of k and the to-type alone -- g, c and r follow from k -- whichever wave, group or slot scores it: ascending steps
+// within a lane, then a xor butterfly over the group's 16 lanes (commutative steps: every lane ends with the same bits).
+// Equal to-rows give equal score bits and a permuted candidate list the same result, as k5_rescore_topn documents.
+// score: int8 fp32(inv_a[row] inv_b[j] sum) with the handle's own factor (1 / ||q||, the row's scale, or 1); bits
+// fp32(inv_a[row] sum / sqrt(dim)) -- the cosine of the float vector and the +-1 vector -- or fp32(sum) when not normalised.
+template <bool kBits, bool kRowInLds>
+__global__ __launch_bounds__(256) void k5_mixed_rescore(const float *__restrict__ A, const float *__restrict__ inv_a, int64_t n_a,
+                                                         int64_t ld_a, const unsigned char *__restrict__ B,
+                                                         const float *__restrict__ inv_b, int64_t n_b, int64_t pitch_b,
+                                                         int64_t dim, int32_t normalize, const int32_t *__restrict__ cand, int32_t m,
+                                                         int32_t ntop, float lower_bound, int32_t *__restrict__ out_idx,
+                                                         float *__restrict__ out_val)
+{
+    __shared__ __attribute__((aligned(16))) uint64_t keys[kRescoreMax];
+    __shared__ __attribute__((aligned(16))) float xs[kRowInLds ? kRescoreLds : 4];
+    constexpr int kPiece = kBits ? 64 : 16;            // values of a lane's piece
+    constexpr int kStep = 16 * kPiece;                 // values of a group's step
+    constexpr int kSteps = kBits ? 2 : 4;              // steps whose loads are in flight together
+    const int tid = threadIdx.x, wave = tid >> 6, grp = (tid >> 4) & 3, g = tid & 15;
+    const int rot = kBits ? g : g >> 2;
+    const int len_a = (int)ld_a, len_b = (int)(kBits ? pitch_b * 8 : pitch_b);      // the two rows' ends, in values
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    const double root_dim = sqrt((double)dim);
+    for (int64_t row = blockIdx.x; row < n_a; row += gridDim.x) {
+        const float *xa = A + row * ld_a;
+        if (kRowInLds) {
+            for (int k = tid * 4; k < len_a; k += 1024) *(float4 *)(xs + k) = *(const float4 *)(xa + k);
+            __syncthreads();
+        }
+        const float *pa = kRowInLds ? xs : xa;
+        const double fa = (double)inv_a[row];
+        const int32_t *c = cand + row * m;
+        for (int slot0 = 0; slot0 < m; slot0 += 16) {
+            const int slot = slot0 + wave * 4 + grp;
+            const int32_t j = slot < m ? c[slot] : -1;
+            const bool live = j >= 0 && j < n_b;
+            double acc = 0.0;
+            if (live) {
+                const unsigned char *xb = B + (int64_t)j * pitch_b;
+                for (int k0 = 0; k0 < len_b; k0 += kSteps * kStep) {
+                    if (kBits) {
+                        uint2 w[kSteps];
+#pragma unroll
+                        for (int u = 0; u < kSteps; ++u) {
+                            const int k = k0 + u * kStep + g * kPiece;
+                            w[u] = k < len_b ? *(const uint2 *)(xb + (k >> 3)) : make_uint2(0u, 0u);
+                        }
+#pragma unroll
+                        for (int u = 0; u < kSteps; ++u) {
+                            const int k = k0 + u * kStep + g * kPiece;
+                            if (k >= len_b) continue;
+                            const uint64_t bits = ((uint64_t)w[u].y << 32) | w[u].x;
+#pragma unroll 4
+                            for (int t = 0; t < 16; ++t) {
+                                const int tt = (t + rot) & 15, ka = k + 4 * tt;
+                                const float4 a = ka < len_a ? *(const float4 *)(pa + ka) : zero;
+                                // values 4 tt .. 4 tt + 3 of the piece: byte tt / 2, its high nibble first, most significant bit first
+                                const uint32_t nib = ~(uint32_t)(bits >> (8 * (tt >> 1) + 4 * (1 - (tt & 1))));
+                                acc += (double)__uint_as_float(__float_as_uint(a.x) ^ ((nib << 28) & 0x80000000u));
+                                acc += (double)__uint_as_float(__float_as_uint(a.y) ^ ((nib << 29) & 0x80000000u));
+                                acc += (double)__uint_as_float(__float_as_uint(a.z) ^ ((nib << 30) & 0x80000000u));
+                                acc += (double)__uint_as_float(__float_as_uint(a.w) ^ ((nib << 31) & 0x80000000u));
+                            }
+                        }
+                    }
+                    else {
+                        u32x4 q[kSteps];
+#pragma unroll
+                        for (int u = 0; u < kSteps; ++u) {
+                            const int k = k0 + u * kStep + g * kPiece;
+                            const u32x4 none = {0u, 0u, 0u, 0u};
+                            q[u] = k < len_b ? *(const u32x4 *)(xb + k) : none;
+                        }
+#pragma unroll
+                        for (int u = 0; u < kSteps; ++u) {
+                            const int k = k0 + u * kStep + g * kPiece;
+                            if (k >= len_b) continue;
+#pragma unroll
+                            for (int t = 0; t < 4; ++t) {
+                                const int tt = (t + rot) & 3, ka = k + 4 * tt;
+                                const float4 a = ka < len_a ? *(const float4 *)(pa + ka) : zero;
+                                const int32_t v = (int32_t)(tt == 0 ? q[u].x : tt == 1 ? q[u].y : tt == 2 ? q[u].z : q[u].w);
+                                acc = fma((double)a.x, (double)((v << 24) >> 24), acc);
+                                acc = fma((double)a.y, (double)((v << 16) >> 24), acc);
+                                acc = fma((double)a.z, (double)((v << 8) >> 24), acc);
+                                acc = fma((double)a.w, (double)(v >> 24), acc);
+                            }
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int o = 8; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);      // (within the group of 16; every lane takes part)
+            uint64_t key = 0ull;
+            if (live) {
+                const float s = kBits ? (normalize ? (float)(fa * acc / root_dim) : (float)acc) : (float)(fa * (double)inv_b[j] * acc);
+                if (s > lower_bound) key = ((uint64_t)__float_as_uint(s) << 32) | (uint32_t)(~(uint32_t)j);
+            }
+            if (g == 0 && slot < m) keys[slot] = key;
+        }
+        __syncthreads();
+        // the ranking of k5_rescore_topn: a thread counts the keys above each of its own and writes rank r < ntop to column r
+        uint64_t mine[kRescoreMax / 256];
+        int rank[kRescoreMax / 256];
+#pragma unroll
+        for (int u = 0; u < kRescoreMax / 256; ++u) {
+            mine[u] = tid + 256 * u < m ? keys[tid + 256 * u] : 0ull;
+            rank[u] = 0;
+        }
+        int n_keys = 0;
+        for (int q = 0; q < m; ++q) {
+            const uint64_t k = keys[q];
+            n_keys += k != 0ull;
+#pragma unroll
+            for (int u = 0; u < kRescoreMax / 256; ++u) rank[u] += k > mine[u];
+        }
+        int32_t *oi = out_idx + row * ntop;
+        float *ov = out_val + row * ntop;
+#pragma unroll
+        for (int u = 0; u < kRescoreMax / 256; ++u)
+            if (mine[u] && rank[u] < ntop) {
+                oi[rank[u]] = (int32_t)(~(uint32_t)mine[u]);
+                ov[rank[u]] = __uint_as_float((uint32_t)(mine[u] >> 32));
+            }
+        for (int r = n_keys + tid; r < ntop; r += 256) {
+            oi[r] = -1;
+            ov[r] = 0.f;
+        }
+        __syncthreads();      // the next row reuses keys and xs
+    }
+}
+
 }  // namespace pfz
 
 using namespace pfz;
@@ -1299,6 +1450,58 @@ int pfz_dense_rescore_topn(pfz_ctx *ctx, const pfz_dense *from_exact, const pfz_
         hipLaunchKernelGGL(kernel, grid, dim3(256), 0, ctx->stream, (const float *)from_exact->x, (const float *)from_exact->inv, n_from,
                            (const float *)to_exact->x, (const float *)to_exact->inv, to_exact->n, from_exact->ld,
                            (const int32_t *)candidates->idx, m, ntop, lower_bound, out->idx, out->val);
+    }
+    PFZ_HIP(hipGetLastError());
+    return PFZ_OK;
+}
+
+int pfz_dense_rescore_topn_mixed(pfz_ctx *ctx, const pfz_dense *from_exact, const pfz_dense *to_coarse, const pfz_topn *candidates,
+                                 int32_t ntop, float lower_bound, pfz_topn *out)
+{
+    PFZ_REQUIRE(ctx && from_exact && to_coarse && candidates && out, "pfz_dense_rescore_topn_mixed: NULL argument");
+    PFZ_REQUIRE(from_exact->dtype == PFZ_DENSE_F32, "pfz_dense_rescore_topn_mixed: the from-vectors must be float32, got %s",
+                dense_dtype_name(from_exact->dtype));
+    const bool bits = to_coarse->dtype == PFZ_DENSE_B1;
+    PFZ_REQUIRE(bits || to_coarse->dtype == PFZ_DENSE_I8,
+                "pfz_dense_rescore_topn_mixed: the to-vectors must be int8 or binary, got %s (pfz_dense_rescore_topn is the entry for "
+                "float32 to-vectors)", dense_dtype_name(to_coarse->dtype));
+    PFZ_REQUIRE(!bits || from_exact->dim == to_coarse->dim,
+                "pfz_dense_rescore_topn_mixed: from-vectors have %lld columns, to-vectors %lld bits (rows packed on the host count 8 "
+                "bits per byte: float vectors whose width is not a multiple of 8 cannot be paired with them)",
+                (long long)from_exact->dim, (long long)to_coarse->dim);
+    PFZ_REQUIRE(from_exact->dim == to_coarse->dim, "pfz_dense_rescore_topn_mixed: from-vectors have %lld columns, to-vectors %lld",
+                (long long)from_exact->dim, (long long)to_coarse->dim);
+    PFZ_REQUIRE(!bits || from_exact->normalize == to_coarse->normalize,
+                "pfz_dense_rescore_topn_mixed: the binary to-vectors were uploaded %s normalize, the from-vectors %s: the score is "
+                "one or the other", to_coarse->normalize ? "with" : "without", from_exact->normalize ? "with" : "without");
+    PFZ_REQUIRE(candidates != out, "pfz_dense_rescore_topn_mixed: the candidate table and the result are one buffer");
+    PFZ_REQUIRE(candidates->n_rows >= from_exact->n,
+                "pfz_dense_rescore_topn_mixed: the candidate table has %lld rows, the from-vectors %lld", (long long)candidates->n_rows,
+                (long long)from_exact->n);
+    const int32_t m = candidates->ntop;
+    if (m > kRescoreMax) {
+        set_error("pfz_dense_rescore_topn_mixed: %d candidates per row exceed the %d one pass ranks", m, kRescoreMax);
+        return PFZ_ERR_UNSUPPORTED;
+    }
+    PFZ_REQUIRE(ntop >= 1 && ntop <= m, "pfz_dense_rescore_topn_mixed: ntop %d is outside 1 .. %d, the candidates per row", ntop, m);
+    PFZ_REQUIRE(lower_bound == lower_bound, "pfz_dense_rescore_topn_mixed: lower_bound is NaN");
+    PFZ_REQUIRE(out->n_rows >= from_exact->n && out->ntop == ntop, "pfz_dense_rescore_topn_mixed: result buffer is %lldx%d, need %lldx%d",
+                (long long)out->n_rows, out->ntop, (long long)from_exact->n, ntop);
+    const int64_t n_from = from_exact->n;
+    if (n_from == 0) return PFZ_OK;
+    PFZ_HIP(hipSetDevice(ctx->device));
+    if (lower_bound < 0.f) lower_bound = 0.f;   // non-positive similarities are "no match" (_utils.py:122-123)
+    {
+        ProfScope ps(ctx, "k5_mixed_rescore");
+        const bool lds = from_exact->ld <= kRescoreLds;
+        auto *kernel = bits ? (lds ? k5_mixed_rescore<true, true> : k5_mixed_rescore<true, false>)
+                            : (lds ? k5_mixed_rescore<false, true> : k5_mixed_rescore<false, false>);
+        const int64_t pitch = bits ? to_coarse->ld / 8 : to_coarse->ld;      // bytes of a to-row
+        const dim3 grid((unsigned)std::min<int64_t>(n_from, (int64_t)1 << 20));
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, ctx->stream, (const float *)from_exact->x, (const float *)from_exact->inv, n_from,
+                           from_exact->ld, (const unsigned char *)to_coarse->x, (const float *)to_coarse->inv, to_coarse->n, pitch,
+                           to_coarse->dim, to_coarse->normalize, (const int32_t *)candidates->idx, m, ntop, lower_bound, out->idx,
+                           out->val);
     }
     PFZ_HIP(hipGetLastError());
     return PFZ_OK;

@@ -80,6 +80,22 @@ class Embeddings(BaseMatcher):
                    for packed uint8 / int8 arrays (no full-precision vectors).  `match` raises ValueError when it is set
                    together with `precision` or a `compute_dtype` other than None / "float32".  Anything else raises
                    ValueError; kept through pickling; the resident to-side is re-uploaded when it changes.
+        rescore_to: None (default: `rescore_multiplier` scores against the float32 vectors of both sides, as above) or "int8" /
+                   "binary" / "ubinary": `m.binary = "ubinary"; m.rescore_multiplier = 16; m.rescore_to = "int8"`.  The
+                   candidates are then scored with the float32 FROM-vectors against the TO-side in that form (k5_mixed_rescore:
+                   float64 sums, rounded once), the way sentence-transformers rescores a quantised corpus: the to-side never
+                   exists as float32 on the device -- at 500 000 x 768, 48 MB of bits (+ 0.38 GB with "int8") instead of
+                   1.54 GB beside them.  The pairs are precision="int8" with "int8", `binary` with "binary" / "ubinary", and
+                   `binary` with "int8" ("binary search, int8 rescoring"); anything else, a 16-bit `compute_dtype`, or no
+                   `rescore_multiplier` makes `match` raise ValueError.  The Similarity is the cosine (cosine_method "sparse":
+                   the dot product) of the float from-vector and the int8 to-vector -- dequantised, for float to-vectors
+                   quantised here -- or of the float from-vector and the +-1 vector the bits stand for, to 1e-5;
+                   `min_similarity` cuts on it.  The columns are the fp32 top-n only as far as the quantised to-side ranks
+                   them so.  `embeddings_from` must be float (np.int8 / packed arrays raise "no full-precision vectors");
+                   `embeddings_to` may be float, or for equal forms the np.int8 array or the packed np.uint8 / np.int8 array
+                   itself -- a corpus that exists only in quantised form.  Validated when set, kept through pickling; the
+                   to-side of the rescoring is resident like the coarse one and re-made when `rescore_to` or the to-side
+                   changes.
     """
     def __init__(self,
                  embedding_method: Optional[Callable[[List[str]], np.ndarray]] = None,
@@ -105,6 +121,8 @@ class Embeddings(BaseMatcher):
         self._rescore_multiplier = None
         self._dev_to_exact = None      # float32 DeviceDense of the to-side, beside _dev_to, while rescoring is on
         self._binary = None
+        self._rescore_to = None
+        self._dev_to_exact_form = None  # what _dev_to_exact holds: "float32", or the checked rescore_to it was made for
 
     @property
     def compute_dtype(self) -> Optional[str]:
@@ -138,6 +156,15 @@ class Embeddings(BaseMatcher):
     @binary.setter
     def binary(self, value: Optional[str]):
         self._binary = _lib.check_binary(value)
+
+    @property
+    def rescore_to(self) -> Optional[str]:
+        return self._rescore_to
+
+    @rescore_to.setter
+    def rescore_to(self, value: Optional[str]):
+        _lib.check_rescore_to(value)
+        self._rescore_to = value
 
     def match(self,
               from_list: List[str],
@@ -176,11 +203,30 @@ class Embeddings(BaseMatcher):
             dtype = _lib.operand_type(self.compute_dtype, self.precision)
             upload = _lib.DeviceDense.upload_as
         multiplier = _lib.check_rescore_multiplier(self.rescore_multiplier)
+        rescore_to = _lib.check_rescore_to(self.rescore_to)
+        if rescore_to is not None:
+            if multiplier is None:
+                raise ValueError(f"rescore_to={self.rescore_to!r} is set without a rescore_multiplier: there are no candidates "
+                                 "to rescore (set rescore_multiplier to an int >= 1, or leave rescore_to at None)")
+            if dtype in ("float16", "bfloat16"):
+                raise ValueError(f"rescore_to={self.rescore_to!r} is set together with compute_dtype={self.compute_dtype!r}: "
+                                 'the to-side is rescored in its int8 or binary form (set precision="int8" or binary)')
+            if dtype != "float32":
+                _lib.check_mixed_pair(dtype, rescore_to)
         if multiplier is not None:
             if dtype == "float32":
                 raise ValueError("rescore_multiplier is set but the operands are float32: there is nothing to rescore "
                                  '(set precision="int8" or a 16-bit compute_dtype, or leave rescore_multiplier at None)')
-            for side, vec in (("embeddings_from", embeddings_from), ("embeddings_to", embeddings_to)):
+            sides = (("embeddings_from", embeddings_from), ("embeddings_to", embeddings_to))
+            if rescore_to is not None:
+                to = np.asarray(embeddings_to)
+                if to.dtype == np.int8 or (bits and to.dtype == np.uint8):      # the to-side as the search itself reads it
+                    if dtype != rescore_to:
+                        raise ValueError(f"embeddings_to is already a {to.dtype} array, the {dtype} search's own form: "
+                                         f"rescore_to={self.rescore_to!r} can only name the same form then (pass float "
+                                         "embeddings to have both forms made here)")
+                    sides = sides[:1]
+            for side, vec in sides:
                 if np.asarray(vec).dtype in (np.int8, np.float16, np.uint16) + ((np.uint8,) if bits else ()):
                     raise ValueError(f"rescore_multiplier is set but {side} is already a {np.asarray(vec).dtype} array: "
                                      "there are no full-precision vectors to rescore against (pass float32 embeddings)")
@@ -195,8 +241,12 @@ class Embeddings(BaseMatcher):
             self._dev_to_normalize = normalize
             self._dev_to_dtype = dtype
             self._dev_to_exact = None
-        if multiplier is not None and self._dev_to_exact is None:      # (follows every re-upload of the coarse to-side)
-            self._dev_to_exact = upload(ctx, embeddings_to, "float32", normalize)
+        exact_form = "float32" if rescore_to is None else rescore_to
+        if multiplier is not None and (self._dev_to_exact is None or self._dev_to_exact_form != exact_form):
+            # (follows every re-upload of the coarse to-side.)  With rescore_to no float32 to-side is made: the coarse handle
+            # itself, or the int8 form beside the bits
+            self._dev_to_exact = self._dev_to if exact_form == dtype else upload(ctx, embeddings_to, exact_form, normalize)
+            self._dev_to_exact_form = exact_form
         self_match = to_list is None
         same = self_match and embeddings_to is embeddings_from
         from_dev = self._dev_to if same else upload(ctx, embeddings_from, dtype, normalize)
@@ -205,7 +255,7 @@ class Embeddings(BaseMatcher):
                              + (_lib.BITS_WIDTH_HINT if bits else ""))
         top_n = clip_top_n(self.top_n, to_list)
         if multiplier is not None:
-            from_exact = self._dev_to_exact if same else upload(ctx, embeddings_from, "float32", normalize)
+            from_exact = self._dev_to_exact if same and rescore_to is None else upload(ctx, embeddings_from, "float32", normalize)
             idx, val = _lib.dense_topn_rescored(ctx, from_dev, self._dev_to, from_exact, self._dev_to_exact, max(top_n, 1), lower,
                                                 multiplier, exclude_diag=self_match).download()
         else:
@@ -223,6 +273,8 @@ class Embeddings(BaseMatcher):
         self.__dict__.setdefault("_precision", None)
         self.__dict__.setdefault("_rescore_multiplier", None)
         self.__dict__.setdefault("_binary", None)
+        self.__dict__.setdefault("_rescore_to", None)
+        self.__dict__.setdefault("_dev_to_exact_form", None)
         self._dev_to = None
         self._dev_to_exact = None
 

@@ -297,7 +297,11 @@ class DenseMatchJob:
     row on those operands and scores them against the float32 form of the same vectors, rescore_from / rescore_to -- arrays
     (uploaded here with `normalize`) or float32 DeviceDense handles of this context; rescore_to=None with to_vectors=None
     is the from-side again (_lib.dense_topn_rescored).  The scores and `min_similarity` are then the fp32 path's; the
-    candidate buffer is allocated here, once."""
+    candidate buffer is allocated here, once.
+    rescore_to may instead be an int8 or 1-bit DeviceDense of this context with the shape of to_vectors -- the to_vectors handle
+    itself, or an int8 handle beside 1-bit to_vectors: the float32 rescore_from is then scored against that quantised to-side
+    (_lib.dense_rescore_mixed) and no float32 to-side exists on the device.  The scores are those of the float from-vectors and
+    the quantised to-vectors; the columns are the fp32 top-n only as far as that to-side ranks them so."""
 
     def __init__(self, ctx, from_shard, to_vectors, top_n=1, min_similarity=0.0, normalize=True, comm=None,
                  self_match=False, shard_offset=0, rows_per_rank=None, rescore_from=None, rescore_to=None,
@@ -326,7 +330,12 @@ class DenseMatchJob:
                 return vec if isinstance(vec, _lib.DeviceDense) else _lib.DeviceDense.upload_as(ctx, vec, "float32", normalize)
             self.from_exact = exact(rescore_from)
             self.to_exact = self.from_exact if rescore_to is None else exact(rescore_to)
+            # a quantised to-side to rescore the float32 from-vectors against (one of _lib.MIXED_RESCORE_PAIRS)
+            mixed = (isinstance(rescore_to, _lib.DeviceDense) and self.from_exact.dtype == "float32"
+                     and (self.to_dev.dtype, rescore_to.dtype) in _lib.MIXED_RESCORE_PAIRS)
             for coarse, fine in ((self.from_dev, self.from_exact), (self.to_dev, self.to_exact)):
+                if mixed and fine is self.to_exact and (fine.n, fine.dim) == (coarse.n, coarse.dim):
+                    continue
                 if fine.dtype != "float32" or (fine.n, fine.dim) != (coarse.n, coarse.dim):
                     raise ValueError(f"the rescoring operand is {fine.dtype} {(fine.n, fine.dim)}; it must be the float32 form "
                                      f"of the {(coarse.n, coarse.dim)} vectors that are searched")
