@@ -79,7 +79,9 @@ int pfz_event_wait(pfz_ctx *ctx, int32_t slot);
 int pfz_prof_enable(pfz_ctx *ctx, int32_t on);
 int pfz_prof_reset(pfz_ctx *ctx);
 /* total ms and launch count of kernel `name` since the last reset (blocks).  Every form of K3 is timed as
- * `k3_cossim_topn`; `k3_lockstep` (0 ms, a count only) says how many of those launches the lock-step form served. */
+ * `k3_cossim_topn`; `k3_lockstep` (0 ms, a count only) says how many of those launches the lock-step form served.
+ * K8: `k8_jaro` (every launch of a call), `k8_jaro_general` (its general-kernel launches), `k8_pairs_scored` (0 ms; the
+ * count is the number of pairs whose float64 score was computed). */
 int pfz_prof_get(pfz_ctx *ctx, const char *name, double *total_ms, int64_t *launches);
 
 /* ---- CSR matrices --------------------------------------------------------
@@ -307,6 +309,36 @@ int pfz_fuzz_extract_one_dev(pfz_ctx *ctx, const pfz_strings *from_strings, cons
  * strings, strings with more than 32 distinct tokens (scored by the general kernel) */
 int pfz_fuzz_plan_info(pfz_ctx *ctx, const pfz_strings *to_strings, int64_t *n_symbols, int64_t *n_groups, int64_t *n_tokens,
                        int64_t *n_general_strings);
+
+/* ---- K8: all-pairs Jaro / Jaro-Winkler similarity + row arg-max --------------
+ * Replaces the hot loop of EditDistance._calculate_edit_distance (reference
+ * polyfuzz/models/_distance.py:89-102) with the `scorer` argument (_distance.py:32) set to
+ * jellyfish.jaro_similarity (scorer = 0) or jellyfish.jaro_winkler_similarity (scorer = 1), the scorer of
+ * the reference's custom-model tutorial: for every from-string of rows [from_begin, from_end) the FIRST
+ * to-string with the maximal score (np.argmax, _distance.py:99) and that score, float64 on jellyfish's
+ * 0..1 scale, on code points, with jellyfish's default arguments (no long_tolerance):
+ *   r = max(max(|a|,|b|) / 2 - 1, 0); greedy matches within r positions, m of them; t = the number of k whose
+ *   k-th matched characters of a and of b differ, halved rounding down;
+ *   w = (m/|a| + m/|b| + (m - t)/m) / 3, 0 when m = 0 (so 0 when either string is empty);
+ *   Jaro-Winkler: w > 0.7 becomes w + (l * 0.1) * (1 - w), l = common prefix, at most 4.
+ * skip_idx, the row range and the -1 / 0 result of a row without a candidate: as pfz_indel_argmax.
+ * Any length and any alphabet: from-strings of up to 64 characters against to-strings of up to 256 run in
+ * registers, all other pairs in a general -- slow -- kernel.  The to-side preparation is pfz_indel_*'s,
+ * cached on the to-list's handle.  PARITY UNPINNED: the scorers restate jellyfish's definition; jellyfish itself
+ * is compared wherever it is installed (tests/test_jaro_cpu.py).
+ * scorer outside {0, 1}: PFZ_ERR_INVALID.  out_idx / out_score: host buffers of from_end - from_begin
+ * entries.  Blocks. */
+int pfz_jaro_argmax(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings, int32_t scorer,
+                    const int32_t *skip_idx, int64_t from_begin, int64_t from_end, int32_t *out_idx, double *out_score);
+/* pfz_jaro_argmax with the result left on the device in the layout of pfz_indel_argmax_dev (_distance.py:89-102): `out`
+ * must have 2 columns and >= from_end - from_begin rows; row r gets idx[r][0] = the first arg-max (idx[r][1] = -1)
+ * and the float64 score's bits in its two value lanes.  Enqueues. */
+int pfz_jaro_argmax_dev(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings, int32_t scorer,
+                        const int32_t *skip_idx, int64_t from_begin, int64_t from_end, pfz_topn *out);
+/* every score (_distance.py:32,97) of rows [from_begin, from_end) x all to-strings as float64, row-major host buffer
+ * (test / small-input entry point).  Blocks. */
+int pfz_jaro_matrix_host(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings, int32_t scorer,
+                         int64_t from_begin, int64_t from_end, double *out_matrix);
 
 /* ---- K5: dense cosine top-n -----------------------------------------------
  * Replaces cosine_similarity on dense embedding matrices

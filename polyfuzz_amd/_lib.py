@@ -91,6 +91,9 @@ SIGNATURES = {
     "pfz_indel_matrix_host": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp]),
     "pfz_indel_plan_info": (ctypes.c_int, [c_vp, c_vp, P(c_i64), P(c_i64), P(c_i64)]),
     "pfz_indel_argmax_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp]),
+    "pfz_jaro_argmax": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
+    "pfz_jaro_argmax_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp]),
+    "pfz_jaro_matrix_host": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_vp]),
     "pfz_fuzz_extract_one": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "pfz_fuzz_extract_one_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "pfz_fuzz_plan_info": (ctypes.c_int, [c_vp, c_vp, P(c_i64), P(c_i64), P(c_i64), P(c_i64)]),
@@ -725,6 +728,38 @@ def indel_matrix(ctx, from_dev, to_dev, begin=0, end=None):
     end = from_dev.n if end is None else end
     out = np.empty((end - begin, to_dev.n), np.float64)
     check(ctx.lib.pfz_indel_matrix_host(ctx.h, from_dev.h, to_dev.h, int(begin), int(end), _ptr(out)))
+    return out
+
+
+# K8: jellyfish.jaro_similarity / jaro_winkler_similarity (default arguments), float64 on the 0..1 scale.  PARITY UNPINNED:
+# jellyfish is not importable where this was built; the definition is restated in include/polyfuzz_hip.h.
+JARO_SCORERS = {"jaro": 0, "jaro_winkler": 1}
+
+
+def jaro_argmax(ctx, from_dev, to_dev, scorer, skip_idx=None, begin=0, end=None):
+    """K8: (first arg-max index int32[n], score float64[n]) of from-rows [begin, end)."""
+    end = from_dev.n if end is None else end
+    n = end - begin
+    idx = np.empty(n, np.int32)
+    score = np.empty(n, np.float64)
+    skip_idx = _skip_array(skip_idx, from_dev.n)
+    check(ctx.lib.pfz_jaro_argmax(ctx.h, from_dev.h, to_dev.h, JARO_SCORERS[scorer], _ptr(skip_idx), int(begin), int(end),
+                                  _ptr(idx), _ptr(score)))
+    return idx, score
+
+
+def jaro_argmax_dev(ctx, from_dev, to_dev, scorer, out, skip_idx=None, begin=0, end=None):
+    """K8 with the (first arg-max, float64 score) rows left in the 2-column DeviceTopN `out` (see best_from_topn)."""
+    end = from_dev.n if end is None else end
+    skip_idx = _skip_array(skip_idx, from_dev.n)
+    check(ctx.lib.pfz_jaro_argmax_dev(ctx.h, from_dev.h, to_dev.h, JARO_SCORERS[scorer], _ptr(skip_idx), int(begin), int(end), out.h))
+
+
+def jaro_matrix(ctx, from_dev, to_dev, scorer, begin=0, end=None):
+    """K8: every score of from-rows [begin, end) x all to-strings, float64 [end - begin, n_to] (the test entry)."""
+    end = from_dev.n if end is None else end
+    out = np.empty((end - begin, to_dev.n), np.float64)
+    check(ctx.lib.pfz_jaro_matrix_host(ctx.h, from_dev.h, to_dev.h, JARO_SCORERS[scorer], int(begin), int(end), _ptr(out)))
     return out
 
 

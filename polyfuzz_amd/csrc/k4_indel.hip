@@ -31,7 +31,7 @@
 // on its pfz_strings handle, so a repeated to-list costs no preparation at all.
 // Roofline: integer VALU + LDS lookups; HBM traffic is the to-strings once per
 // from-string out of L2 (0.3 MB) -- not HBM-bound.
-#include "pfz_internal.h"
+#include "k4_plan.h"
 
 #include <algorithm>
 #include <limits.h>
@@ -575,23 +575,6 @@ __global__ __launch_bounds__(256) void k4_pack(const void *__restrict__ chars, c
 
 }  // namespace pfz
 
-struct pfz_indel_plan {
-    pfz_ctx *ctx = nullptr;
-    int32_t n_sym = 0, idb = 8;          // alphabet size, bits per packed symbol
-    uint32_t lut_len = 0;
-    uint16_t *lut = nullptr;             // device [lut_len]
-    uint32_t *packed = nullptr;          // device
-    int64_t *g_off = nullptr;
-    int32_t *g_steps = nullptr, *b_len = nullptr, *b_orig = nullptr;
-    int64_t n_groups = 0;
-    int64_t char_steps = 0;              // sum over to-strings of their (padded) steps * 64 / per: the bench's work count
-    ~pfz_indel_plan()
-    {
-        for (void *p : {(void *)lut, (void *)packed, (void *)g_off, (void *)g_steps, (void *)b_len, (void *)b_orig})
-            if (p) pfz::pool_free(p);
-    }
-};
-
 void pfz_indel_plan_free(pfz_indel_plan *p) { delete p; }
 
 namespace pfz {
@@ -685,6 +668,14 @@ static int build_plan(pfz_ctx *ctx, const pfz_strings *T, pfz_indel_plan **out)
     return PFZ_OK;
 }
 
+int indel_plan_get(pfz_ctx *ctx, const pfz_strings *T_c, const pfz_indel_plan **out)
+{
+    pfz_strings *T = const_cast<pfz_strings *>(T_c);    // the plan cache lives inside the (otherwise read-only) to-list
+    if (!T->indel_plan) PFZ_TRY(build_plan(ctx, T, &T->indel_plan));
+    *out = T->indel_plan;
+    return PFZ_OK;
+}
+
 template <typename WORD, int W>
 static int launch_class(pfz_ctx *ctx, const IndelArgs &A, int idb, unsigned grid, hipStream_t st)
 {
@@ -710,9 +701,9 @@ static int indel_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T_c,
         set_error("pfz_indel: list too long");
         return PFZ_ERR_UNSUPPORTED;
     }
-    pfz_strings *T = const_cast<pfz_strings *>(T_c);    // the plan cache lives inside the (otherwise read-only) to-list
-    if (!T->indel_plan) PFZ_TRY(build_plan(ctx, T, &T->indel_plan));
-    const pfz_indel_plan *pl = T->indel_plan;
+    const pfz_strings *T = T_c;
+    const pfz_indel_plan *pl;
+    PFZ_TRY(indel_plan_get(ctx, T, &pl));
 
     // from side: word classes by length
     static const int kClassMax[7] = {32, 64, 128, 256, 512, 1024, INT_MAX};
@@ -937,14 +928,12 @@ int pfz_indel_matrix_host(pfz_ctx *ctx, const pfz_strings *from_strings, const p
 int pfz_indel_plan_info(pfz_ctx *ctx, const pfz_strings *to_strings, int64_t *n_symbols, int64_t *n_groups, int64_t *char_steps)
 {
     PFZ_REQUIRE(ctx && to_strings, "pfz_indel_plan_info: NULL argument");
-    pfz_strings *T = const_cast<pfz_strings *>(to_strings);
-    if (!T->indel_plan) {
-        PFZ_HIP(hipSetDevice(ctx->device));
-        PFZ_TRY(build_plan(ctx, T, &T->indel_plan));
-    }
-    if (n_symbols) *n_symbols = T->indel_plan->n_sym;
-    if (n_groups) *n_groups = T->indel_plan->n_groups;
-    if (char_steps) *char_steps = T->indel_plan->char_steps;
+    PFZ_HIP(hipSetDevice(ctx->device));
+    const pfz_indel_plan *pl;
+    PFZ_TRY(indel_plan_get(ctx, to_strings, &pl));
+    if (n_symbols) *n_symbols = pl->n_sym;
+    if (n_groups) *n_groups = pl->n_groups;
+    if (char_steps) *char_steps = pl->char_steps;
     return PFZ_OK;
 }
 

@@ -373,9 +373,9 @@ ProfScope::~ProfScope()
     pe.end.push_back(e);
 }
 
-void prof_count(pfz_ctx *ctx, const char *name)
+void prof_count(pfz_ctx *ctx, const char *name, int64_t n)
 {
-    if (ctx->prof) ctx->prof_entries[name].launches += 1;
+    if (ctx->prof) ctx->prof_entries[name].launches += n;
 }
 
 static void prof_fold(pfz_ctx *ctx, ProfEntry &pe)

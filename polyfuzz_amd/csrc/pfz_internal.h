@@ -285,8 +285,8 @@ struct ProfScope {
     ~ProfScope();
 };
 // a launch counted under a name of its own while ctx->prof is on: no events, no time (pfz_prof_get: 0 ms, the count) -- which of
-// several kernels that share one timed scope served a call
-void prof_count(pfz_ctx *ctx, const char *name);
+// several kernels that share one timed scope served a call (n = 1), or how much work a launch did (K8: pairs scored)
+void prof_count(pfz_ctx *ctx, const char *name, int64_t n = 1);
 
 // Caching device allocator of a context (pfz_api.hip).  hipMalloc/hipFree are
 // slow and hipFree synchronises the device, so blocks are size-classed and

@@ -7,6 +7,8 @@ first arg-max per from-string.  Here the whole score matrix + arg-max is one HIP
 kernel (K4: bit-parallel LCS, fused first-max reduction).  `scorer` may be any
 rapidfuzz.fuzz scorer (or its name): ratio / QRatio / token_sort_ratio run through K4,
 WRatio / partial_ratio / token_set_ratio / token_ratio / partial_token_* through K7;
+or jellyfish.jaro_similarity / jaro_winkler_similarity (the scorer of the reference's
+custom-model tutorial, docs/tutorial/models/models.md:46-58), which run through K8;
 any other callable raises -- there is no CPU path to fall back to.
 """
 import time
@@ -20,11 +22,35 @@ from ._base import BaseMatcher
 from ._utils import pair_frame, pair_frame_blocks
 
 
+_JARO_NAMES = {"jaro": "jaro", "jaro_similarity": "jaro", "jaro_winkler": "jaro_winkler", "jaro_winkler_similarity": "jaro_winkler"}
+_JELLYFISH_FUNCTIONS = ("jaro_similarity", "jaro_winkler_similarity")
+
+
+def _jaro_scorer(scorer) -> str:
+    """K8's name ("jaro" / "jaro_winkler") of the jellyfish function `scorer` stands for, or '': one of the four names, a
+    callable of jellyfish's that carries one of its two names, or -- compiled functions do not always say where they are
+    from -- the very object jellyfish exports under that name.  A functools.partial (long_tolerance=True has no kernel) or
+    somebody else's function of the same name is neither."""
+    if isinstance(scorer, str):
+        return _JARO_NAMES.get(scorer, "")
+    name = getattr(scorer, "__name__", "")
+    if name in _JELLYFISH_FUNCTIONS and (getattr(scorer, "__module__", "") or "").split(".")[0] == "jellyfish":
+        return _JARO_NAMES[name]
+    try:
+        import jellyfish
+    except ImportError:
+        return ""
+    return next((_JARO_NAMES[n] for n in _JELLYFISH_FUNCTIONS if getattr(jellyfish, n, None) is scorer), "")
+
+
 def _device_scorer(scorer) -> str:
-    """Name of the rapidfuzz.fuzz scorer `scorer` stands for, or '' when it has no kernel."""
+    """Name of the rapidfuzz.fuzz scorer (or K8's name of the jellyfish scorer) `scorer` stands for, or '' when it has no
+    kernel."""
     from ._rapidfuzz import _DEVICE_SCORERS
     if scorer is None:
         return "ratio"                                     # the reference's default (_distance.py:32)
+    if _jaro_scorer(scorer):
+        return _jaro_scorer(scorer)
     name = scorer if isinstance(scorer, str) else getattr(scorer, "__name__", "")
     if not isinstance(scorer, str) and "rapidfuzz" not in (getattr(scorer, "__module__", "") or ""):
         return ""
@@ -37,8 +63,10 @@ class EditDistance(BaseMatcher):
 
     Arguments (reference _distance.py:18-23):
         n_jobs: accepted for compatibility; the GPU kernel ignores it
-        scorer: a rapidfuzz.fuzz scorer or its name; default "ratio" / rapidfuzz.fuzz.ratio.  Other callables
-                have no kernel (NotImplementedError).
+        scorer: a rapidfuzz.fuzz scorer or its name; default "ratio" / rapidfuzz.fuzz.ratio.  Or
+                jellyfish.jaro_similarity / jellyfish.jaro_winkler_similarity, or one of the names "jaro",
+                "jaro_similarity", "jaro_winkler", "jaro_winkler_similarity".  Other callables -- a functools.partial
+                of these included -- have no kernel (NotImplementedError).
         model_id: The name of the particular instance, used when comparing models
         normalize: Whether to min-max normalize the similarity scores (_distance.py:83-86)
 
@@ -48,6 +76,12 @@ class EditDistance(BaseMatcher):
     scorers (K7: WRatio, partial_ratio, the token_set family): from-strings of up to 256 characters and 32 distinct tokens
     in the LDS kernel, anything beyond (and to-strings beyond 32 distinct tokens) in K7's general kernel, which is slow.
     Any length and any alphabet is accepted.  There is no CPU fallback.
+
+    The Jaro scorers (K8): Similarity is the scorer's own float64 value on jellyfish's 0..1 scale, unscaled, as the
+    reference passes it through; jellyfish's default arguments (no long_tolerance), on code points.  From-strings of up to
+    64 characters against to-strings of up to 256 run in registers; longer strings take a general -- slow -- kernel.  PARITY UNPINNED:
+    jellyfish is not importable where this was built, the scorers are the restatement of its definition in
+    include/polyfuzz_hip.h (tests/test_jaro_cpu.py compares with jellyfish itself wherever it is installed).
     """
     def __init__(self,
                  n_jobs: int = 1,
@@ -59,7 +93,7 @@ class EditDistance(BaseMatcher):
         self._scorer_name = _device_scorer(scorer)
         if not self._scorer_name:
             raise NotImplementedError(
-                "polyfuzz_amd.EditDistance runs the rapidfuzz.fuzz scorers on the GPU; "
+                "polyfuzz_amd.EditDistance runs the rapidfuzz.fuzz scorers and jellyfish's two Jaro scorers on the GPU; "
                 f"scorer {scorer!r} has no HIP kernel and there is no CPU fallback")
         self.scorer = scorer
         self.normalize = normalize
@@ -113,7 +147,7 @@ class EditDistance(BaseMatcher):
         if len(names) - (1 if self_match else 0) <= 0 and len(from_list) > 0:
             raise ValueError("attempt to get argmax of an empty sequence")   # np.argmax([]) in the reference
         from ._rapidfuzz import best_choice_async, upload_for
-        name = self._scorer_name              # "ratio": K4; the other rapidfuzz.fuzz scorers: K4 on transformed strings, or K7
+        name = self._scorer_name              # "ratio": K4; the other rapidfuzz.fuzz scorers: K4 on transformed strings, or K7; Jaro: K8
         to_dev = None
         if not self_match:
             if reuse_to:
