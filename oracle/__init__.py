@@ -27,6 +27,10 @@ Pinning status (see DESIGN.md "Oracle"):
   published semantics: PARITY UNPINNED, anchored on the values rapidfuzz publishes
   (tests/test_fuzz_oracle_cpu.py).  fuzz_scorers.c is the same statement in plain C (held equal to the Python file
   bit for bit by the same test): the fast checker of K7 at full list sizes and bench.py's CPU arm for RapidFuzz.
+* jaro.c: jellyfish's jaro_similarity / jaro_winkler_similarity restated in plain C from the definition in
+  tests/jaro_oracle.py (held equal to that Python statement bit for bit by tests/test_jaro_cpu.py): the fast checker of K8
+  at the sizes a Python oracle cannot reach.  jellyfish is not installed where this was written: PARITY UNPINNED,
+  anchored on the published values and compared with jellyfish wherever it is importable.
 * reference_path.py: the reference's own executable TF-IDF path (sklearn
   vectoriser + dense cosine + full sorts + frame), the CPU arm "(i)" of
   bench.py -- pinned cell for cell on frames the reference package produced.
@@ -39,4 +43,4 @@ from .tfidf_oracle import (clean_string, create_ngrams, TfidfOracle)      # noqa
 from .tfidf_numpy import TfidfNumpyOracle      # noqa: F401
 from .dense import dense_cossim, dense_cossim_topn   # noqa: F401
 from .native import (cossim_topn, cossim_dense, indel_ratio, indel_argmax, fuzz_score, fuzz_extract_one, fuzz_matrix,  # noqa: F401
-                     build as build_native)
+                     jaro_matrix, jaro_argmax, build as build_native)

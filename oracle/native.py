@@ -17,7 +17,7 @@ _f64p = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
 
 def build(force=False):
     """Compile the C restatement with gcc (no GPU needed)."""
-    srcs = [os.path.join(_HERE, f) for f in ("cossim_topn.c", "indel.c", "fuzz_scorers.c")]
+    srcs = [os.path.join(_HERE, f) for f in ("cossim_topn.c", "indel.c", "fuzz_scorers.c", "jaro.c")]
     if (not force and os.path.exists(_SO)
             and all(os.path.getmtime(_SO) >= os.path.getmtime(s) for s in srcs)):
         return _SO
@@ -65,6 +65,12 @@ def _load():
     lib.oracle_fuzz_matrix.restype = ctypes.c_int
     lib.oracle_fuzz_matrix.argtypes = [_u32p, _i64p, ctypes.c_int64, _u32p, _i64p, ctypes.c_int64, ctypes.c_int32,
                                        ctypes.c_int64, ctypes.c_int64, _f64p]
+    lib.oracle_jaro_matrix.restype = ctypes.c_int
+    lib.oracle_jaro_matrix.argtypes = [_u32p, _i64p, ctypes.c_int64, _u32p, _i64p, ctypes.c_int64, ctypes.c_int32,
+                                       ctypes.c_int64, ctypes.c_int64, _f64p]
+    lib.oracle_jaro_argmax.restype = ctypes.c_int
+    lib.oracle_jaro_argmax.argtypes = [_u32p, _i64p, ctypes.c_int64, _u32p, _i64p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
+                                       ctypes.c_int64, ctypes.c_int64, _i32p, _f64p]
     _lib = lib
     return lib
 
@@ -196,3 +202,42 @@ def fuzz_matrix(from_list, to_list, scorer, rows=None):
     if rc != 0:
         raise ValueError(f"oracle_fuzz_matrix failed ({rc})")
     return out
+
+
+# the order of oracle/jaro.c's scorer argument (and of polyfuzz_amd._lib.JARO_SCORERS)
+JARO_SCORER_IDS = {"jaro": 0, "jaro_winkler": 1}
+
+
+def jaro_matrix(from_list, to_list, scorer, rows=None):
+    """float64 [rows, len(to_list)]: jellyfish's jaro_similarity / jaro_winkler_similarity of every pair (oracle/jaro.c,
+    == tests/jaro_oracle.py) for from-rows `rows` = (begin, end)."""
+    lib = _load()
+    acp, aoff = _codepoints(from_list)
+    bcp, boff = _codepoints(to_list)
+    r0, r1 = (0, len(from_list)) if rows is None else rows
+    out = np.empty((r1 - r0, len(to_list)), np.float64)
+    rc = lib.oracle_jaro_matrix(acp, aoff, len(from_list), bcp, boff, len(to_list), JARO_SCORER_IDS[scorer], r0, r1, out)
+    if rc != 0:
+        raise ValueError(f"oracle_jaro_matrix failed ({rc})")
+    return out
+
+
+def jaro_argmax(from_list, to_list, scorer, skip=None, rows=None):
+    """np.argmax / np.max of every from-row's scores (reference _distance.py:97-100) for from-rows `rows` = (begin, end), over the
+    choices `skip` leaves in (the codes of tests/jaro_oracle.py left_out, one per from-string): (index of the first maximum int32,
+    its score float64); a row without a choice gets -1 / 0.0."""
+    lib = _load()
+    acp, aoff = _codepoints(from_list)
+    bcp, boff = _codepoints(to_list)
+    r0, r1 = (0, len(from_list)) if rows is None else rows
+    out_idx = np.empty(r1 - r0, np.int32)
+    out_score = np.empty(r1 - r0, np.float64)
+    sk = None
+    if skip is not None:
+        sk = np.ascontiguousarray(skip, np.int32)
+        assert len(sk) == len(from_list)
+    rc = lib.oracle_jaro_argmax(acp, aoff, len(from_list), bcp, boff, len(to_list), JARO_SCORER_IDS[scorer],
+                                sk.ctypes.data_as(ctypes.c_void_p) if sk is not None else None, r0, r1, out_idx, out_score)
+    if rc != 0:
+        raise ValueError(f"oracle_jaro_argmax failed ({rc})")
+    return out_idx, out_score

@@ -183,6 +183,51 @@ def load_c3_fuzz_golden(scorer):
     return rows, idx, score
 
 
+# ---- K8 held to the C oracle (oracle/jaro.c); config 3's lists at full size (tests/golden/c3_jaro_oracle_*.npz, make_golden_c3_jaro.py) ----
+
+JARO_SCORERS = ("jaro", "jaro_winkler")
+
+
+def _row_shards(n_rows, workers):
+    cuts = np.linspace(0, n_rows, min(workers, max(n_rows, 1)) * 4 + 1).astype(np.int64)
+    return [(int(a), int(b)) for a, b in zip(cuts[:-1], cuts[1:]) if b > a]
+
+
+def jaro_oracle_matrix(oracle, from_list, to_list, scorer, workers=8):
+    """oracle.jaro_matrix with the from-rows cut over a thread pool (ctypes releases the GIL for the C call)"""
+    import concurrent.futures as cf
+    out = np.empty((len(from_list), len(to_list)), np.float64)
+    with cf.ThreadPoolExecutor(workers) as ex:
+        for (a, b), part in zip(_row_shards(len(from_list), workers),
+                                ex.map(lambda r: oracle.jaro_matrix(from_list, to_list, scorer, rows=r), _row_shards(len(from_list), workers))):
+            out[a:b] = part
+    return out
+
+
+def jaro_oracle_argmax(oracle, from_list, to_list, scorer, skip=None, workers=8):
+    """oracle.jaro_argmax with the from-rows cut over a thread pool: (int32 idx, float64 score) of every from-row"""
+    import concurrent.futures as cf
+    with cf.ThreadPoolExecutor(workers) as ex:
+        parts = list(ex.map(lambda r: oracle.jaro_argmax(from_list, to_list, scorer, skip, rows=r), _row_shards(len(from_list), workers)))
+    if not parts:
+        return np.empty(0, np.int32), np.empty(0, np.float64)
+    return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+
+
+def c3_jaro_golden_path(scorer):
+    import os
+    return os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", f"c3_jaro_oracle_{scorer}.npz")
+
+
+def load_c3_jaro_golden(scorer):
+    """-> (idx int32[20 000], score float64[20 000]) of the fixture; a missing file raises (a test fails on it, it does not skip)"""
+    g = np.load(c3_jaro_golden_path(scorer))
+    assert str(g["scorer"]) == scorer and str(g["source"]) == "oracle"
+    idx, score = g["idx"], g["score"]
+    assert idx.dtype == np.int32 and score.dtype == np.float64 and idx.shape == score.shape == (20_000,)
+    return idx, score
+
+
 # ---- which form of K3 served a call ---------------------------------------------------------------------------------------------
 
 @contextlib.contextmanager

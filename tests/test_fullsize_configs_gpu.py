@@ -1,4 +1,4 @@
-"""Configs 3 (RapidFuzz), 4 and 5 of BASELINE.json held to the CPU oracle AT THEIR REAL SIZE inside the suite -- until now three of the
+"""Configs 3 (RapidFuzz; and the same lists under K8's Jaro / Jaro-Winkler), 4 and 5 of BASELINE.json held to the CPU oracle AT THEIR REAL SIZE inside the suite -- until now three of the
 five benchmark configurations met the oracle at full size only in `bench.py --full`:
 
 * K7: the whole 20 000 x 20 000 IMDB-title configuration under all ten rapidfuzz.fuzz scorers, bit for bit against
@@ -106,6 +106,48 @@ def test_config_3_matcher_frames_equal_the_oracle_fixture(ctx, c3):
     assert de["From"].tolist() == fl
     assert de["To"].tolist() == [tl[j] for j in s_idx.tolist()]
     np.testing.assert_array_equal(de["Similarity"].to_numpy(), s_score)
+
+
+# ---- 1b. config 3's lists under Jaro / Jaro-Winkler (K8 at the size its timing is quoted at) ---------------------------------------
+
+@pytest.mark.parametrize("scorer", helpers.JARO_SCORERS)
+def test_config_3_lists_jaro_equals_the_oracle_fixture(ctx, c3, scorer):
+    """K8 on the RESIDENT 20 000 x 20 000 titles (what tools/bench_jaro.py times): first arg-max and float64 score of all 20 000 rows ==
+    tests/golden/c3_jaro_oracle_*.npz (oracle/jaro.c's answers; tests/test_jaro_golden_cpu.py keeps the files equal to the committed
+    oracle), through the host entry and jaro_argmax_dev.  The share of the 4e8 pairs whose float64 score the arg-max computed is
+    printed.  Measured on an MI355X: 43 382 896 (Jaro) / 43 383 985 (Jaro-Winkler) of 4e8 pairs, 10.85 %."""
+    from polyfuzz_amd import _lib
+    fl, tl = c3
+    e_idx, e_score = helpers.load_c3_jaro_golden(scorer)
+    rows = np.arange(20_000)
+    f_dev, t_dev = _lib.DeviceStrings.upload(ctx, fl), _lib.DeviceStrings.upload(ctx, tl)
+    ctx.prof_enable(True)
+    ctx.prof_reset()
+    try:
+        idx, score = _lib.jaro_argmax(ctx, f_dev, t_dev, scorer)
+        scored = ctx.prof_get("k8_pairs_scored")[1]
+    finally:
+        ctx.prof_enable(False)
+    print(f"K8 {scorer}, 20 000 x 20 000 titles: {scored} of {len(fl) * len(tl)} pairs scored, share {scored / (len(fl) * len(tl)):.4f}")
+    assert idx.shape == score.shape == (20_000,) and idx.dtype == np.int32 and score.dtype == np.float64
+    _assert_rows_equal(f"{scorer}, resident lists", fl, tl, rows, idx, score, e_idx, e_score)
+    assert 0 < scored < len(fl) * len(tl)
+    out = _lib.DeviceTopN.alloc(ctx, 20_000, 2)
+    _lib.jaro_argmax_dev(ctx, f_dev, t_dev, scorer, out)
+    d_idx, d_score = _lib.best_from_topn(*out.download())
+    _assert_rows_equal(f"{scorer}, resident lists, device entry", fl, tl, rows, d_idx[:20_000], d_score[:20_000], e_idx, e_score)
+
+
+def test_config_3_jaro_winkler_matcher_frame_equals_the_oracle_fixture(ctx, c3):
+    """`EditDistance(scorer="jaro_winkler", normalize=False).match(from, to)` at this size: From, To and Similarity of all 20 000 rows
+    from the fixture"""
+    from polyfuzz_amd.models import EditDistance
+    fl, tl = c3
+    e_idx, e_score = helpers.load_c3_jaro_golden("jaro_winkler")
+    df = EditDistance(scorer="jaro_winkler", normalize=False).match(fl, tl)
+    assert len(df) == 20_000 and df["From"].tolist() == fl
+    assert df["To"].tolist() == [tl[j] for j in e_idx.tolist()]
+    np.testing.assert_array_equal(df["Similarity"].to_numpy(), e_score)
 
 
 # ---- 2. config 4's shard on the lock-step kernel's natural dispatch ------------------------------------------------------------------
