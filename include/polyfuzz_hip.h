@@ -81,7 +81,9 @@ int pfz_prof_reset(pfz_ctx *ctx);
 /* total ms and launch count of kernel `name` since the last reset (blocks).  Every form of K3 is timed as
  * `k3_cossim_topn`; `k3_lockstep` (0 ms, a count only) says how many of those launches the lock-step form served.
  * K8: `k8_jaro` (every launch of a call), `k8_jaro_general` (its general-kernel launches), `k8_pairs_scored` (0 ms; the
- * count is the number of pairs whose float64 score was computed). */
+ * count is the number of pairs whose float64 score was computed).
+ * K9: `k9_lev` (every launch of a call), `k9_lev_general` (its general-kernel launches), `k9_pairs_walked` (0 ms; the count is
+ * the number of pairs whose recurrence was walked -- the others fell to the length bound). */
 int pfz_prof_get(pfz_ctx *ctx, const char *name, double *total_ms, int64_t *launches);
 
 /* ---- CSR matrices --------------------------------------------------------
@@ -339,6 +341,37 @@ int pfz_jaro_argmax_dev(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz
  * (test / small-input entry point).  Blocks. */
 int pfz_jaro_matrix_host(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings, int32_t scorer,
                          int64_t from_begin, int64_t from_end, double *out_matrix);
+
+/* ---- K9: all-pairs Levenshtein / OSA similarity + row arg-max -----------------
+ * Replaces the hot loop of EditDistance._calculate_edit_distance (reference
+ * polyfuzz/models/_distance.py:89-102) with the `scorer` argument (_distance.py:32) set to rapidfuzz's
+ * Levenshtein.normalized_similarity (scorer = 0) or OSA.normalized_similarity (scorer = 1), default arguments, on
+ * code points: for every from-string of rows [from_begin, from_end) the FIRST to-string with the maximal score
+ * (np.argmax, _distance.py:99) and that score (np.max), float64 on the 0..1 scale, unscaled:
+ *   d = the fewest unit-cost insertions, deletions and substitutions that turn a into b (Levenshtein); OSA (optimal
+ *   string alignment) also counts the transposition of two adjacent characters as one edit, no substring edited
+ *   twice: osa("CA","ABC") = 3 (unrestricted Damerau: 2), osa("ab","ba") = 1 (Levenshtein: 2);
+ *   M = max(|a|, |b|);  sim = 1.0 - (double)d / (double)M, 1.0 when M = 0: one division, one subtraction, not fused.
+ * skip_idx, the row range and the -1 / 0 result of a row without a candidate: as pfz_indel_argmax.
+ * Any length and any alphabet: from-strings of up to 64 characters run in registers against to-strings of any
+ * length, longer ones (and alphabets whose match table exceeds 60 KiB) in a general -- slow -- kernel.  The arg-max
+ * walks a from-string's to-strings from the nearest length outwards and stops where d >= ||a| - |b|| puts every
+ * further one strictly below the best so far.  The to-side preparation is pfz_indel_*'s, cached on the to-list's
+ * handle.  PARITY UNPINNED: the scorers restate rapidfuzz's definition; rapidfuzz itself is compared wherever it
+ * is installed (tests/test_levenshtein_cpu.py).
+ * scorer outside {0, 1}: PFZ_ERR_INVALID.  out_idx / out_score: host buffers of from_end - from_begin
+ * entries.  Blocks. */
+int pfz_lev_argmax(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings, int32_t scorer,
+                   const int32_t *skip_idx, int64_t from_begin, int64_t from_end, int32_t *out_idx, double *out_score);
+/* pfz_lev_argmax with the result left on the device in the layout of pfz_indel_argmax_dev (_distance.py:89-102): `out`
+ * must have 2 columns and >= from_end - from_begin rows; row r gets idx[r][0] = the first arg-max (idx[r][1] = -1)
+ * and the float64 score's bits in its two value lanes.  Enqueues. */
+int pfz_lev_argmax_dev(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings, int32_t scorer,
+                       const int32_t *skip_idx, int64_t from_begin, int64_t from_end, pfz_topn *out);
+/* every DISTANCE d of rows [from_begin, from_end) x all to-strings as int32, row-major host buffer (test / small-input
+ * entry point; every pair is walked).  The similarity follows in one IEEE division and subtraction.  Blocks. */
+int pfz_lev_matrix_host(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings, int32_t scorer,
+                        int64_t from_begin, int64_t from_end, int32_t *out_matrix);
 
 /* ---- K5: dense cosine top-n -----------------------------------------------
  * Replaces cosine_similarity on dense embedding matrices

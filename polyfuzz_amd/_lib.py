@@ -94,6 +94,9 @@ SIGNATURES = {
     "pfz_jaro_argmax": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "pfz_jaro_argmax_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp]),
     "pfz_jaro_matrix_host": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_vp]),
+    "pfz_lev_argmax": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
+    "pfz_lev_argmax_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp]),
+    "pfz_lev_matrix_host": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_vp]),
     "pfz_fuzz_extract_one": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "pfz_fuzz_extract_one_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "pfz_fuzz_plan_info": (ctypes.c_int, [c_vp, c_vp, P(c_i64), P(c_i64), P(c_i64), P(c_i64)]),
@@ -760,6 +763,38 @@ def jaro_matrix(ctx, from_dev, to_dev, scorer, begin=0, end=None):
     end = from_dev.n if end is None else end
     out = np.empty((end - begin, to_dev.n), np.float64)
     check(ctx.lib.pfz_jaro_matrix_host(ctx.h, from_dev.h, to_dev.h, JARO_SCORERS[scorer], int(begin), int(end), _ptr(out)))
+    return out
+
+
+# K9: rapidfuzz's Levenshtein.normalized_similarity / OSA.normalized_similarity (default arguments), float64 on the 0..1 scale.
+# PARITY UNPINNED: rapidfuzz is not importable where this was built; the definition is restated in include/polyfuzz_hip.h.
+LEV_SCORERS = {"levenshtein": 0, "osa": 1}
+
+
+def lev_argmax(ctx, from_dev, to_dev, scorer, skip_idx=None, begin=0, end=None):
+    """K9: (first arg-max index int32[n], similarity float64[n]) of from-rows [begin, end)."""
+    end = from_dev.n if end is None else end
+    n = end - begin
+    idx = np.empty(n, np.int32)
+    score = np.empty(n, np.float64)
+    skip_idx = _skip_array(skip_idx, from_dev.n)
+    check(ctx.lib.pfz_lev_argmax(ctx.h, from_dev.h, to_dev.h, LEV_SCORERS[scorer], _ptr(skip_idx), int(begin), int(end),
+                                 _ptr(idx), _ptr(score)))
+    return idx, score
+
+
+def lev_argmax_dev(ctx, from_dev, to_dev, scorer, out, skip_idx=None, begin=0, end=None):
+    """K9 with the (first arg-max, float64 similarity) rows left in the 2-column DeviceTopN `out` (see best_from_topn)."""
+    end = from_dev.n if end is None else end
+    skip_idx = _skip_array(skip_idx, from_dev.n)
+    check(ctx.lib.pfz_lev_argmax_dev(ctx.h, from_dev.h, to_dev.h, LEV_SCORERS[scorer], _ptr(skip_idx), int(begin), int(end), out.h))
+
+
+def lev_matrix(ctx, from_dev, to_dev, scorer, begin=0, end=None):
+    """K9: every DISTANCE of from-rows [begin, end) x all to-strings, int32 [end - begin, n_to] (the test entry)."""
+    end = from_dev.n if end is None else end
+    out = np.empty((end - begin, to_dev.n), np.int32)
+    check(ctx.lib.pfz_lev_matrix_host(ctx.h, from_dev.h, to_dev.h, LEV_SCORERS[scorer], int(begin), int(end), _ptr(out)))
     return out
 
 

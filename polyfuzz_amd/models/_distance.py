@@ -9,7 +9,8 @@ rapidfuzz.fuzz scorer (or its name): ratio / QRatio / token_sort_ratio run throu
 WRatio / partial_ratio / token_set_ratio / token_ratio / partial_token_* through K7;
 or jellyfish.jaro_similarity / jaro_winkler_similarity (the scorer of the reference's
 custom-model tutorial, docs/tutorial/models/models.md:46-58), which run through K8;
-any other callable raises -- there is no CPU path to fall back to.
+or rapidfuzz's Levenshtein.normalized_similarity / OSA.normalized_similarity, which run
+through K9; any other callable raises -- there is no CPU path to fall back to.
 """
 import time
 from typing import Callable, List, Union
@@ -43,14 +44,44 @@ def _jaro_scorer(scorer) -> str:
     return next((_JARO_NAMES[n] for n in _JELLYFISH_FUNCTIONS if getattr(jellyfish, n, None) is scorer), "")
 
 
+_LEV_NAMES = {"levenshtein": "levenshtein", "levenshtein_normalized_similarity": "levenshtein", "osa": "osa",
+              "osa_normalized_similarity": "osa"}
+_LEV_MODULES = {"Levenshtein": "levenshtein", "Levenshtein_py": "levenshtein", "OSA": "osa", "OSA_py": "osa"}
+
+
+def _lev_scorer(scorer) -> str:
+    """K9's name ("levenshtein" / "osa") of the rapidfuzz function `scorer` stands for, or '': one of the four names; the very
+    object rapidfuzz.distance.Levenshtein.normalized_similarity / rapidfuzz.distance.OSA.normalized_similarity (by identity:
+    the check that counts); or a callable named `normalized_similarity` whose module is rapidfuzz.distance.Levenshtein,
+    .Levenshtein_py, .OSA or .OSA_py -- what names rapidfuzz's compiled functions actually carry could not be looked up where
+    this was written, rapidfuzz is not installed there.  normalized_distance, distance and similarity (an arg-max over a
+    distance is a caller's mistake; similarity is not on the 0..1 scale), a functools.partial (weights, score_cutoff and
+    processor have no kernel) and somebody else's function of the same name are none of these."""
+    if isinstance(scorer, str):
+        return _LEV_NAMES.get(scorer, "")
+    try:
+        from rapidfuzz.distance import OSA, Levenshtein
+        for mod, name in ((Levenshtein, "levenshtein"), (OSA, "osa")):
+            if getattr(mod, "normalized_similarity", None) is scorer:
+                return name
+    except ImportError:
+        pass
+    module = getattr(scorer, "__module__", "") or ""
+    if getattr(scorer, "__name__", "") == "normalized_similarity" and module.startswith("rapidfuzz.distance."):
+        return _LEV_MODULES.get(module.split(".")[-1], "")
+    return ""
+
+
 def _device_scorer(scorer) -> str:
-    """Name of the rapidfuzz.fuzz scorer (or K8's name of the jellyfish scorer) `scorer` stands for, or '' when it has no
-    kernel."""
+    """Name of the rapidfuzz.fuzz scorer (or K8's name of the jellyfish scorer, or K9's of the rapidfuzz.distance scorer)
+    `scorer` stands for, or '' when it has no kernel."""
     from ._rapidfuzz import _DEVICE_SCORERS
     if scorer is None:
         return "ratio"                                     # the reference's default (_distance.py:32)
     if _jaro_scorer(scorer):
         return _jaro_scorer(scorer)
+    if _lev_scorer(scorer):
+        return _lev_scorer(scorer)
     name = scorer if isinstance(scorer, str) else getattr(scorer, "__name__", "")
     if not isinstance(scorer, str) and "rapidfuzz" not in (getattr(scorer, "__module__", "") or ""):
         return ""
@@ -65,8 +96,10 @@ class EditDistance(BaseMatcher):
         n_jobs: accepted for compatibility; the GPU kernel ignores it
         scorer: a rapidfuzz.fuzz scorer or its name; default "ratio" / rapidfuzz.fuzz.ratio.  Or
                 jellyfish.jaro_similarity / jellyfish.jaro_winkler_similarity, or one of the names "jaro",
-                "jaro_similarity", "jaro_winkler", "jaro_winkler_similarity".  Other callables -- a functools.partial
-                of these included -- have no kernel (NotImplementedError).
+                "jaro_similarity", "jaro_winkler", "jaro_winkler_similarity".  Or
+                rapidfuzz.distance.Levenshtein.normalized_similarity / rapidfuzz.distance.OSA.normalized_similarity, or
+                one of the names "levenshtein", "levenshtein_normalized_similarity", "osa", "osa_normalized_similarity".
+                Other callables -- a functools.partial of these included -- have no kernel (NotImplementedError).
         model_id: The name of the particular instance, used when comparing models
         normalize: Whether to min-max normalize the similarity scores (_distance.py:83-86)
 
@@ -82,6 +115,16 @@ class EditDistance(BaseMatcher):
     64 characters against to-strings of up to 256 run in registers; longer strings take a general -- slow -- kernel.  PARITY UNPINNED:
     jellyfish is not importable where this was built, the scorers are the restatement of its definition in
     include/polyfuzz_hip.h (tests/test_jaro_cpu.py compares with jellyfish itself wherever it is installed).
+
+    Levenshtein and OSA (K9): Similarity is rapidfuzz's normalized_similarity, 1 - d / max(|from|, |to|) as float64 on the 0..1
+    scale (1.0 for two empty strings), unscaled, as the reference passes a scorer's value through; d is the unit-cost edit
+    distance, for "osa" with the transposition of two adjacent characters as one edit (optimal string alignment; unrestricted
+    Damerau-Levenshtein, Hamming, custom weights and the distance callables have no kernel).  From-strings of up to 64
+    characters run in registers against to-strings of any length, longer ones in a general -- slow -- kernel; a from-string's
+    to-strings are walked from the nearest length outwards and left alone where the difference in length alone puts them below
+    the best so far.  PARITY UNPINNED beyond the oracle; live pin armed: rapidfuzz is not importable where this was built,
+    the scorers are the restatement of its definition in include/polyfuzz_hip.h (tests/test_levenshtein_cpu.py compares with
+    rapidfuzz itself wherever it is installed).
     """
     def __init__(self,
                  n_jobs: int = 1,
@@ -93,7 +136,8 @@ class EditDistance(BaseMatcher):
         self._scorer_name = _device_scorer(scorer)
         if not self._scorer_name:
             raise NotImplementedError(
-                "polyfuzz_amd.EditDistance runs the rapidfuzz.fuzz scorers and jellyfish's two Jaro scorers on the GPU; "
+                "polyfuzz_amd.EditDistance runs the rapidfuzz.fuzz scorers, jellyfish's two Jaro scorers and rapidfuzz's Levenshtein / OSA "
+                "normalized_similarity on the GPU; "
                 f"scorer {scorer!r} has no HIP kernel and there is no CPU fallback")
         self.scorer = scorer
         self.normalize = normalize
@@ -147,7 +191,7 @@ class EditDistance(BaseMatcher):
         if len(names) - (1 if self_match else 0) <= 0 and len(from_list) > 0:
             raise ValueError("attempt to get argmax of an empty sequence")   # np.argmax([]) in the reference
         from ._rapidfuzz import best_choice_async, upload_for
-        name = self._scorer_name              # "ratio": K4; the other rapidfuzz.fuzz scorers: K4 on transformed strings, or K7; Jaro: K8
+        name = self._scorer_name              # "ratio": K4; the other rapidfuzz.fuzz scorers: K4 on transformed strings, or K7; Jaro: K8; Levenshtein / OSA: K9
         to_dev = None
         if not self_match:
             if reuse_to:

@@ -85,7 +85,7 @@ class _PendingBest:
 
 
 def best_choice_async(ctx, name, from_list, names, skip, self_match, to_dev=None):
-    """Enqueue the best-choice pass of every from-string under the rapidfuzz.fuzz (or K8 Jaro) scorer `name` and return at once (the
+    """Enqueue the best-choice pass of every from-string under the rapidfuzz.fuzz (or K8 Jaro, K9 Levenshtein / OSA) scorer `name` and return at once (the
     caller builds its From column while the device works); `names` are the choices (the from-list itself in a
     self-match, where skip[i] is the choice left out for from-string i -- still the from-string's own first occurrence
     in the ORIGINAL list).  to_dev: the choices already resident (upload_for), e.g. from the previous call of a fitted
@@ -99,6 +99,8 @@ def best_choice_async(ctx, name, from_list, names, skip, self_match, to_dev=None
         _lib.fuzz_extract_one_dev(ctx, f_dev, t_dev, name, out, skip)
     elif name in _lib.JARO_SCORERS:           # (EditDistance only: scores on jellyfish's 0..1 scale, not rapidfuzz's 0..100)
         _lib.jaro_argmax_dev(ctx, f_dev, t_dev, name, out, skip)
+    elif name in _lib.LEV_SCORERS:            # (EditDistance only, K9: similarities on the 0..1 scale)
+        _lib.lev_argmax_dev(ctx, f_dev, t_dev, name, out, skip)
     else:
         _lib.indel_argmax_dev(ctx, f_dev, t_dev, out, skip)
         if name == "QRatio":
