@@ -268,6 +268,16 @@ int pfz_indel_argmax_dev(pfz_ctx *ctx, const pfz_strings *from_strings, const pf
  * row-major host buffer (test / small-input entry point).  Blocks. */
 int pfz_indel_matrix_host(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings,
                           int64_t from_begin, int64_t from_end, double *out_matrix);
+/* The ntop best choices of every from-string of rows [from_begin, from_end) under rapidfuzz.fuzz.ratio: extends
+ * the np.argmax / np.max of the reference's loop (polyfuzz/models/_distance.py:89-102) to what
+ * np.argsort(-scores, kind="stable")[:ntop] gives on the scores that loop computes -- float64 ratio descending, equal
+ * ratios by ascending to-index -- so column 0 is pfz_indel_argmax's result.  out_idx / out_score: host buffers of
+ * (from_end - from_begin) * ntop entries, row-major; the slots beyond the choices a row has (skip_idx as in
+ * pfz_indel_argmax; ntop may exceed the to-list) carry -1 / 0.0.  Exact: every pair is scored, every wave keeps one
+ * sorted list of ntop keys (csrc/topn_wave.h).  ntop < 1: PFZ_ERR_INVALID; ntop > 64: PFZ_ERR_UNSUPPORTED.  Blocks. */
+int pfz_indel_topn(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings,
+                   const int32_t *skip_idx, int64_t from_begin, int64_t from_end, int32_t ntop,
+                   int32_t *out_idx, double *out_score);
 /* K4's preparation of a to-list -- alphabet (distinct code points of the to-list), to-strings sorted by
  * length into groups of 64, symbols packed per group on the device -- depends on the to-list alone: it is
  * built on the first pfz_indel_* call that uses the handle as the to-side and cached on it, so matching
@@ -368,6 +378,17 @@ int pfz_lev_argmax(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_stri
  * and the float64 score's bits in its two value lanes.  Enqueues. */
 int pfz_lev_argmax_dev(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings, int32_t scorer,
                        const int32_t *skip_idx, int64_t from_begin, int64_t from_end, pfz_topn *out);
+/* The ntop best choices of every from-string of rows [from_begin, from_end) under the Levenshtein (scorer = 0) or OSA
+ * (scorer = 1) similarity: extends the np.argmax / np.max of the reference's loop (polyfuzz/models/_distance.py:89-102)
+ * to what np.argsort(-scores, kind="stable")[:ntop] gives on the scores that loop computes -- float64 score descending,
+ * equal scores by ascending to-index -- so column 0 is pfz_lev_argmax's result.  out_idx / out_score: host buffers of
+ * (from_end - from_begin) * ntop entries, row-major; the slots beyond the choices a row has (skip_idx as in
+ * pfz_indel_argmax; ntop may exceed the to-list) carry -1 / 0.0.  Exact: a to-string is left unwalked only where
+ * d >= ||a| - |b|| puts it strictly below a score that ntop walked choices of the row have reached (csrc/topn_wave.h).
+ * ntop < 1: PFZ_ERR_INVALID; ntop > 64: PFZ_ERR_UNSUPPORTED.  Blocks. */
+int pfz_lev_topn(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings, int32_t scorer,
+                 const int32_t *skip_idx, int64_t from_begin, int64_t from_end, int32_t ntop,
+                 int32_t *out_idx, double *out_score);
 /* every DISTANCE d of rows [from_begin, from_end) x all to-strings as int32, row-major host buffer (test / small-input
  * entry point; every pair is walked).  The similarity follows in one IEEE division and subtraction.  Blocks. */
 int pfz_lev_matrix_host(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings, int32_t scorer,

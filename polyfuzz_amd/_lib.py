@@ -91,11 +91,13 @@ SIGNATURES = {
     "pfz_indel_matrix_host": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp]),
     "pfz_indel_plan_info": (ctypes.c_int, [c_vp, c_vp, P(c_i64), P(c_i64), P(c_i64)]),
     "pfz_indel_argmax_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp]),
+    "pfz_indel_topn": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp]),
     "pfz_jaro_argmax": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "pfz_jaro_argmax_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp]),
     "pfz_jaro_matrix_host": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_vp]),
     "pfz_lev_argmax": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "pfz_lev_argmax_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp]),
+    "pfz_lev_topn": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp]),
     "pfz_lev_matrix_host": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_vp]),
     "pfz_fuzz_extract_one": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "pfz_fuzz_extract_one_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
@@ -651,6 +653,18 @@ def indel_argmax(ctx, from_dev, to_dev, skip_idx=None, begin=0, end=None):
     return idx, score
 
 
+def indel_topn(ctx, from_dev, to_dev, ntop, skip_idx=None, begin=0, end=None):
+    """K4: the ntop best choices of from-rows [begin, end) -- (index int32[n, ntop], ratio float64[n, ntop]) in the order
+    (ratio descending, to-index ascending); -1 / 0.0 beyond the choices a row has.  ntop <= 64 (PfzUnsupported beyond)."""
+    end = from_dev.n if end is None else end
+    n = end - begin
+    idx = np.empty((n, max(int(ntop), 0)), np.int32)           # (ntop < 1 is the library's to refuse)
+    score = np.empty((n, max(int(ntop), 0)), np.float64)
+    skip_idx = _skip_array(skip_idx, from_dev.n)
+    check(ctx.lib.pfz_indel_topn(ctx.h, from_dev.h, to_dev.h, _ptr(skip_idx), int(begin), int(end), int(ntop), _ptr(idx), _ptr(score)))
+    return idx, score
+
+
 def indel_plan_info(ctx, to_dev):
     """Build (once) and describe K4's cached to-side plan of a DeviceStrings handle."""
     v = [c_i64() for _ in range(3)]
@@ -788,6 +802,19 @@ def lev_argmax_dev(ctx, from_dev, to_dev, scorer, out, skip_idx=None, begin=0, e
     end = from_dev.n if end is None else end
     skip_idx = _skip_array(skip_idx, from_dev.n)
     check(ctx.lib.pfz_lev_argmax_dev(ctx.h, from_dev.h, to_dev.h, LEV_SCORERS[scorer], _ptr(skip_idx), int(begin), int(end), out.h))
+
+
+def lev_topn(ctx, from_dev, to_dev, scorer, ntop, skip_idx=None, begin=0, end=None):
+    """K9: the ntop best choices of from-rows [begin, end) -- (index int32[n, ntop], similarity float64[n, ntop]) in the order
+    (similarity descending, to-index ascending); -1 / 0.0 beyond the choices a row has.  ntop <= 64 (PfzUnsupported beyond)."""
+    end = from_dev.n if end is None else end
+    n = end - begin
+    idx = np.empty((n, max(int(ntop), 0)), np.int32)           # (ntop < 1 is the library's to refuse)
+    score = np.empty((n, max(int(ntop), 0)), np.float64)
+    skip_idx = _skip_array(skip_idx, from_dev.n)
+    check(ctx.lib.pfz_lev_topn(ctx.h, from_dev.h, to_dev.h, LEV_SCORERS[scorer], _ptr(skip_idx), int(begin), int(end), int(ntop),
+                               _ptr(idx), _ptr(score)))
+    return idx, score
 
 
 def lev_matrix(ctx, from_dev, to_dev, scorer, begin=0, end=None):

@@ -29,9 +29,14 @@
 // The to-side "plan" -- alphabet, length-sorted groups, packed symbols -- depends on
 // the to-list alone; it is built once per to-list (packing on the device) and cached
 // on its pfz_strings handle, so a repeated to-list costs no preparation at all.
+// The top-n form (pfz_indel_topn, topn_wave.h) is built on the one-from-string-per-workgroup kernel and on the general kernel:
+// every wave keeps one sorted list of its ntop best pairs, keyed by the float64 ratio itself (struct Best below: it orders
+// the pairs exactly as the rationals do), the waves leave their lists side by side and topn_merge picks the row's.  The
+// quad / octo kernels keep their bests in registers per from-string and have no top-n form.  Every pair is scored.
 // Roofline: integer VALU + LDS lookups; HBM traffic is the to-strings once per
 // from-string out of L2 (0.3 MB) -- not HBM-bound.
 #include "k4_plan.h"
+#include "topn_wave.h"
 
 #include <algorithm>
 #include <limits.h>
@@ -99,6 +104,8 @@ struct IndelArgs {
     double *matrix;            // optional [(from_end-from_begin) * n_to]
     int32_t parts;             // the to-groups of a from-string (or quad) are split over `parts` workgroups ...
     int32_t *partial;          // ... which leave (lcs, maximum, idx) per (class row, part) here for k4_merge_parts
+    int32_t ntop;              // the top-n kernels: wave w of part p of row r (its place in `rows`) leaves its list in
+    TopnKey *lists;            // lists[((r * parts + p) * 4 + w) * ntop]: one buffer per launch
 };
 
 // The running best of a from-string is kept as the exact rational lcs / maximum (maximum = |a| + |b|): the ratio
@@ -142,8 +149,9 @@ __device__ inline double ratio_of(int lcs, int64_t maximum)
     return (1.0 - norm_dist) * 100.0;
 }
 
-template <typename WORD, int W, int IDB>
-__global__ __launch_bounds__(256) void k4_indel_kernel(IndelArgs A)
+// TOPN: a list of A.ntop per wave in place of a best per lane
+template <typename WORD, int W, int IDB, bool TOPN>
+__device__ __forceinline__ void k4_indel_body(const IndelArgs &A)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     WORD *pm = (WORD *)smem_raw;
@@ -173,6 +181,7 @@ __global__ __launch_bounds__(256) void k4_indel_kernel(IndelArgs A)
 
         const int skip = A.skip_idx ? A.skip_idx[row] : -1;
         Best best = {0, 1, INT_MAX};
+        TopnList list = topn_empty();
         for (int g = wave + 4 * part; g < A.n_groups; g += 4 * parts) {
             WORD V[W];
 #pragma unroll
@@ -193,7 +202,11 @@ __global__ __launch_bounds__(256) void k4_indel_kernel(IndelArgs A)
             for (int w = 0; w < W; ++w) lcs += popc_word((WORD)~V[w]);
             const int slot = g * 64 + lane;
             const int orig = A.b_orig[slot];
-            if (orig >= 0) {
+            if constexpr (TOPN) {
+                const int lb = A.b_len[slot];
+                topn_insert(list, A.ntop, orig >= 0 && !choice_left_out(orig, skip, A.skip_up_to), m + lb == 0 ? 100.0 : ratio_of(lcs, (int64_t)m + lb), orig);
+            }
+            else if (orig >= 0) {
                 const int lb = A.b_len[slot];
                 if (A.matrix) A.matrix[((int64_t)row - A.from_begin) * A.n_to + orig] = choice_left_out(orig, skip, A.skip_up_to) ? -1.0 : ratio_of(lcs, (int64_t)m + lb);
                 if (!choice_left_out(orig, skip, A.skip_up_to)) {
@@ -202,15 +215,18 @@ __global__ __launch_bounds__(256) void k4_indel_kernel(IndelArgs A)
                 }
             }
         }
+        if constexpr (TOPN) topn_store(list, A.ntop, A.lists + (((int64_t)r * parts + part) * 4 + wave) * A.ntop);
         // first maximum: (score desc, original index asc)
-        wave_best(best);
-        if (lane == 0) {
-            red[wave][0] = best.lcs;
-            red[wave][1] = best.mx;
-            red[wave][2] = best.idx;
+        if constexpr (!TOPN) {
+            wave_best(best);
+            if (lane == 0) {
+                red[wave][0] = best.lcs;
+                red[wave][1] = best.mx;
+                red[wave][2] = best.idx;
+            }
         }
         __syncthreads();
-        if (tid == 0) {
+        if (!TOPN && tid == 0) {
             for (int w = 1; w < 4; ++w)
                 if (red[w][2] != INT_MAX) take(best, red[w][0], red[w][1], red[w][2]);
             if (parts > 1) {
@@ -234,6 +250,18 @@ __global__ __launch_bounds__(256) void k4_indel_kernel(IndelArgs A)
         }
         __syncthreads();
     }
+}
+
+template <typename WORD, int W, int IDB>
+__global__ __launch_bounds__(256) void k4_indel_kernel(IndelArgs A)
+{
+    k4_indel_body<WORD, W, IDB, false>(A);
+}
+
+template <typename WORD, int W, int IDB>
+__global__ __launch_bounds__(256) void k4_indel_topn_kernel(IndelArgs A)
+{
+    k4_indel_body<WORD, W, IDB, true>(A);
 }
 
 // From-strings of <= 32 characters (95 % of the IMDB titles, 80 % of the company names) go FOUR per workgroup pass:
@@ -436,9 +464,9 @@ __global__ __launch_bounds__(256) void k4_merge_parts(IndelArgs A)
 // LDS (thousands of distinct CJK characters with long strings).  Same recurrence, any number W of 64-bit words, with
 // the match table of the workgroup's from-string and every lane's V in global scratch (L2): slow -- every word-step
 // is two loads and a store -- but the reference accepts such inputs, so the engine does too.  One to-string per lane.
-template <int IDB>
-__global__ __launch_bounds__(256) void k4_indel_general_kernel(IndelArgs A, int32_t W, uint64_t *__restrict__ pm_all,
-                                                                uint64_t *__restrict__ v_all)
+template <int IDB, bool TOPN>
+__device__ __forceinline__ void k4_indel_general_body(const IndelArgs &A, int32_t W, uint64_t *__restrict__ pm_all,
+                                                      uint64_t *__restrict__ v_all)
 {
     __shared__ int red[4][3];
     constexpr int PER = 32 / IDB;
@@ -461,6 +489,7 @@ __global__ __launch_bounds__(256) void k4_indel_general_kernel(IndelArgs A, int3
         __syncthreads();
         const int skip = A.skip_idx ? A.skip_idx[row] : -1;
         Best best = {0, 1, INT_MAX};
+        TopnList list = topn_empty();
         for (int g = wave; g < A.n_groups; g += 4) {
             for (int w = 0; w < W; ++w) V[(int64_t)w * 256] = ~0ull;
             const uint32_t *gp = A.b_packed + A.g_off[g] + lane;
@@ -488,7 +517,11 @@ __global__ __launch_bounds__(256) void k4_indel_general_kernel(IndelArgs A, int3
             for (int w = 0; w < W; ++w) lcs += __popcll(~V[(int64_t)w * 256]);
             const int slot = g * 64 + lane;
             const int orig = A.b_orig[slot];
-            if (orig >= 0) {
+            if constexpr (TOPN) {
+                const int lb = A.b_len[slot];
+                topn_insert(list, A.ntop, orig >= 0 && !choice_left_out(orig, skip, A.skip_up_to), m + lb == 0 ? 100.0 : ratio_of(lcs, (int64_t)m + lb), orig);
+            }
+            else if (orig >= 0) {
                 const int lb = A.b_len[slot];
                 if (A.matrix) A.matrix[((int64_t)row - A.from_begin) * A.n_to + orig] = choice_left_out(orig, skip, A.skip_up_to) ? -1.0 : ratio_of(lcs, (int64_t)m + lb);
                 if (!choice_left_out(orig, skip, A.skip_up_to)) {
@@ -497,14 +530,17 @@ __global__ __launch_bounds__(256) void k4_indel_general_kernel(IndelArgs A, int3
                 }
             }
         }
-        wave_best(best);
-        if (lane == 0) {
-            red[wave][0] = best.lcs;
-            red[wave][1] = best.mx;
-            red[wave][2] = best.idx;
+        if constexpr (TOPN) topn_store(list, A.ntop, A.lists + ((int64_t)r * 4 + wave) * A.ntop);
+        if constexpr (!TOPN) {
+            wave_best(best);
+            if (lane == 0) {
+                red[wave][0] = best.lcs;
+                red[wave][1] = best.mx;
+                red[wave][2] = best.idx;
+            }
         }
         __syncthreads();
-        if (tid == 0) {
+        if (!TOPN && tid == 0) {
             for (int w = 1; w < 4; ++w)
                 if (red[w][2] != INT_MAX) take(best, red[w][0], red[w][1], red[w][2]);
             const int64_t o = (int64_t)row - A.from_begin;
@@ -518,6 +554,20 @@ __global__ __launch_bounds__(256) void k4_indel_general_kernel(IndelArgs A, int3
         __threadfence_block();
         __syncthreads();
     }
+}
+
+template <int IDB>
+__global__ __launch_bounds__(256) void k4_indel_general_kernel(IndelArgs A, int32_t W, uint64_t *__restrict__ pm_all,
+                                                                uint64_t *__restrict__ v_all)
+{
+    k4_indel_general_body<IDB, false>(A, W, pm_all, v_all);
+}
+
+template <int IDB>
+__global__ __launch_bounds__(256) void k4_indel_general_topn_kernel(IndelArgs A, int32_t W, uint64_t *__restrict__ pm_all,
+                                                                     uint64_t *__restrict__ v_all)
+{
+    k4_indel_general_body<IDB, true>(A, W, pm_all, v_all);
 }
 
 // ---- to-side plan (cached on the to-list's handle) -----------------------------
@@ -680,7 +730,11 @@ template <typename WORD, int W>
 static int launch_class(pfz_ctx *ctx, const IndelArgs &A, int idb, unsigned grid, hipStream_t st)
 {
     const size_t lds = (size_t)A.n_sym1 * W * sizeof(WORD);
-    if (idb == 8)
+    if (A.ntop > 0 && idb == 8)
+        hipLaunchKernelGGL((k4_indel_topn_kernel<WORD, W, 8>), dim3(grid), dim3(256), lds, st, A);
+    else if (A.ntop > 0)
+        hipLaunchKernelGGL((k4_indel_topn_kernel<WORD, W, 16>), dim3(grid), dim3(256), lds, st, A);
+    else if (idb == 8)
         hipLaunchKernelGGL((k4_indel_kernel<WORD, W, 8>), dim3(grid), dim3(256), lds, st, A);
     else
         hipLaunchKernelGGL((k4_indel_kernel<WORD, W, 16>), dim3(grid), dim3(256), lds, st, A);
@@ -689,8 +743,9 @@ static int launch_class(pfz_ctx *ctx, const IndelArgs &A, int idb, unsigned grid
 }
 
 static int indel_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T_c, const int32_t *skip_idx, int64_t begin,
-                     int64_t end, int32_t *out_idx, double *out_score, double *out_matrix, pfz_topn *out_dev = nullptr)
+                     int64_t end, int32_t *out_idx, double *out_score, double *out_matrix, pfz_topn *out_dev = nullptr, int32_t ntop = 0)
 {
+    // ntop == 0: the arg-max kernels; ntop >= 1: the top-n kernels, out_idx / out_score of [rows * ntop]
     PFZ_REQUIRE(ctx && F && T_c, "pfz_indel: NULL argument");
     PFZ_REQUIRE(begin >= 0 && begin <= end && end <= F->n, "pfz_indel: row range [%lld,%lld) outside [0,%lld)",
                 (long long)begin, (long long)end, (long long)F->n);
@@ -728,7 +783,7 @@ static int indel_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T_c,
         }
     }
     const int64_t n_to = T->n;
-    DevBuf d_skip, d_oidx, d_oscore, d_matrix, d_rows[7], d_pm, d_v;
+    DevBuf d_skip, d_oidx, d_oscore, d_matrix, d_rows[7], d_pm, d_v, d_lists[7];
     int skip_up_to = 0;
     if (skip_idx) {
         std::vector<int32_t> codes(skip_idx, skip_idx + F->n);
@@ -736,8 +791,9 @@ static int indel_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T_c,
         PFZ_REQUIRE(skip_up_to >= 0, "pfz_indel_argmax: skip_idx mixes single choices (>= 0) and 'up to' codes (<= -2)");
         PFZ_TRY(d_skip.upload(ctx, codes));
     }
-    PFZ_TRY(d_oidx.alloc(ctx, (size_t)n_rows * sizeof(int32_t)));
-    PFZ_TRY(d_oscore.alloc(ctx, (size_t)n_rows * sizeof(double)));
+    const size_t n_out = (size_t)n_rows * (size_t)std::max(ntop, 1);
+    PFZ_TRY(d_oidx.alloc(ctx, n_out * sizeof(int32_t)));
+    PFZ_TRY(d_oscore.alloc(ctx, n_out * sizeof(double)));
     if (out_matrix) PFZ_TRY(d_matrix.alloc(ctx, (size_t)n_rows * (size_t)n_to * sizeof(double)));
 
     IndelArgs A;
@@ -763,6 +819,8 @@ static int indel_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T_c,
     const int64_t max_grid = (int64_t)ctx->prop.multiProcessorCount * 8;
     A.parts = 1;
     A.partial = nullptr;
+    A.ntop = ntop;
+    A.lists = nullptr;
     // A class with few rows (the 33 IMDB titles beyond 64 characters ran as 33 workgroups for 178 us) or a unit count
     // that is a small non-integer multiple of the chip's workgroup slots (5000 quads on 2048 slots: the third round is
     // 44 % full) splits every unit's to-groups over `parts` workgroups: >= 4 rounds of work units, each part at least
@@ -774,6 +832,8 @@ static int indel_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T_c,
         return (int32_t)parts;
     };
     auto merge = [&](hipStream_t st) -> int {
+        if (ntop > 0)
+            return topn_merge(A.lists, 4 * A.parts, ntop, A.rows, begin, A.n_rows, (int32_t *)d_oidx.p, (double *)d_oscore.p, st);
         if (A.parts <= 1) return PFZ_OK;
         hipLaunchKernelGGL(k4_merge_parts, dim3((unsigned)((A.n_rows + 255) / 256)), dim3(256), 0, st, A);
         PFZ_HIP(hipGetLastError());
@@ -781,9 +841,16 @@ static int indel_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T_c,
     };
     // every launch has its own (row, part) records: the classes run on two streams
     DevBuf d_part[8];
-    int n_part = 0;
+    int n_part = 0, n_lists = 0;
     auto ensure_partial = [&]() -> int {
         A.partial = nullptr;
+        if (ntop > 0) {
+            // the launch's own lists: its rows x its parts x 4 waves x ntop keys, every one written by the kernel
+            DevBuf &l = d_lists[n_lists++];
+            PFZ_TRY(l.alloc(ctx, (size_t)A.n_rows * (size_t)A.parts * 4 * (size_t)ntop * sizeof(TopnKey)));
+            A.lists = (TopnKey *)l.p;
+            return PFZ_OK;
+        }
         if (A.parts <= 1) return PFZ_OK;
         DevBuf &b = d_part[n_part++];
         PFZ_TRY(b.alloc(ctx, (size_t)A.n_rows * (size_t)A.parts * 3 * sizeof(int32_t)));
@@ -801,7 +868,7 @@ static int indel_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T_c,
     // the row lists of all classes first (the side stream starts from an event recorded behind these copies); class 0:
     // several short from-strings per workgroup pass (PFZ_K4_NO_QUAD=1: the one-string kernel, tests) -- eight of <= 16
     // characters, four of 17 .. 32 (PFZ_K4_NO_OCTO=1: four of <= 32)
-    const bool quad = !cls[0].empty() && !out_matrix && (size_t)A.n_sym1 * sizeof(uint4) <= 60 * 1024 && T->max_len < (1 << 24) - 64 &&
+    const bool quad = !cls[0].empty() && !out_matrix && ntop == 0 && (size_t)A.n_sym1 * sizeof(uint4) <= 60 * 1024 && T->max_len < (1 << 24) - 64 &&
                       !knob_set(knob::K4_NO_QUAD);
     std::vector<int32_t> rows8, rows4;
     if (quad) {
@@ -880,17 +947,25 @@ static int indel_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T_c,
         PFZ_TRY(d_rows[6].upload(ctx, cls[6]));
         A.rows = (const int32_t *)d_rows[6].p;
         A.n_rows = (int32_t)cls[6].size();
-        if (pl->idb == 8)
+        PFZ_TRY(ensure_partial());
+        if (ntop > 0 && pl->idb == 8)
+            hipLaunchKernelGGL((k4_indel_general_topn_kernel<8>), dim3((unsigned)gridg), dim3(256), 0, ctx->stream, A, W,
+                               (uint64_t *)d_pm.p, (uint64_t *)d_v.p);
+        else if (ntop > 0)
+            hipLaunchKernelGGL((k4_indel_general_topn_kernel<16>), dim3((unsigned)gridg), dim3(256), 0, ctx->stream, A, W,
+                               (uint64_t *)d_pm.p, (uint64_t *)d_v.p);
+        else if (pl->idb == 8)
             hipLaunchKernelGGL((k4_indel_general_kernel<8>), dim3((unsigned)gridg), dim3(256), 0, ctx->stream, A, W,
                                (uint64_t *)d_pm.p, (uint64_t *)d_v.p);
         else
             hipLaunchKernelGGL((k4_indel_general_kernel<16>), dim3((unsigned)gridg), dim3(256), 0, ctx->stream, A, W,
                                (uint64_t *)d_pm.p, (uint64_t *)d_v.p);
         PFZ_HIP(hipGetLastError());
+        PFZ_TRY(merge(ctx->stream));
     }
     if (out_dev) return best_to_topn(ctx, (const int32_t *)d_oidx.p, (const double *)d_oscore.p, n_rows, out_dev);     // (no copy, no wait)
-    if (out_idx) PFZ_TRY(copy_d2h(ctx, out_idx, d_oidx.p, (size_t)n_rows * sizeof(int32_t)));
-    if (out_score) PFZ_TRY(copy_d2h(ctx, out_score, d_oscore.p, (size_t)n_rows * sizeof(double)));
+    if (out_idx) PFZ_TRY(copy_d2h(ctx, out_idx, d_oidx.p, n_out * sizeof(int32_t)));
+    if (out_score) PFZ_TRY(copy_d2h(ctx, out_score, d_oscore.p, n_out * sizeof(double)));
     if (out_matrix) PFZ_TRY(copy_d2h(ctx, out_matrix, d_matrix.p, (size_t)n_rows * (size_t)n_to * sizeof(double)));
     PFZ_HIP(hipStreamSynchronize(ctx->stream));
     return PFZ_OK;
@@ -915,6 +990,18 @@ int pfz_indel_argmax_dev(pfz_ctx *ctx, const pfz_strings *from_strings, const pf
     PFZ_REQUIRE(out && out->ntop == 2 && out->n_rows >= from_end - from_begin,
                 "pfz_indel_argmax_dev: the result buffer must have 2 columns and >= %lld rows", (long long)(from_end - from_begin));
     return indel_run(ctx, from_strings, to_strings, skip_idx, from_begin, from_end, nullptr, nullptr, nullptr, out);
+}
+
+int pfz_indel_topn(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings, const int32_t *skip_idx,
+                   int64_t from_begin, int64_t from_end, int32_t ntop, int32_t *out_idx, double *out_score)
+{
+    PFZ_REQUIRE(out_idx && out_score, "pfz_indel_topn: NULL output");
+    PFZ_REQUIRE(ntop >= 1, "pfz_indel_topn: ntop %d < 1", ntop);
+    if (ntop > kTopnMax) {
+        set_error("pfz_indel_topn: ntop %d exceeds the limit of %d (one list entry per lane of a wave)", ntop, kTopnMax);
+        return PFZ_ERR_UNSUPPORTED;
+    }
+    return indel_run(ctx, from_strings, to_strings, skip_idx, from_begin, from_end, out_idx, out_score, nullptr, nullptr, ntop);
 }
 
 int pfz_indel_matrix_host(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings,

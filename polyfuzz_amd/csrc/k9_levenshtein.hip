@@ -20,9 +20,15 @@
 // Register kernel: from-strings of up to 32 characters in 32-bit words, of up to 64 in 64-bit words.  Longer from-strings, and an
 // alphabet whose table exceeds 60 KiB, take the general kernel: words and match table in global memory, every pair walked, slow.
 // Every launch leaves (score, index) records per from-string and part; k9_merge picks the first maximum of a row over them.
+// The top-n form (pfz_lev_topn, topn_wave.h): every wave keeps ONE sorted list of its ntop best pairs, one entry per lane, in place
+// of the lanes' bests.  The workgroup's LDS word then holds the best LAST entry of a full list: ntop choices at or above that
+// score exist in the row, so a to-string whose length bound is STRICTLY below it is none of the row's ntop best -- the same
+// test, the same walk order, the same end of a direction.  The waves leave their lists side by side, in a buffer per launch
+// (rows of the class x its parts x 4 x ntop keys); topn_merge picks the row's.
 // Bound: integer VALU + LDS look-ups, one sweep per pair (measured beside K4 and K8).
 #include "k4_plan.h"
 #include "k9_core.h"
+#include "topn_wave.h"
 
 #include <algorithm>
 #include <limits.h>
@@ -58,6 +64,8 @@ struct LevArgs {
     int32_t n_slots;           // part p of row r leaves its best in rec[(r - from_begin) * n_slots + p]
     LevRec *rec;
     unsigned long long *n_walked;   // optional: pairs whose recurrence was walked (the profile's work count)
+    int32_t ntop;              // the top-n kernels: wave w of part p of row r leaves its list in
+    TopnKey *lists;            // lists[((r * parts + p) * 4 + w) * ntop], r the row's place in `rows`: one buffer per launch
 };
 
 struct LevBest {
@@ -111,8 +119,9 @@ __device__ inline void lev_lds_or(uint64_t *p, uint64_t v) { atomicOr((unsigned 
 constexpr int K9_LDS_HEAD = 16;      // the workgroup's best in front of the match table (which stays 16-byte aligned)
 
 // WORD: uint32_t (from-strings of <= 32 characters) or uint64_t (<= 64), against to-strings of any length
-template <typename WORD, int IDB, bool OSA>
-__global__ __launch_bounds__(256) void k9_lev_kernel(LevArgs A)
+// TOPN: a list of A.ntop per wave in place of a best per lane
+template <typename WORD, int IDB, bool OSA, bool TOPN>
+__device__ __forceinline__ void k9_lev_body(const LevArgs &A)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     unsigned long long *wg_best = (unsigned long long *)smem_raw;
@@ -139,6 +148,7 @@ __global__ __launch_bounds__(256) void k9_lev_kernel(LevArgs A)
 
         const int skip = A.skip_idx ? A.skip_idx[row] : -1;
         LevBest best = {-1.0, INT_MAX};
+        TopnList list = topn_empty();
         int walked = 0;
         // this wave's groups: base + stride * k, k < K (wave-uniform: say so, or the loops below get a per-lane trip count)
         const int base = __builtin_amdgcn_readfirstlane(wave + 4 * part), stride = 4 * parts;
@@ -186,6 +196,15 @@ __global__ __launch_bounds__(256) void k9_lev_kernel(LevArgs A)
                 for (int q = 0; q < PER; ++q)
                     lev_step<WORD, OSA>(s, pm[__builtin_amdgcn_ubfe(pk, q * IDB, IDB)], t * PER + q < lb);
             }
+            if constexpr (TOPN) {
+                walked += real;
+                topn_insert(list, A.ntop, !out, out ? 0.0 : lev_similarity(lev_distance(s.dist, la, lb), la, lb), orig);
+                // a full list: A.ntop choices at or above its last entry's score exist
+                double last;
+                if (topn_full(list, A.ntop, &last) && last > wb && lane == 0)
+                    atomicMax(wg_best, (unsigned long long)__double_as_longlong(last));
+                continue;
+            }
             if (!real) continue;
             ++walked;
             const int d = lev_distance(s.dist, la, lb);
@@ -195,19 +214,35 @@ __global__ __launch_bounds__(256) void k9_lev_kernel(LevArgs A)
             lev_take(best, sc, orig);
             if (prune && sc > wb) atomicMax(wg_best, (unsigned long long)__double_as_longlong(sc));
         }
-        lev_block_best(best, red_s, red_i, A.rec + ((int64_t)row - A.from_begin) * A.n_slots + part);
+        if constexpr (TOPN) {
+            topn_store(list, A.ntop, A.lists + (((int64_t)r * parts + part) * 4 + wave) * A.ntop);
+            __syncthreads();      // (every wave is done with the match table)
+        }
+        else lev_block_best(best, red_s, red_i, A.rec + ((int64_t)row - A.from_begin) * A.n_slots + part);
         lev_count_walked(A.n_walked, walked);
         if (my_sym) pm[my_sym] = 0;      // clear the entries of this from-string
         __syncthreads();
     }
 }
 
+template <typename WORD, int IDB, bool OSA>
+__global__ __launch_bounds__(256) void k9_lev_kernel(LevArgs A)
+{
+    k9_lev_body<WORD, IDB, OSA, false>(A);
+}
+
+template <typename WORD, int IDB, bool OSA>
+__global__ __launch_bounds__(256) void k9_lev_topn_kernel(LevArgs A)
+{
+    k9_lev_body<WORD, IDB, OSA, true>(A);
+}
+
 // The general case: any from-length, any alphabet.  The match table of the workgroup's from-string (WA words per symbol) and every
 // lane's column (VP, VN and, for OSA, the previous D0: WA words each) are in global memory; every pair is walked.
-template <int IDB, bool OSA>
-__global__ __launch_bounds__(256) void k9_lev_general_kernel(LevArgs A, int32_t WA, uint64_t *__restrict__ pm_all,
-                                                              uint64_t *__restrict__ vp_all, uint64_t *__restrict__ vn_all,
-                                                              uint64_t *__restrict__ d0_all)
+template <int IDB, bool OSA, bool TOPN>
+__device__ __forceinline__ void k9_lev_general_body(const LevArgs &A, int32_t WA, uint64_t *__restrict__ pm_all,
+                                                    uint64_t *__restrict__ vp_all, uint64_t *__restrict__ vn_all,
+                                                    uint64_t *__restrict__ d0_all)
 {
     __shared__ double red_s[4];
     __shared__ int red_i[4];
@@ -233,6 +268,7 @@ __global__ __launch_bounds__(256) void k9_lev_general_kernel(LevArgs A, int32_t 
         const int skip = A.skip_idx ? A.skip_idx[row] : -1;
         const uint64_t last = la > 0 ? 1ull << ((la - 1) % 64) : 0ull;
         LevBest best = {-1.0, INT_MAX};
+        TopnList list = topn_empty();
         int walked = 0;
         for (int g = wave + 4 * part; g < A.n_groups; g += 4 * parts) {
             const uint32_t *gp = A.b_packed + A.g_off[g] + lane;
@@ -266,14 +302,23 @@ __global__ __launch_bounds__(256) void k9_lev_general_kernel(LevArgs A, int32_t 
                     c_prev = c;
                 }
             }
-            if (orig >= 0) {
+            if constexpr (TOPN) {
+                const bool have = orig >= 0 && !choice_left_out(orig, skip, A.skip_up_to);
+                walked += orig >= 0;
+                topn_insert(list, A.ntop, have, have ? lev_similarity(lev_distance(dist, la, lb), la, lb) : 0.0, orig);
+            }
+            else if (orig >= 0) {
                 ++walked;
                 const int d = lev_distance(dist, la, lb);
                 if (A.matrix) A.matrix[((int64_t)row - A.from_begin) * A.n_to + orig] = d;
                 if (!choice_left_out(orig, skip, A.skip_up_to)) lev_take(best, lev_similarity(d, la, lb), orig);
             }
         }
-        lev_block_best(best, red_s, red_i, A.rec + ((int64_t)row - A.from_begin) * A.n_slots + part);
+        if constexpr (TOPN) {
+            topn_store(list, A.ntop, A.lists + (((int64_t)r * parts + part) * 4 + wave) * A.ntop);
+            __syncthreads();      // (every wave is done with the match table)
+        }
+        else lev_block_best(best, red_s, red_i, A.rec + ((int64_t)row - A.from_begin) * A.n_slots + part);
         lev_count_walked(A.n_walked, walked);
         for (int p = tid; p < la; p += 256) {
             const int sy = lev_a_symbol(A, a0 + p);
@@ -282,6 +327,22 @@ __global__ __launch_bounds__(256) void k9_lev_general_kernel(LevArgs A, int32_t 
         __threadfence_block();
         __syncthreads();
     }
+}
+
+template <int IDB, bool OSA>
+__global__ __launch_bounds__(256) void k9_lev_general_kernel(LevArgs A, int32_t WA, uint64_t *__restrict__ pm_all,
+                                                              uint64_t *__restrict__ vp_all, uint64_t *__restrict__ vn_all,
+                                                              uint64_t *__restrict__ d0_all)
+{
+    k9_lev_general_body<IDB, OSA, false>(A, WA, pm_all, vp_all, vn_all, d0_all);
+}
+
+template <int IDB, bool OSA>
+__global__ __launch_bounds__(256) void k9_lev_general_topn_kernel(LevArgs A, int32_t WA, uint64_t *__restrict__ pm_all,
+                                                                   uint64_t *__restrict__ vp_all, uint64_t *__restrict__ vn_all,
+                                                                   uint64_t *__restrict__ d0_all)
+{
+    k9_lev_general_body<IDB, OSA, true>(A, WA, pm_all, vp_all, vn_all, d0_all);
 }
 
 // the first maximum of every from-string over the records its launch left
@@ -302,15 +363,22 @@ __global__ __launch_bounds__(256) void k9_merge(const LevRec *__restrict__ rec, 
 template <typename WORD>
 static void launch_reg(const LevArgs &A, int idb, int osa, dim3 grid, size_t lds, hipStream_t st)
 {
-    if (idb == 8 && !osa) hipLaunchKernelGGL((k9_lev_kernel<WORD, 8, false>), grid, dim3(256), lds, st, A);
+    if (A.ntop > 0) {
+        if (idb == 8 && !osa) hipLaunchKernelGGL((k9_lev_topn_kernel<WORD, 8, false>), grid, dim3(256), lds, st, A);
+        else if (idb == 8) hipLaunchKernelGGL((k9_lev_topn_kernel<WORD, 8, true>), grid, dim3(256), lds, st, A);
+        else if (!osa) hipLaunchKernelGGL((k9_lev_topn_kernel<WORD, 16, false>), grid, dim3(256), lds, st, A);
+        else hipLaunchKernelGGL((k9_lev_topn_kernel<WORD, 16, true>), grid, dim3(256), lds, st, A);
+    }
+    else if (idb == 8 && !osa) hipLaunchKernelGGL((k9_lev_kernel<WORD, 8, false>), grid, dim3(256), lds, st, A);
     else if (idb == 8) hipLaunchKernelGGL((k9_lev_kernel<WORD, 8, true>), grid, dim3(256), lds, st, A);
     else if (!osa) hipLaunchKernelGGL((k9_lev_kernel<WORD, 16, false>), grid, dim3(256), lds, st, A);
     else hipLaunchKernelGGL((k9_lev_kernel<WORD, 16, true>), grid, dim3(256), lds, st, A);
 }
 
 static int lev_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, int32_t scorer, const int32_t *skip_idx, int64_t begin,
-                   int64_t end, int32_t *out_idx, double *out_score, int32_t *out_matrix, pfz_topn *out_dev = nullptr)
+                   int64_t end, int32_t *out_idx, double *out_score, int32_t *out_matrix, pfz_topn *out_dev = nullptr, int32_t ntop = 0)
 {
+    // ntop == 0: the arg-max kernels; ntop >= 1: the top-n kernels, out_idx / out_score of [rows * ntop]
     PFZ_REQUIRE(ctx && F && T, "pfz_lev: NULL argument");
     PFZ_REQUIRE(scorer == 0 || scorer == 1, "pfz_lev: scorer %d is neither 0 (Levenshtein) nor 1 (OSA)", scorer);
     PFZ_REQUIRE(begin >= 0 && begin <= end && end <= F->n, "pfz_lev: row range [%lld,%lld) outside [0,%lld)", (long long)begin,
@@ -339,7 +407,7 @@ static int lev_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, int
         if (cls == 2) longest = std::max(longest, la);
     }
 
-    DevBuf d_skip, d_oidx, d_oscore, d_matrix, d_rows[3], d_rec, d_pm, d_vp, d_vn, d_d0, d_walked;
+    DevBuf d_skip, d_oidx, d_oscore, d_matrix, d_rows[3], d_lists[3], d_rec, d_pm, d_vp, d_vn, d_d0, d_walked;
     int skip_up_to = 0;
     if (skip_idx) {
         std::vector<int32_t> codes(skip_idx, skip_idx + F->n);
@@ -347,8 +415,9 @@ static int lev_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, int
         PFZ_REQUIRE(skip_up_to >= 0, "pfz_lev_argmax: skip_idx mixes single choices (>= 0) and 'up to' codes (<= -2)");
         PFZ_TRY(d_skip.upload(ctx, codes));
     }
-    PFZ_TRY(d_oidx.alloc(ctx, (size_t)n_rows * sizeof(int32_t)));
-    PFZ_TRY(d_oscore.alloc(ctx, (size_t)n_rows * sizeof(double)));
+    const size_t n_out = (size_t)n_rows * (size_t)std::max(ntop, 1);
+    PFZ_TRY(d_oidx.alloc(ctx, n_out * sizeof(int32_t)));
+    PFZ_TRY(d_oscore.alloc(ctx, n_out * sizeof(double)));
     if (out_matrix) PFZ_TRY(d_matrix.alloc(ctx, (size_t)n_rows * (size_t)n_to * sizeof(int32_t)));
 
     // Few from-strings: the to-groups of each are split over `parts` workgroups (K4's rule: >= 4 rounds of work units on the chip,
@@ -366,9 +435,13 @@ static int lev_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, int
         parts[c] = (int32_t)std::max<int64_t>(1, std::min(want, cap));
         n_slots = std::max(n_slots, parts[c]);
     }
-    const size_t rec_bytes = (size_t)n_rows * (size_t)n_slots * sizeof(LevRec);
+    // (top-n: every class has a list buffer of its own -- rows of the class x ITS parts x 4 waves x ntop keys, all of them written)
+    const size_t rec_bytes = ntop > 0 ? 0 : (size_t)n_rows * (size_t)n_slots * sizeof(LevRec);
     PFZ_TRY(d_rec.alloc(ctx, rec_bytes));
-    PFZ_HIP(hipMemsetAsync(d_rec.p, 0xff, rec_bytes, ctx->stream));      // idx = -1: no candidate
+    if (rec_bytes) PFZ_HIP(hipMemsetAsync(d_rec.p, 0xff, rec_bytes, ctx->stream));      // idx = -1: no candidate
+    if (ntop > 0)
+        for (int c = 0; c < 3; ++c)
+            if (parts[c] != 0) PFZ_TRY(d_lists[c].alloc(ctx, rows_cls[c].size() * (size_t)parts[c] * 4 * (size_t)ntop * sizeof(TopnKey)));
 
     LevArgs A;
     A.a_chars = F->chars;
@@ -390,6 +463,8 @@ static int lev_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, int
     A.matrix = out_matrix ? (int32_t *)d_matrix.p : nullptr;
     A.n_slots = n_slots;
     A.rec = (LevRec *)d_rec.p;
+    A.ntop = ntop;
+    A.lists = nullptr;
     A.n_walked = nullptr;
     if (ctx->prof) {          // pfz_prof_get("k9_pairs_walked"): how many pairs the arg-max walked (read after the timed scope)
         PFZ_TRY(d_walked.alloc(ctx, sizeof(unsigned long long)));
@@ -404,6 +479,7 @@ static int lev_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, int
             A.rows = d_rows[c].as<int32_t>();
             A.n_rows = (int32_t)rows_cls[c].size();
             A.parts = parts[c];
+            A.lists = d_lists[c].as<TopnKey>();
             const dim3 grid((unsigned)std::min<int64_t>((int64_t)A.n_rows * A.parts, max_grid));
             const size_t lds = K9_LDS_HEAD + (size_t)A.n_sym1 * (c == 1 ? sizeof(uint64_t) : sizeof(uint32_t));
             if (c == 0) launch_reg<uint32_t>(A, pl->idb, scorer, grid, lds, ctx->stream);
@@ -414,6 +490,7 @@ static int lev_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, int
             A.rows = d_rows[2].as<int32_t>();
             A.n_rows = (int32_t)rows_cls[2].size();
             A.parts = parts[2];
+            A.lists = d_lists[2].as<TopnKey>();
             const int32_t WA = (int32_t)((longest + 63) / 64);
             int64_t grid = std::min<int64_t>((int64_t)A.n_rows * A.parts, max_grid);
             const size_t pm_per = (size_t)A.n_sym1 * (size_t)WA * sizeof(uint64_t);
@@ -431,8 +508,14 @@ static int lev_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, int
             PFZ_TRY(d_d0.alloc(ctx, col_bytes));
             PFZ_HIP(hipMemsetAsync(d_pm.p, 0, pm_per * (size_t)grid, ctx->stream));
 #define PFZ_K9_GENERAL(IDB, OSA)                                                                                             \
-    hipLaunchKernelGGL((k9_lev_general_kernel<IDB, OSA>), dim3((unsigned)grid), dim3(256), 0, ctx->stream, A, WA,            \
-                       d_pm.as<uint64_t>(), d_vp.as<uint64_t>(), d_vn.as<uint64_t>(), d_d0.as<uint64_t>())
+    do {                                                                                                                     \
+        if (ntop > 0)                                                                                                        \
+            hipLaunchKernelGGL((k9_lev_general_topn_kernel<IDB, OSA>), dim3((unsigned)grid), dim3(256), 0, ctx->stream, A,   \
+                               WA, d_pm.as<uint64_t>(), d_vp.as<uint64_t>(), d_vn.as<uint64_t>(), d_d0.as<uint64_t>());      \
+        else                                                                                                                 \
+            hipLaunchKernelGGL((k9_lev_general_kernel<IDB, OSA>), dim3((unsigned)grid), dim3(256), 0, ctx->stream, A, WA,    \
+                               d_pm.as<uint64_t>(), d_vp.as<uint64_t>(), d_vn.as<uint64_t>(), d_d0.as<uint64_t>());          \
+    } while (0)
             if (pl->idb == 8 && !scorer) PFZ_K9_GENERAL(8, false);
             else if (pl->idb == 8) PFZ_K9_GENERAL(8, true);
             else if (!scorer) PFZ_K9_GENERAL(16, false);
@@ -440,8 +523,15 @@ static int lev_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, int
 #undef PFZ_K9_GENERAL
             PFZ_HIP(hipGetLastError());
         }
-        hipLaunchKernelGGL(k9_merge, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, ctx->stream, (const LevRec *)d_rec.p, n_slots,
-                           n_rows, d_oidx.as<int32_t>(), d_oscore.as<double>());
+        if (ntop > 0) {
+            for (int c = 0; c < 3; ++c)
+                if (parts[c] != 0)
+                    PFZ_TRY(topn_merge(d_lists[c].as<TopnKey>(), 4 * parts[c], ntop, d_rows[c].as<int32_t>(), begin, (int64_t)rows_cls[c].size(),
+                                       d_oidx.as<int32_t>(), d_oscore.as<double>(), ctx->stream));
+        }
+        else
+            hipLaunchKernelGGL(k9_merge, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, ctx->stream, (const LevRec *)d_rec.p, n_slots,
+                               n_rows, d_oidx.as<int32_t>(), d_oscore.as<double>());
         PFZ_HIP(hipGetLastError());
     }
     if (A.n_walked) {
@@ -450,8 +540,8 @@ static int lev_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, int
         prof_count(ctx, "k9_pairs_walked", (int64_t)n);
     }
     if (out_dev) return best_to_topn(ctx, d_oidx.as<int32_t>(), d_oscore.as<double>(), n_rows, out_dev);     // (no copy, no wait)
-    if (out_idx) PFZ_TRY(copy_d2h(ctx, out_idx, d_oidx.p, (size_t)n_rows * sizeof(int32_t)));
-    if (out_score) PFZ_TRY(copy_d2h(ctx, out_score, d_oscore.p, (size_t)n_rows * sizeof(double)));
+    if (out_idx) PFZ_TRY(copy_d2h(ctx, out_idx, d_oidx.p, n_out * sizeof(int32_t)));
+    if (out_score) PFZ_TRY(copy_d2h(ctx, out_score, d_oscore.p, n_out * sizeof(double)));
     if (out_matrix) PFZ_TRY(copy_d2h(ctx, out_matrix, d_matrix.p, (size_t)n_rows * (size_t)n_to * sizeof(int32_t)));
     PFZ_HIP(hipStreamSynchronize(ctx->stream));
     return PFZ_OK;
@@ -476,6 +566,18 @@ int pfz_lev_argmax_dev(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_
     PFZ_REQUIRE(out && out->ntop == 2 && out->n_rows >= from_end - from_begin,
                 "pfz_lev_argmax_dev: the result buffer must have 2 columns and >= %lld rows", (long long)(from_end - from_begin));
     return lev_run(ctx, from_strings, to_strings, scorer, skip_idx, from_begin, from_end, nullptr, nullptr, nullptr, out);
+}
+
+int pfz_lev_topn(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings, int32_t scorer, const int32_t *skip_idx,
+                 int64_t from_begin, int64_t from_end, int32_t ntop, int32_t *out_idx, double *out_score)
+{
+    PFZ_REQUIRE(out_idx && out_score, "pfz_lev_topn: NULL output");
+    PFZ_REQUIRE(ntop >= 1, "pfz_lev_topn: ntop %d < 1", ntop);
+    if (ntop > kTopnMax) {
+        set_error("pfz_lev_topn: ntop %d exceeds the limit of %d (one list entry per lane of a wave)", ntop, kTopnMax);
+        return PFZ_ERR_UNSUPPORTED;
+    }
+    return lev_run(ctx, from_strings, to_strings, scorer, skip_idx, from_begin, from_end, out_idx, out_score, nullptr, nullptr, ntop);
 }
 
 int pfz_lev_matrix_host(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings, int32_t scorer,

@@ -1,6 +1,7 @@
 // Context, error reporting, timers, CSR / top-n containers and the shared
 // device scan of libpolyfuzz_hip.so.
 #include "pfz_internal.h"
+#include "topn_wave.h"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -588,6 +589,40 @@ int exclusive_scan_i32(pfz_ctx *ctx, int32_t *data, int64_t n, LazyI32 *total)
     hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)n_tiles), dim3(kScanThreads), 0, ctx->stream, data, n, tile_sums);
     PFZ_HIP(hipGetLastError());
     return total ? lazy_begin(ctx, total, data + n) : PFZ_OK;
+}
+
+// topn_wave.h: one wave per row picks the row's top-n out of the lists its waves and parts left
+static __global__ __launch_bounds__(256) void topn_merge_kernel(const TopnKey *__restrict__ lists, int32_t n_lists, int32_t ntop,
+                                                                 const int32_t *__restrict__ rows, int64_t from_begin, int64_t n_rows,
+                                                                 int32_t *__restrict__ out_idx, double *__restrict__ out_score)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);       // (wave-uniform)
+    if (r >= n_rows) return;
+    const int64_t n_keys = (int64_t)n_lists * ntop;
+    const TopnKey *src = lists + r * n_keys;
+    TopnList l = topn_empty();
+    for (int64_t k0 = 0; k0 < n_keys; k0 += 64) {
+        const bool in = k0 + lane < n_keys;
+        const double s = in ? src[k0 + lane].score : 0.0;
+        const int i = in ? src[k0 + lane].idx : -1;
+        topn_insert(l, ntop, i >= 0, s, i);
+    }
+    const int64_t o = rows ? (int64_t)rows[r] - from_begin : r;
+    if (lane < ntop) {
+        out_idx[o * ntop + lane] = l.idx == INT_MAX ? -1 : l.idx;
+        out_score[o * ntop + lane] = l.idx == INT_MAX ? 0.0 : l.score;
+    }
+}
+
+int topn_merge(const TopnKey *lists, int32_t n_lists, int32_t ntop, const int32_t *rows, int64_t from_begin, int64_t n_rows,
+               int32_t *out_idx, double *out_score, hipStream_t st)
+{
+    if (n_rows <= 0) return PFZ_OK;
+    hipLaunchKernelGGL(topn_merge_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, st, lists, n_lists, ntop, rows, from_begin,
+                       n_rows, out_idx, out_score);
+    PFZ_HIP(hipGetLastError());
+    return PFZ_OK;
 }
 
 }  // namespace pfz

@@ -20,7 +20,7 @@ import pandas as pd
 
 from .. import _lib
 from ._base import BaseMatcher
-from ._utils import pair_frame, pair_frame_blocks
+from ._utils import gather_column, object_column, pair_frame, pair_frame_blocks
 
 
 _JARO_NAMES = {"jaro": "jaro", "jaro_similarity": "jaro", "jaro_winkler": "jaro_winkler", "jaro_winkler_similarity": "jaro_winkler"}
@@ -88,6 +88,38 @@ def _device_scorer(scorer) -> str:
     return name if name in _DEVICE_SCORERS else ""
 
 
+# the scorers whose kernels have a top-n form (K4 on one fixed string per list element, K9); Jaro (K8) and the per-pair scorers
+# (K7) prune around a single best and keep their arg-max only
+_TOP_N_SCORERS = ("ratio", "QRatio", "token_sort_ratio", "levenshtein", "osa")
+_TOP_N_MAX = 64                 # one list entry per lane of a wave (csrc/topn_wave.h)
+
+
+def _top_n_choices(ctx, name, from_list, names, skip, self_match, to_dev, ntop):
+    """(index int32[n, ntop], score float64[n, ntop]) of every from-string's ntop best choices under scorer `name`, in the order
+    (score descending, choice index ascending); the arguments are best_choice_async's"""
+    from ._rapidfuzz import upload_for
+    f_dev = upload_for(ctx, name, from_list)
+    t_dev = f_dev if self_match else (to_dev if to_dev is not None else upload_for(ctx, name, names))
+    if name in _lib.LEV_SCORERS:
+        return _lib.lev_topn(ctx, f_dev, t_dev, name, ntop, skip)
+    idx, score = _lib.indel_topn(ctx, f_dev, t_dev, ntop, skip)
+    if name == "QRatio":
+        # QRatio differs from ratio only when BOTH strings are empty (0 instead of 100): an empty from-string scores 0 against
+        # every choice, so its columns are simply its first choices
+        # (the skip code alone says which: 0 .. ntop - 1 without the one choice left out, or the ntop behind "everything up to")
+        n_to = len(names)
+        for i in [i for i, s in enumerate(from_list) if len(s) == 0]:
+            sk = -1 if skip is None else int(skip[i])
+            if sk <= -2:
+                first = np.arange(-1 - sk, min(n_to, -1 - sk + ntop))
+            else:
+                first = np.arange(0, min(n_to, ntop + 1))
+                first = first[first != sk][:ntop]
+            idx[i], score[i] = -1, 0.0
+            idx[i, :len(first)] = first
+    return idx, score
+
+
 class EditDistance(BaseMatcher):
     """
     Calculate the Edit Distance between lists of strings (Indel ratio, rapidfuzz.fuzz.ratio)
@@ -125,6 +157,17 @@ class EditDistance(BaseMatcher):
     the best so far.  PARITY UNPINNED beyond the oracle; live pin armed: rapidfuzz is not importable where this was built,
     the scorers are the restatement of its definition in include/polyfuzz_hip.h (tests/test_levenshtein_cpu.py compares with
     rapidfuzz itself wherever it is installed).
+
+    top_n (attribute, default 1; the constructor keeps the reference's signature: `m = EditDistance(scorer="osa"); m.top_n = 5`):
+    the number of best choices per from-string.  The reference's facade has it for TFIDF and Embeddings only (polyfuzz.py:100),
+    its edit-distance loop cannot afford more than the one np.argmax (_distance.py:89-102); here the columns To, Similarity,
+    To_2, Similarity_2, ... (the layout of cosine_similarity's frame) are the choices in the order np.argsort(-scores,
+    kind="stable") gives: score descending, equal scores in list order, exact, on the device -- for "ratio", "QRatio",
+    "token_sort_ratio" (K4), "levenshtein" and "osa" (K9).  The scores are the scorer's own float64, unrounded; `normalize` takes
+    ONE minimum and maximum over all Similarity columns.  top_n is clipped to the number of choices every row has (the
+    reference's clip, _utils.py:55-56); more than 64 after clipping raises _lib.PfzUnsupported; the Jaro scorers and the
+    per-pair scorers (K7) raise NotImplementedError from `match` -- their kernels keep a single best.  An int >= 1, else
+    ValueError; kept through pickling.
     """
     def __init__(self,
                  n_jobs: int = 1,
@@ -144,6 +187,18 @@ class EditDistance(BaseMatcher):
         self.n_jobs = n_jobs
         self._to_dev = self._to_names = None     # device copy (+ cached K4 plan) of the last to-list
         self.last_timings = None
+        self._top_n = 1
+
+    @property
+    def top_n(self) -> int:
+        """best choices per from-string (class docstring); 1: the best match, the reference's frame"""
+        return self.__dict__.get("_top_n", 1)          # (a matcher pickled before the attribute existed)
+
+    @top_n.setter
+    def top_n(self, value):
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < 1:
+            raise ValueError(f"top_n must be an int >= 1, not {value!r}")
+        self._top_n = int(value)
 
     def match(self,
               from_list: List[str],
@@ -155,6 +210,8 @@ class EditDistance(BaseMatcher):
         polyfuzz.py:234-240).  `re_train=False` only lets this matcher re-use what is resident: when the list it is handed
         IS the previous call's (the same object, or an equal list), its device copy and K4 plan (alphabet, length-sorted
         packed groups) are used again -- no upload, no preparation.  Any other list is uploaded. """
+        if self.top_n > 1:
+            return self._match_top_n(from_list, to_list, reuse_to=kwargs.get("re_train", True) is False)
         t0 = time.perf_counter()
         pending, names = self._best(from_list, to_list, reuse_to=kwargs.get("re_train", True) is False)
         blocks = pair_frame_blocks(from_list)        # (the From column: host work while the device scores)
@@ -168,7 +225,33 @@ class EditDistance(BaseMatcher):
         self.last_timings = {"device": (t1 - t0) * 1e3, "frame": (time.perf_counter() - t1) * 1e3}
         return matches
 
-    def _best(self, from_list, to_list, reuse_to=False):
+    def _match_top_n(self, from_list, to_list, reuse_to):
+        """the frame From, To, Similarity, To_2, Similarity_2, ... of the top_n best choices (class docstring)"""
+        if self._scorer_name not in _TOP_N_SCORERS:
+            raise NotImplementedError(
+                f"EditDistance.top_n > 1 runs on the GPU for the scorers {_TOP_N_SCORERS}; the kernels of scorer "
+                f"{self._scorer_name!r} keep a single best per from-string -- set top_n = 1")
+        t0 = time.perf_counter()
+        # every row has len(to_list) choices, or one less in a self-match (reference _utils.py:55-56, applied to choices)
+        ntop = max(1, min(self.top_n, (len(from_list) - 1) if to_list is None else len(to_list)))
+        if ntop > _TOP_N_MAX:
+            raise _lib.PfzUnsupported(-4, f"EditDistance.top_n = {ntop} exceeds the limit of {_TOP_N_MAX} best choices per from-string")
+        (idx, score), names = self._best(from_list, to_list, reuse_to=reuse_to, top_n=ntop)
+        t1 = time.perf_counter()
+        data = {"From": object_column(from_list)}
+        for r in range(ntop):
+            data["To" if r == 0 else f"To_{r + 1}"] = gather_column(names, np.ascontiguousarray(idx[:, r]))
+            data["Similarity" if r == 0 else f"Similarity_{r + 1}"] = score[:, r].copy()
+        matches = pd.DataFrame(data, copy=False)
+        if self.normalize and score.size:      # _distance.py:83-86 with one minimum and one maximum over all Similarity columns
+            lo, hi = score.min(), score.max()
+            for r in range(ntop):
+                c = "Similarity" if r == 0 else f"Similarity_{r + 1}"
+                matches[c] = (matches[c] - lo) / (hi - lo)
+        self.last_timings = {"device": (t1 - t0) * 1e3, "frame": (time.perf_counter() - t1) * 1e3}
+        return matches
+
+    def _best(self, from_list, to_list, reuse_to=False, top_n=None):
         ctx = _lib.Context.default()
         self_match = to_list is None
         skip = None
@@ -199,6 +282,8 @@ class EditDistance(BaseMatcher):
             else:
                 to_dev = upload_for(ctx, name, names)
             self._to_dev, self._to_names = to_dev, snap
+        if top_n is not None:
+            return _top_n_choices(ctx, name, from_list, names, skip, self_match, to_dev, top_n), names
         return best_choice_async(ctx, name, from_list, names, skip, self_match, to_dev=to_dev), names
 
     # a matcher is pickled by joblib (reference _distance.py:77, polyfuzz.py:429-457): device handles stay behind
