@@ -394,6 +394,33 @@ int pfz_lev_topn(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_string
 int pfz_lev_matrix_host(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings, int32_t scorer,
                         int64_t from_begin, int64_t from_end, int32_t *out_matrix);
 
+/* ---- K10: a candidate table rescored by edit distance ----------------------
+ * Blocking, then exact scoring: extends the reference's edit-distance loop (polyfuzz/models/_distance.py:89-102: scorer(from, to)
+ * for every to-string, then the best) restricted to the candidates a cheap matcher left per from-string (the top_n table of
+ * polyfuzz/models/_utils.py:82-91, e.g. a pfz_cossim_topn result of the TF-IDF matrices of the same two lists).  `candidates` is a
+ * result buffer of at least from_strings->n rows whose idx half holds, per from-row, indices into `to_strings`; its val half is
+ * ignored, and the table is read on the device, never downloaded.  An index outside [0, n_to), the -1 of an empty slot among
+ * them, is skipped wherever it stands; real indices are distinct within a row (not checked: pfz_dense_rescore_topn's contract).
+ * For every candidate j of row i: score(from[i], to[j]) under `scorer` -- the float64 value, bit for bit, that pfz_indel_argmax
+ * (ratio, 0..100, 100.0 for two empty strings), pfz_lev_argmax (Levenshtein / OSA, 0..1) and pfz_jaro_argmax (Jaro /
+ * Jaro-Winkler, 0..1) compute for that pair, on the raw strings as uploaded.  Every valid candidate is scored; nothing is pruned.
+ * out_idx / out_score: host buffers of from_strings->n * ntop entries, row-major: a row's candidates by (float64 score
+ * descending, to-index ascending) -- np.argsort(-scores, kind="stable")[:ntop] over the row's valid candidates taken in
+ * ascending index order --, the first ntop of them, then (-1, 0.0); ntop may exceed the candidates a row has.  The position of a
+ * candidate inside its row does not influence the result.  Any length and any alphabet: from-strings of up to 64 characters run
+ * in registers (Jaro: against candidates of up to 256 characters), everything else, and alphabets whose match table exceeds
+ * 60 KiB, in a general -- slow -- kernel.  The to-side preparation is pfz_indel_*'s, cached on the to-list's handle.
+ * PFZ_ERR_INVALID: a NULL argument, a scorer outside 0 .. 4, ntop < 1, fewer candidate rows than from-strings;
+ * PFZ_ERR_UNSUPPORTED: more than 1024 candidates per row, ntop > 64 (one list entry per lane of a wave, csrc/topn_wave.h).
+ * from_strings->n == 0: PFZ_OK, nothing is done.  Blocks. */
+#define PFZ_PAIR_RATIO 0
+#define PFZ_PAIR_LEVENSHTEIN 1
+#define PFZ_PAIR_OSA 2
+#define PFZ_PAIR_JARO 3
+#define PFZ_PAIR_JARO_WINKLER 4
+int pfz_pairs_rescore_topn(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings,
+                           const pfz_topn *candidates, int32_t scorer, int32_t ntop, int32_t *out_idx, double *out_score);
+
 /* ---- K5: dense cosine top-n -----------------------------------------------
  * Replaces cosine_similarity on dense embedding matrices
  * (reference _utils.py:74-77,95; Embeddings.match _embeddings.py:127-133):

@@ -99,6 +99,7 @@ SIGNATURES = {
     "pfz_lev_argmax_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp]),
     "pfz_lev_topn": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp]),
     "pfz_lev_matrix_host": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_vp]),
+    "pfz_pairs_rescore_topn": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
     "pfz_fuzz_extract_one": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "pfz_fuzz_extract_one_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "pfz_fuzz_plan_info": (ctypes.c_int, [c_vp, c_vp, P(c_i64), P(c_i64), P(c_i64), P(c_i64)]),
@@ -823,6 +824,25 @@ def lev_matrix(ctx, from_dev, to_dev, scorer, begin=0, end=None):
     out = np.empty((end - begin, to_dev.n), np.int32)
     check(ctx.lib.pfz_lev_matrix_host(ctx.h, from_dev.h, to_dev.h, LEV_SCORERS[scorer], int(begin), int(end), _ptr(out)))
     return out
+
+
+# scorer of K10 -> PFZ_PAIR_* (include/polyfuzz_hip.h)
+PAIR_SCORERS = {"ratio": 0, "levenshtein": 1, "osa": 2, "jaro": 3, "jaro_winkler": 4}
+PAIR_MAX_CANDIDATES = 1024             # candidates per from-row pfz_pairs_rescore_topn ranks
+PAIR_MAX_TOP_N = 64                    # one list entry per lane of a wave (csrc/topn_wave.h)
+
+
+def pairs_rescore_topn(ctx, from_dev, to_dev, candidates, scorer, ntop):
+    """K10: the candidates of every from-string -- row i of the DeviceTopN `candidates`: indices into to_dev, anything outside
+    [0, n_to) skipped -- scored under `scorer` (a PAIR_SCORERS name, or its id) and re-ranked: (index int32[n, ntop], score
+    float64[n, ntop]) in the order (score descending, to-index ascending); -1 / 0.0 beyond the candidates a row has.  The table
+    stays on the device.  ntop <= 64 and <= 1024 candidates per row (PfzUnsupported beyond)."""
+    n = from_dev.n
+    idx = np.empty((n, max(int(ntop), 0)), np.int32)           # (ntop < 1 is the library's to refuse)
+    score = np.empty((n, max(int(ntop), 0)), np.float64)
+    sid = PAIR_SCORERS[scorer] if isinstance(scorer, str) else int(scorer)
+    check(ctx.lib.pfz_pairs_rescore_topn(ctx.h, from_dev.h, to_dev.h, candidates.h, sid, int(ntop), _ptr(idx), _ptr(score)))
+    return idx, score
 
 
 # compute_dtype of the dense path -> PFZ_DENSE_* (include/polyfuzz_hip.h)

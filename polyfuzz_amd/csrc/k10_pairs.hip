@@ -1,0 +1,460 @@
+// K10 -- a GIVEN list of pairs under an edit-distance scorer: per from-string the candidates of a device-resident table are scored
+// and re-ranked (pfz_pairs_rescore_topn).
+//
+// Extends the hot loop of EditDistance._calculate_edit_distance, reference polyfuzz/models/_distance.py:89-102 -- scorer(from, to)
+// for every to-string, then the best -- restricted to the candidates a cheap matcher left (the top_n table of
+// polyfuzz/models/_utils.py:82-91): blocking, then exact scoring of the few.  The scorers are K4's ratio, K9's Levenshtein / OSA
+// and K8's Jaro / Jaro-Winkler; a pair's float64 score comes from the very functions those kernels call (k10_core.h ratio_of,
+// k9_core.h, k8_core.h), so it has the bits the all-pairs kernels produce for that pair.
+//
+// Mapping to CDNA4
+//   workgroup = ONE wave = one from-string at a time: its match table PM[symbol] (bit i: a[i] == symbol) lives in LDS, set for the
+//     row's characters and cleared by the positions it set, as in K8 / K9.  A table per wave is what makes the waves independent:
+//     a row's work is m candidates, far too little for four waves to share;
+//   lane = one candidate, taken in chunks of 64 in the order they stand in the row.  The candidates are wherever the blocking put
+//     them, not in the K4 plan's length-sorted groups, so a lane gathers its to-string's code units (1 or 4 bytes) from the raw
+//     pfz_strings buffers and maps them through the plan's code unit -> symbol table (`lut`, cached on the to-handle); the lanes
+//     of a chunk walk strings of different lengths and the wave waits for its longest;
+//   the wave keeps the row's list with topn_wave.h -- one entry per lane, hence ntop <= 64 -- and writes the row's result itself:
+//     (float64 score descending, to-index ascending), then (-1, 0.0).  The keys of a row are distinct (distinct indices), so the
+//     order in which the chunks offer them does not show in the result.
+// Every valid candidate is scored: no bound, no pruning -- the table is short.
+// Register kernels: from-strings of up to 32 characters in 32-bit words, of up to 64 in 64-bit words; the to-string is a stream of
+// any length for ratio / Levenshtein / OSA.  Jaro keeps a to-string's flag words in registers with compile-time indices (256
+// positions, as K8); a row that holds a longer candidate is handed to the general kernel whole (a byte per row says so, written
+// here, read there -- the table is never looked at on the host).
+// General kernel: longer from-strings, those Jaro rows, and every row when the match table exceeds 60 KiB of LDS -- words and match
+// table in global memory, any length, any alphabet, slow.
+// Bound: integer VALU + LDS look-ups behind a dependent chain of gathered loads (code unit -> lut -> PM) per to-character
+// (measured beside the all-pairs kernels).
+#include "k10_core.h"
+#include "k4_plan.h"
+#include "k8_core.h"
+#include "k9_core.h"
+#include "topn_wave.h"
+
+#include <algorithm>
+#include <limits.h>
+
+namespace pfz {
+
+constexpr int kPairsMaxCandidates = 1024;      // per row, as pfz_dense_rescore_topn
+constexpr int kPairsJaroRegLen = 256;          // to-positions whose flags the Jaro register kernel keeps
+
+enum { PAIR_RATIO = 0, PAIR_LEVENSHTEIN = 1, PAIR_OSA = 2, PAIR_JARO = 3, PAIR_JARO_WINKLER = 4 };
+enum { MODE_REG32 = 0, MODE_REG64 = 1, MODE_GENERAL = 2 };
+
+struct PairArgs {
+    const void *a_chars;       // from-strings: code units of a_width bytes
+    int32_t a_width;
+    const int64_t *a_off;      // [n_from + 1]
+    const void *b_chars;       // to-strings, the raw list
+    int32_t b_width;
+    const int64_t *b_off;      // [n_to + 1]
+    int64_t n_to;
+    const uint16_t *lut;       // code unit -> symbol rank (0 = not in the to-list's alphabet), lut_len entries
+    uint32_t lut_len;
+    int32_t n_sym1;            // alphabet size + 1 (symbol 0: an empty table entry)
+    const int32_t *cand;       // [>= n_from][m] candidate to-indices; anything outside [0, n_to) is skipped
+    int32_t m;
+    const int32_t *rows;       // the from-rows of this launch (register kernels)
+    int32_t n_rows;
+    uint8_t *mode;             // [n_from] MODE_*: the general kernel serves the rows marked MODE_GENERAL
+    int32_t scorer;            // PAIR_*
+    int32_t ntop;
+    int32_t *out_idx;          // [n_from][ntop]
+    double *out_score;
+};
+
+__device__ inline int pair_symbol(const void *chars, int width, int64_t at, const PairArgs &A)
+{
+    const uint32_t c = width == 1 ? (uint32_t)((const uint8_t *)chars)[at] : ((const uint32_t *)chars)[at];
+    return c < A.lut_len ? (int)A.lut[c] : 0;
+}
+
+__device__ inline void pair_lds_or(uint32_t *p, uint32_t v) { atomicOr(p, v); }
+__device__ inline void pair_lds_or(uint64_t *p, uint64_t v) { atomicOr((unsigned long long *)p, (unsigned long long)v); }
+
+// lane k of the chunk at c0: its candidate's to-index, or -1 (no candidate: beyond the row, an empty slot, outside the to-list)
+__device__ inline int pair_candidate(const PairArgs &A, int64_t row, int c0)
+{
+    const int k = c0 + (int)(threadIdx.x & 63);
+    const int j = k < A.m ? A.cand[row * A.m + k] : -1;
+    return j >= 0 && (int64_t)j < A.n_to ? j : -1;
+}
+
+__device__ inline void pair_store_row(const PairArgs &A, int64_t row, const TopnList &l)
+{
+    const int lane = threadIdx.x & 63;
+    if (lane < A.ntop) {
+        A.out_idx[row * A.ntop + lane] = l.idx == INT_MAX ? -1 : l.idx;
+        A.out_score[row * A.ntop + lane] = l.idx == INT_MAX ? 0.0 : l.score;
+    }
+}
+
+// one pair in registers: the from-string is in the wave's match table `pm`, the lane walks its to-string [b0, b0 + lb)
+template <typename WORD, int FAMILY>      // FAMILY: PAIR_RATIO, PAIR_LEVENSHTEIN, PAIR_OSA, PAIR_JARO (Winkler: A.scorer)
+__device__ __forceinline__ double pair_score_reg(const PairArgs &A, const WORD *pm, int la, int64_t b0, int lb)
+{
+    if constexpr (FAMILY == PAIR_RATIO) {
+        WORD v = (WORD)~(WORD)0;
+        for (int t = 0; t < lb; ++t) lcs_step_reg<WORD>(v, pm[pair_symbol(A.b_chars, A.b_width, b0 + t, A)]);
+        const int lcs = __popcll((uint64_t)(WORD)~v);
+        return la + lb == 0 ? 100.0 : ratio_of(lcs, (int64_t)la + lb);
+    }
+    else if constexpr (FAMILY == PAIR_LEVENSHTEIN || FAMILY == PAIR_OSA) {
+        LevState<WORD> s;
+        lev_begin(s, la);
+        for (int t = 0; t < lb; ++t) lev_step<WORD, FAMILY == PAIR_OSA>(s, pm[pair_symbol(A.b_chars, A.b_width, b0 + t, A)], true);
+        return lev_similarity(lev_distance(s.dist, la, lb), la, lb);
+    }
+    else {
+        constexpr int WB = (int)sizeof(WORD) * 8;
+        constexpr int NB = kPairsJaroRegLen / WB;      // lb <= 256: the caller's promise
+        JaroFlags<WORD> s;
+        WORD fb[NB];
+        jaro_begin(s, jaro_range(la, lb));
+#pragma unroll
+        for (int k = 0; k < NB; ++k) {
+            s.fb = 0;
+            const int hi = min(lb, (k + 1) * WB);
+            for (int j = k * WB; j < hi; ++j) jaro_match<WORD>(s, pm[pair_symbol(A.b_chars, A.b_width, b0 + j, A)], j, j - k * WB);
+            fb[k] = s.fb;
+        }
+        const int m = __popcll((uint64_t)s.fa);
+        const int prefix = jaro_prefix(s.pre);
+        int half_t = 0;
+        if (m >= 2) {          // (one flagged pair cannot be out of order)
+#pragma unroll
+            for (int k = 0; k < NB; ++k) {
+                s.fb = fb[k];
+                const int hi = min(lb, (k + 1) * WB);
+                for (int j = k * WB; j < hi; ++j)
+                    half_t += jaro_transpose<WORD>(s, pm[pair_symbol(A.b_chars, A.b_width, b0 + j, A)], j - k * WB);
+            }
+        }
+        return jaro_score(m, half_t, la, lb, prefix, A.scorer == PAIR_JARO_WINKLER);
+    }
+}
+
+// WORD: uint32_t (from-strings of <= 32 characters) or uint64_t (<= 64).  One wave per workgroup.
+template <typename WORD, int FAMILY>
+__global__ __launch_bounds__(64) void k10_pairs_kernel(PairArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    WORD *pm = (WORD *)smem_raw;
+    const int lane = threadIdx.x;
+
+    for (int p = lane; p < A.n_sym1; p += 64) pm[p] = 0;
+    __syncthreads();
+
+    for (int r = blockIdx.x; r < A.n_rows; r += gridDim.x) {
+        const int64_t row = A.rows[r];
+        if constexpr (FAMILY == PAIR_JARO) {
+            // a candidate of more than 256 characters: the row is the general kernel's
+            bool longer = false;
+            for (int c0 = 0; c0 < A.m; c0 += 64) {
+                const int j = pair_candidate(A, row, c0);
+                longer |= j >= 0 && A.b_off[j + 1] - A.b_off[j] > kPairsJaroRegLen;
+            }
+            if (__any(longer)) {
+                if (lane == 0) A.mode[row] = MODE_GENERAL;
+                continue;
+            }
+        }
+        const int64_t a0 = A.a_off[row];
+        const int la = (int)(A.a_off[row + 1] - a0);      // fits the WORD
+        const int my_sym = lane < la ? pair_symbol(A.a_chars, A.a_width, a0 + lane, A) : 0;
+        if (my_sym) pair_lds_or(&pm[my_sym], (WORD)1 << lane);
+        __syncthreads();
+
+        TopnList list = topn_empty();
+        for (int c0 = 0; c0 < A.m; c0 += 64) {
+            const int j = pair_candidate(A, row, c0);
+            const int64_t b0 = j >= 0 ? A.b_off[j] : 0;
+            const int lb = j >= 0 ? (int)(A.b_off[j + 1] - b0) : 0;
+            double sc = 0.0;
+            if (j >= 0) sc = pair_score_reg<WORD, FAMILY>(A, pm, la, b0, lb);
+            topn_insert(list, A.ntop, j >= 0, sc, j);      // (all 64 lanes: the loop and its bounds are the wave's)
+        }
+        pair_store_row(A, row, list);
+        if (my_sym) pm[my_sym] = 0;      // clear the entries of this from-string
+        __syncthreads();
+    }
+}
+
+// one pair of the general kernel: the from-string's match table `pm` (WA words per symbol, W of them in use) and this lane's words
+// s0 / s1 / s2[w * 64] are in global memory
+__device__ __forceinline__ double pair_score_general(const PairArgs &A, const uint64_t *pm, uint64_t *s0, uint64_t *s1, uint64_t *s2,
+                                                     int WA, int W, int la, int64_t b0, int lb)
+{
+    if (A.scorer == PAIR_RATIO) {
+        for (int w = 0; w < W; ++w) s0[(int64_t)w * 64] = ~0ull;
+        for (int t = 0; t < lb; ++t) {
+            const uint64_t *pmc = pm + (int64_t)pair_symbol(A.b_chars, A.b_width, b0 + t, A) * WA;
+            uint64_t carry = 0;
+            for (int w = 0; w < W; ++w) {
+                uint64_t v = s0[(int64_t)w * 64];
+                lcs_step_word(v, pmc[w], carry);
+                s0[(int64_t)w * 64] = v;
+            }
+        }
+        int lcs = 0;
+        for (int w = 0; w < W; ++w) lcs += __popcll(~s0[(int64_t)w * 64]);
+        return la + lb == 0 ? 100.0 : ratio_of(lcs, (int64_t)la + lb);
+    }
+    if (A.scorer == PAIR_LEVENSHTEIN || A.scorer == PAIR_OSA) {
+        // s0 / s1 / s2: VP / VN / the previous step's D0
+        const bool osa = A.scorer == PAIR_OSA;
+        for (int w = 0; w < W; ++w) {
+            s0[(int64_t)w * 64] = low_ones<uint64_t>(la - 64 * w);
+            s1[(int64_t)w * 64] = 0ull;
+            s2[(int64_t)w * 64] = 0ull;
+        }
+        const uint64_t last = la > 0 ? 1ull << ((la - 1) % 64) : 0ull;
+        int dist = la;
+        int c_prev = 0;                                         // (symbol 0: an empty table entry)
+        for (int t = 0; t < lb; ++t) {
+            const int c = pair_symbol(A.b_chars, A.b_width, b0 + t, A);
+            const uint64_t *eq = pm + (int64_t)c * WA, *eq_prev = pm + (int64_t)c_prev * WA;
+            LevCarry cy = lev_carry_begin();
+            uint64_t hp = 0, hn = 0;
+            for (int w = 0; w < W; ++w) {
+                uint64_t x_vp = s0[(int64_t)w * 64], x_vn = s1[(int64_t)w * 64], x_d0 = osa ? s2[(int64_t)w * 64] : 0ull;
+                if (osa) lev_step_word<true>(x_vp, x_vn, x_d0, eq[w], eq_prev[w], cy, &hp, &hn);
+                else lev_step_word<false>(x_vp, x_vn, x_d0, eq[w], 0ull, cy, &hp, &hn);
+                s0[(int64_t)w * 64] = x_vp;
+                s1[(int64_t)w * 64] = x_vn;
+                if (osa) s2[(int64_t)w * 64] = x_d0;
+            }
+            dist += (int)((hp & last) != 0) - (int)((hn & last) != 0);
+            c_prev = c;
+        }
+        return lev_similarity(lev_distance(dist, la, lb), la, lb);
+    }
+    // Jaro.  s0: the flagged from-positions (W words), s1: the flagged to-positions ((lb + 63) / 64 words <= WS)
+    const int WBl = lb > 0 ? (lb + 63) / 64 : 1;
+    const int range = jaro_range(la, lb);
+    for (int w = 0; w < W; ++w) s0[(int64_t)w * 64] = 0ull;
+    for (int w = 0; w < WBl; ++w) s1[(int64_t)w * 64] = 0ull;
+    int m = 0;
+    uint32_t pre = 0;
+    for (int t = 0; t < lb; ++t) {
+        const uint64_t *pmc = pm + (int64_t)pair_symbol(A.b_chars, A.b_width, b0 + t, A) * WA;
+        if (t < 4) pre |= (uint32_t)((pmc[0] >> t) & 1) << t;
+        const int lo = max(t - range, 0), hi = min(t + range, la - 1);
+        for (int w = lo >> 6; w <= hi >> 6 && lo <= hi; ++w) {
+            const uint64_t f = s0[(int64_t)w * 64];
+            const uint64_t x = pmc[w] & bit_span<uint64_t>(max(lo - 64 * w, 0), min(hi - 64 * w, 63)) & ~f;
+            if (x) {
+                s0[(int64_t)w * 64] = f | (x & (0 - x));
+                s1[(int64_t)(t >> 6) * 64] |= 1ull << (t & 63);
+                ++m;
+                break;
+            }
+        }
+    }
+    int half_t = 0;
+    if (m >= 2) {
+        int wa = 0;
+        uint64_t cur = s0[0];
+        for (int t = 0; t < lb; ++t) {
+            if (!((s1[(int64_t)(t >> 6) * 64] >> (t & 63)) & 1)) continue;
+            while (cur == 0 && wa + 1 < W) cur = s0[(int64_t)(++wa) * 64];      // (as many flags on either side)
+            const uint64_t low = cur & (0 - cur);
+            cur ^= low;
+            half_t += !(pm[(int64_t)pair_symbol(A.b_chars, A.b_width, b0 + t, A) * WA + wa] & low);
+        }
+    }
+    return jaro_score(m, half_t, la, lb, jaro_prefix(pre), A.scorer == PAIR_JARO_WINKLER);
+}
+
+// The general case: any lengths, any alphabet.  One wave per workgroup and from-string; the match table of the from-string (WA
+// words per symbol) and every lane's words -- s0 / s1 / s2[(block * WS + w) * 64 + lane], WS words each: V for ratio, VP / VN / D0
+// for Levenshtein / OSA, the from-flags and the to-flags for Jaro -- are in global memory.  Serves the rows marked MODE_GENERAL.
+__global__ __launch_bounds__(64) void k10_pairs_general_kernel(PairArgs A, int32_t WA, int32_t WS, uint64_t *__restrict__ pm_all,
+                                                              uint64_t *__restrict__ s0_all, uint64_t *__restrict__ s1_all,
+                                                              uint64_t *__restrict__ s2_all)
+{
+    const int lane = threadIdx.x;
+    uint64_t *pm = pm_all + (int64_t)blockIdx.x * A.n_sym1 * WA;      // zero on entry, zero again after every row
+    uint64_t *s0 = s0_all + (int64_t)blockIdx.x * WS * 64 + lane;     // s0[w * 64]: this lane's word w
+    uint64_t *s1 = s1_all + (int64_t)blockIdx.x * WS * 64 + lane;
+    uint64_t *s2 = s2_all + (int64_t)blockIdx.x * WS * 64 + lane;
+    for (int64_t row = blockIdx.x; row < A.n_rows; row += gridDim.x) {
+        if (A.mode[row] != MODE_GENERAL) continue;
+        const int64_t a0 = A.a_off[row];
+        const int la = (int)(A.a_off[row + 1] - a0);
+        const int W = la > 0 ? (la + 63) / 64 : 1;                    // <= WA
+        for (int p = lane; p < la; p += 64) {
+            const int sy = pair_symbol(A.a_chars, A.a_width, a0 + p, A);
+            if (sy) atomicOr((unsigned long long *)&pm[(int64_t)sy * WA + p / 64], 1ull << (p % 64));
+        }
+        __threadfence_block();
+        __syncthreads();
+
+        TopnList list = topn_empty();
+        for (int c0 = 0; c0 < A.m; c0 += 64) {
+            const int j = pair_candidate(A, row, c0);
+            const int64_t b0 = j >= 0 ? A.b_off[j] : 0;
+            const int lb = j >= 0 ? (int)(A.b_off[j + 1] - b0) : 0;
+            double sc = 0.0;
+            if (j >= 0) sc = pair_score_general(A, pm, s0, s1, s2, WA, W, la, b0, lb);
+            topn_insert(list, A.ntop, j >= 0, sc, j);      // (all 64 lanes: the loop and its bounds are the wave's)
+        }
+        pair_store_row(A, row, list);
+        for (int p = lane; p < la; p += 64) {
+            const int sy = pair_symbol(A.a_chars, A.a_width, a0 + p, A);
+            if (sy) pm[(int64_t)sy * WA + p / 64] = 0ull;
+        }
+        __threadfence_block();
+        __syncthreads();
+    }
+}
+
+template <typename WORD> static void launch_pairs_reg(const PairArgs &A, dim3 grid, size_t lds, hipStream_t st)
+{
+    switch (A.scorer) {
+    case PAIR_RATIO: hipLaunchKernelGGL((k10_pairs_kernel<WORD, PAIR_RATIO>), grid, dim3(64), lds, st, A); break;
+    case PAIR_LEVENSHTEIN: hipLaunchKernelGGL((k10_pairs_kernel<WORD, PAIR_LEVENSHTEIN>), grid, dim3(64), lds, st, A); break;
+    case PAIR_OSA: hipLaunchKernelGGL((k10_pairs_kernel<WORD, PAIR_OSA>), grid, dim3(64), lds, st, A); break;
+    default: hipLaunchKernelGGL((k10_pairs_kernel<WORD, PAIR_JARO>), grid, dim3(64), lds, st, A); break;
+    }
+}
+
+static int pairs_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, const pfz_topn *C, int32_t scorer, int32_t ntop,
+                     int32_t *out_idx, double *out_score)
+{
+    const int64_t n_from = F->n;
+    const size_t n_out = (size_t)n_from * (size_t)ntop;
+    if (T->n == 0 || C->ntop == 0) {      // no candidate can be valid
+        std::fill(out_idx, out_idx + n_out, -1);
+        std::fill(out_score, out_score + n_out, 0.0);
+        return PFZ_OK;
+    }
+    PFZ_HIP(hipSetDevice(ctx->device));
+    if (T->n >= INT_MAX - 64 || F->n >= INT_MAX || T->max_len >= INT_MAX / 2 || F->max_len >= INT_MAX / 2) {
+        set_error("pfz_pairs_rescore_topn: list or string too long");
+        return PFZ_ERR_UNSUPPORTED;
+    }
+    const pfz_indel_plan *pl;
+    PFZ_TRY(indel_plan_get(ctx, T, &pl));      // (its code unit -> symbol table; the packed groups are not read here)
+
+    const bool jaro = scorer == PAIR_JARO || scorer == PAIR_JARO_WINKLER;
+    const bool lds_fits = (size_t)(pl->n_sym + 1) * sizeof(uint64_t) <= 60 * 1024;
+    std::vector<uint8_t> mode((size_t)n_from);
+    std::vector<int32_t> rows_cls[2];
+    int64_t n_general = 0, longest = 1;
+    for (int64_t i = 0; i < n_from; ++i) {
+        const int64_t la = F->h_off[(size_t)i + 1] - F->h_off[(size_t)i];
+        const int cls = !lds_fits || la > 64 ? MODE_GENERAL : (la > 32 ? MODE_REG64 : MODE_REG32);
+        mode[(size_t)i] = (uint8_t)cls;
+        if (cls == MODE_GENERAL) {
+            ++n_general;
+            longest = std::max(longest, la);
+        }
+        else rows_cls[cls].push_back((int32_t)i);
+    }
+    // (the Jaro register kernels hand a row with a candidate of more than 256 characters on: only a to-list that has one)
+    const bool general = n_general > 0 || (jaro && T->max_len > kPairsJaroRegLen);
+
+    DevBuf d_mode, d_rows[2], d_oidx, d_oscore, d_pm, d_s0, d_s1, d_s2;
+    PFZ_TRY(d_mode.upload(ctx, mode));
+    PFZ_TRY(d_oidx.alloc(ctx, n_out * sizeof(int32_t)));
+    PFZ_TRY(d_oscore.alloc(ctx, n_out * sizeof(double)));
+
+    PairArgs A;
+    A.a_chars = F->chars;
+    A.a_width = F->char_width;
+    A.a_off = F->offsets;
+    A.b_chars = T->chars;
+    A.b_width = T->char_width;
+    A.b_off = T->offsets;
+    A.n_to = T->n;
+    A.lut = pl->lut;
+    A.lut_len = pl->lut_len;
+    A.n_sym1 = pl->n_sym + 1;
+    A.cand = C->idx;
+    A.m = C->ntop;
+    A.rows = nullptr;
+    A.n_rows = 0;
+    A.mode = d_mode.as<uint8_t>();
+    A.scorer = scorer;
+    A.ntop = ntop;
+    A.out_idx = d_oidx.as<int32_t>();
+    A.out_score = d_oscore.as<double>();
+
+    // one wave per workgroup: up to 32 of them per compute unit, the rows dealt round robin
+    const int64_t max_grid = (int64_t)ctx->prop.multiProcessorCount * 32;
+    {
+        ProfScope ps_all(ctx, "k10_pairs");
+        for (int c = 0; c < 2; ++c) {
+            if (rows_cls[c].empty()) continue;
+            PFZ_TRY(d_rows[c].upload(ctx, rows_cls[c]));
+            A.rows = d_rows[c].as<int32_t>();
+            A.n_rows = (int32_t)rows_cls[c].size();
+            const dim3 grid((unsigned)std::min<int64_t>(A.n_rows, max_grid));
+            const size_t lds = (size_t)A.n_sym1 * (c == 1 ? sizeof(uint64_t) : sizeof(uint32_t));
+            if (c == 0) launch_pairs_reg<uint32_t>(A, grid, lds, ctx->stream);
+            else launch_pairs_reg<uint64_t>(A, grid, lds, ctx->stream);
+            PFZ_HIP(hipGetLastError());
+        }
+        if (general) {
+            A.rows = nullptr;
+            A.n_rows = (int32_t)n_from;
+            const int32_t WA = (int32_t)((longest + 63) / 64);
+            const int32_t WS = jaro ? (int32_t)std::max<int64_t>(WA, (T->max_len + 63) / 64) : WA;
+            int64_t grid = std::min<int64_t>(n_general > 0 && !jaro ? n_general : n_from, max_grid);
+            const size_t pm_per = (size_t)A.n_sym1 * (size_t)WA * sizeof(uint64_t);
+            while (grid > 1 && pm_per * (size_t)grid > ((size_t)2 << 30)) grid /= 2;      // <= 2 GiB of match tables
+            if (pm_per * (size_t)grid > ((size_t)8 << 30)) {
+                set_error("pfz_pairs_rescore_topn: a from-string of %lld characters with %d alphabet symbols needs a %zu-byte match table",
+                          (long long)longest, pl->n_sym, pm_per);
+                return PFZ_ERR_UNSUPPORTED;
+            }
+            ProfScope ps(ctx, "k10_pairs_general");
+            const size_t st_bytes = (size_t)grid * (size_t)WS * 64 * sizeof(uint64_t);
+            PFZ_TRY(d_pm.alloc(ctx, pm_per * (size_t)grid));
+            PFZ_TRY(d_s0.alloc(ctx, st_bytes));
+            PFZ_TRY(d_s1.alloc(ctx, st_bytes));
+            PFZ_TRY(d_s2.alloc(ctx, st_bytes));
+            PFZ_HIP(hipMemsetAsync(d_pm.p, 0, pm_per * (size_t)grid, ctx->stream));
+            hipLaunchKernelGGL(k10_pairs_general_kernel, dim3((unsigned)grid), dim3(64), 0, ctx->stream, A, WA, WS, d_pm.as<uint64_t>(),
+                               d_s0.as<uint64_t>(), d_s1.as<uint64_t>(), d_s2.as<uint64_t>());
+            PFZ_HIP(hipGetLastError());
+        }
+    }
+    PFZ_TRY(copy_d2h(ctx, out_idx, d_oidx.p, n_out * sizeof(int32_t)));
+    PFZ_TRY(copy_d2h(ctx, out_score, d_oscore.p, n_out * sizeof(double)));
+    PFZ_HIP(hipStreamSynchronize(ctx->stream));
+    return PFZ_OK;
+}
+
+}  // namespace pfz
+
+using namespace pfz;
+
+extern "C" {
+
+int pfz_pairs_rescore_topn(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings, const pfz_topn *candidates,
+                           int32_t scorer, int32_t ntop, int32_t *out_idx, double *out_score)
+{
+    PFZ_REQUIRE(ctx && from_strings && to_strings && candidates, "pfz_pairs_rescore_topn: NULL argument");
+    PFZ_REQUIRE(scorer >= PAIR_RATIO && scorer <= PAIR_JARO_WINKLER, "pfz_pairs_rescore_topn: scorer %d is outside 0 .. 4", scorer);
+    PFZ_REQUIRE(ntop >= 1, "pfz_pairs_rescore_topn: ntop %d < 1", ntop);
+    PFZ_REQUIRE(candidates->n_rows >= from_strings->n, "pfz_pairs_rescore_topn: the candidate table has %lld rows, the from-list %lld",
+                (long long)candidates->n_rows, (long long)from_strings->n);
+    if (ntop > kTopnMax) {
+        set_error("pfz_pairs_rescore_topn: ntop %d exceeds the limit of %d (one list entry per lane of a wave)", ntop, kTopnMax);
+        return PFZ_ERR_UNSUPPORTED;
+    }
+    if (candidates->ntop > kPairsMaxCandidates) {
+        set_error("pfz_pairs_rescore_topn: %d candidates per row exceed the limit of %d", candidates->ntop, kPairsMaxCandidates);
+        return PFZ_ERR_UNSUPPORTED;
+    }
+    if (from_strings->n == 0) return PFZ_OK;
+    PFZ_REQUIRE(out_idx && out_score, "pfz_pairs_rescore_topn: NULL output");
+    return pairs_run(ctx, from_strings, to_strings, candidates, scorer, ntop, out_idx, out_score);
+}
+
+}  // extern "C"

@@ -35,6 +35,7 @@
 // quad / octo kernels keep their bests in registers per from-string and have no top-n form.  Every pair is scored.
 // Roofline: integer VALU + LDS lookups; HBM traffic is the to-strings once per
 // from-string out of L2 (0.3 MB) -- not HBM-bound.
+#include "k10_core.h"      // ratio_of: the float64 formula, shared with K10
 #include "k4_plan.h"
 #include "topn_wave.h"
 
@@ -139,14 +140,6 @@ __device__ inline void wave_best(Best &b)
         const int ol = __shfl_xor(b.lcs, d, 64), om = __shfl_xor(b.mx, d, 64), oi = __shfl_xor(b.idx, d, 64);
         if (oi != INT_MAX) take(b, ol, om, oi);
     }
-}
-
-// rapidfuzz: norm_dist = dist / maximum (0 when both empty); ratio = (1 - norm_dist) * 100
-__device__ inline double ratio_of(int lcs, int64_t maximum)
-{
-    const int64_t dist = maximum - 2 * (int64_t)lcs;
-    const double norm_dist = maximum != 0 ? (double)dist / (double)maximum : 0.0;
-    return (1.0 - norm_dist) * 100.0;
 }
 
 // TOPN: a list of A.ntop per wave in place of a best per lane

@@ -4,5 +4,6 @@ from ._tfidf import TFIDF
 from ._distance import EditDistance
 from ._rapidfuzz import RapidFuzz
 from ._embeddings import Embeddings
+from ._blocked import BlockedEditDistance
 
-__all__ = ["BaseMatcher", "cosine_similarity", "TFIDF", "EditDistance", "RapidFuzz", "Embeddings"]
+__all__ = ["BaseMatcher", "cosine_similarity", "TFIDF", "EditDistance", "RapidFuzz", "Embeddings", "BlockedEditDistance"]
