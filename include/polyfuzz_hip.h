@@ -83,7 +83,9 @@ int pfz_prof_reset(pfz_ctx *ctx);
  * K8: `k8_jaro` (every launch of a call), `k8_jaro_general` (its general-kernel launches), `k8_pairs_scored` (0 ms; the
  * count is the number of pairs whose float64 score was computed).
  * K9: `k9_lev` (every launch of a call), `k9_lev_general` (its general-kernel launches), `k9_pairs_walked` (0 ms; the count is
- * the number of pairs whose recurrence was walked -- the others fell to the length bound). */
+ * the number of pairs whose recurrence was walked -- the others fell to the length bound).
+ * K11: `k11_join` (the walk of a call), `k11_join_general` (its general-kernel launch), `k11_sort_unpack` (the hits sorted and
+ * turned into CSR). */
 int pfz_prof_get(pfz_ctx *ctx, const char *name, double *total_ms, int64_t *launches);
 
 /* ---- CSR matrices --------------------------------------------------------
@@ -393,6 +395,32 @@ int pfz_lev_topn(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_string
  * entry point; every pair is walked).  The similarity follows in one IEEE division and subtraction.  Blocks. */
 int pfz_lev_matrix_host(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings, int32_t scorer,
                         int64_t from_begin, int64_t from_end, int32_t *out_matrix);
+
+/* ---- K11: all pairs at or above a Levenshtein / OSA similarity -----------------
+ * The threshold form of K9, what deduplication and record linkage ask of the scores of the reference's loop
+ * (polyfuzz/models/_distance.py:89-102; TFIDF has it as min_similarity, polyfuzz/models/_tfidf.py): every pair
+ * (from i, to j) with sim(i, j) >= min_similarity, sim and d as defined for K9 (scorer = 0: Levenshtein, 1: OSA), float64
+ * against float64 -- rapidfuzz's score_cutoff convention: equal is a hit, below is a miss.
+ * to_strings == NULL, or the from-list's own handle: the self-join.  Every unordered pair i < j is reported once, as row i,
+ * to-index j; never (i, i); equal strings at different positions are pairs.
+ * Output, host buffers: CSR over the from-rows.  out_row_ptr int64[n_from + 1]; hit p of row i, out_row_ptr[i] <= p <
+ * out_row_ptr[i + 1]: out_idx[p] the to-index (ascending within a row), out_dist[p] = d, out_sim[p] = sim.  The same call
+ * gives the same bytes every time.
+ * capacity: the hits out_idx / out_dist / out_sim have room for (they may be NULL when it is 0).  *out_total is always the
+ * exact number of hits.  When it exceeds `capacity` the call still returns PFZ_OK, has written NONE of the four output arrays
+ * (the device never writes a hit past the capacity either) and is to be repeated with capacity >= *out_total.
+ * out_counters: NULL, or int64[3] of work counts -- [0] pairs inside the length window (pairs of the call, in a self-join
+ * the unordered ones, whose lengths alone do not put them below min_similarity), [1] those of them walked to their end, not
+ * abandoned, [2] recurrence steps (to-characters) lanes took for pairs still alive.
+ * Exact: a pair is left unwalked or abandoned only where K9's formula, applied to a lower bound of d -- ||a| - |b||, or the
+ * column's bottom cell less the to-characters still to come --, is < min_similarity (csrc/k11_core.h).
+ * From-strings of up to 64 characters run in registers; longer ones (and alphabets whose match table exceeds 60 KiB) in a
+ * general -- slow -- kernel.  The to-side preparation is pfz_indel_*'s, cached on the to-list's handle.
+ * Limits of the packed hit (PFZ_ERR_UNSUPPORTED beyond): lists of at most 2^24 strings, strings of at most 65 535
+ * characters.  scorer outside {0, 1}, a NaN min_similarity or one outside [0, 1], capacity < 0: PFZ_ERR_INVALID.  Blocks. */
+int pfz_lev_join(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings, int32_t scorer,
+                 double min_similarity, int64_t capacity, int64_t *out_row_ptr, int32_t *out_idx, int32_t *out_dist,
+                 double *out_sim, int64_t *out_total, int64_t *out_counters);
 
 /* ---- K10: a candidate table rescored by edit distance ----------------------
  * Blocking, then exact scoring: extends the reference's edit-distance loop (polyfuzz/models/_distance.py:89-102: scorer(from, to)

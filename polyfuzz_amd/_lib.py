@@ -99,6 +99,7 @@ SIGNATURES = {
     "pfz_lev_argmax_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp]),
     "pfz_lev_topn": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp]),
     "pfz_lev_matrix_host": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_vp]),
+    "pfz_lev_join": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_f64, c_i64, c_vp, c_vp, c_vp, c_vp, P(c_i64), c_vp]),
     "pfz_pairs_rescore_topn": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
     "pfz_fuzz_extract_one": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "pfz_fuzz_extract_one_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
@@ -824,6 +825,34 @@ def lev_matrix(ctx, from_dev, to_dev, scorer, begin=0, end=None):
     out = np.empty((end - begin, to_dev.n), np.int32)
     check(ctx.lib.pfz_lev_matrix_host(ctx.h, from_dev.h, to_dev.h, LEV_SCORERS[scorer], int(begin), int(end), _ptr(out)))
     return out
+
+
+LEV_JOIN_COUNTERS = ("pairs_in_window", "pairs_finished", "steps")
+
+
+def lev_join(ctx, from_dev, to_dev, scorer, min_similarity, capacity=None, counters=False):
+    """K11: every pair with similarity >= min_similarity (float64 against float64, equal is a hit) as CSR over the from-rows --
+    (row_ptr int64[n + 1], to-index int32[hits] ascending within a row, distance int32[hits], similarity float64[hits]).
+    to_dev None (or from_dev itself): the self-join, every unordered pair once as (i, j), i < j.  capacity: the hits the first call's
+    buffers have room for (None: a modest guess, four per from-string); when the exact total the call returns exceeds it the
+    call is repeated ONCE with room for that total, never more often.  counters=True appends a dict of LEV_JOIN_COUNTERS (the
+    last call's)."""
+    work = np.zeros(3, np.int64) if counters else None
+    total = c_i64(0)
+    to_h = None if to_dev is None else to_dev.h
+    cap = max(4096, 4 * int(from_dev.n)) if capacity is None else int(capacity)
+    for _ in range(2):
+        row_ptr = np.empty(from_dev.n + 1, np.int64)
+        idx, dist, sim = np.empty(cap, np.int32), np.empty(cap, np.int32), np.empty(cap, np.float64)
+        check(ctx.lib.pfz_lev_join(ctx.h, from_dev.h, to_h, LEV_SCORERS[scorer], float(min_similarity), cap, _ptr(row_ptr), _ptr(idx),
+                                   _ptr(dist), _ptr(sim), ctypes.byref(total), _ptr(work)))
+        if total.value <= cap:
+            break
+        cap = total.value
+    assert total.value <= cap                     # (the second call had room for the exact total)
+    n = total.value
+    out = (row_ptr, idx[:n].copy(), dist[:n].copy(), sim[:n].copy())
+    return out + (dict(zip(LEV_JOIN_COUNTERS, work.tolist())),) if counters else out
 
 
 # scorer of K10 -> PFZ_PAIR_* (include/polyfuzz_hip.h)

@@ -92,6 +92,7 @@ def _device_scorer(scorer) -> str:
 # (K7) prune around a single best and keep their arg-max only
 _TOP_N_SCORERS = ("ratio", "QRatio", "token_sort_ratio", "levenshtein", "osa")
 _TOP_N_MAX = 64                 # one list entry per lane of a wave (csrc/topn_wave.h)
+_JOIN_SCORERS = ("levenshtein", "osa")      # the scorers with a threshold kernel (K11)
 
 
 def _top_n_choices(ctx, name, from_list, names, skip, self_match, to_dev, ntop):
@@ -168,6 +169,9 @@ class EditDistance(BaseMatcher):
     reference's clip, _utils.py:55-56); more than 64 after clipping raises _lib.PfzUnsupported; the Jaro scorers and the
     per-pair scorers (K7) raise NotImplementedError from `match` -- their kernels keep a single best.  An int >= 1, else
     ValueError; kept through pickling.
+
+    join (method, "levenshtein" and "osa"): every pair at least `min_similarity` similar instead of each string's best -- the
+    threshold form (K11), exact, with a self-join that reports each unordered pair once; see `join`.
     """
     def __init__(self,
                  n_jobs: int = 1,
@@ -248,6 +252,42 @@ class EditDistance(BaseMatcher):
             for r in range(ntop):
                 c = "Similarity" if r == 0 else f"Similarity_{r + 1}"
                 matches[c] = (matches[c] - lo) / (hi - lo)
+        self.last_timings = {"device": (t1 - t0) * 1e3, "frame": (time.perf_counter() - t1) * 1e3}
+        return matches
+
+    def join(self,
+             from_list: List[str],
+             to_list: List[str] = None,
+             min_similarity: float = 0.8) -> pd.DataFrame:
+        """ Every pair at least `min_similarity` similar (K11): the frame From, To, Similarity with one row per pair, ordered by
+        from-index, then to-index.  A from-string without a partner has no row.  Similarity is the scorer's own float64,
+        unrounded, and a pair is kept iff that float64 is >= min_similarity (rapidfuzz's score_cutoff: equal is kept).
+        Exact: every such pair is found, whatever their number.
+
+        `normalize` is NOT applied: a rescaled score no longer means the threshold.
+
+        to_list None: the self-join of from_list -- every unordered pair of positions i < j once, as From = from_list[i],
+        To = from_list[j]; never a string with itself, but equal strings at different positions are a pair.
+
+        Scorers "levenshtein" and "osa" only (NotImplementedError otherwise); min_similarity: a number in [0, 1]
+        (ValueError otherwise).  The frame has the columns single_linkage reads. """
+        if self._scorer_name not in _JOIN_SCORERS:
+            raise NotImplementedError(
+                f"EditDistance.join runs on the GPU for the scorers {_JOIN_SCORERS}; scorer {self._scorer_name!r} has no "
+                "threshold kernel")
+        if (isinstance(min_similarity, bool) or not isinstance(min_similarity, (int, float, np.integer, np.floating))
+                or not 0.0 <= float(min_similarity) <= 1.0):      # (NaN compares false)
+            raise ValueError(f"min_similarity must be a number in [0, 1], not {min_similarity!r}")
+        from ._rapidfuzz import upload_for
+        t0 = time.perf_counter()
+        ctx = _lib.Context.default()
+        names = from_list if to_list is None else to_list
+        f_dev = upload_for(ctx, self._scorer_name, from_list)
+        t_dev = None if to_list is None else upload_for(ctx, self._scorer_name, to_list)
+        row_ptr, idx, _, sim = _lib.lev_join(ctx, f_dev, t_dev, self._scorer_name, float(min_similarity))
+        t1 = time.perf_counter()
+        frm = np.repeat(np.arange(len(from_list), dtype=np.int32), np.diff(row_ptr))
+        matches = pd.DataFrame({"From": gather_column(from_list, frm), "To": gather_column(names, idx), "Similarity": sim}, copy=False)
         self.last_timings = {"device": (t1 - t0) * 1e3, "frame": (time.perf_counter() - t1) * 1e3}
         return matches
 
