@@ -85,7 +85,9 @@ int pfz_prof_reset(pfz_ctx *ctx);
  * K9: `k9_lev` (every launch of a call), `k9_lev_general` (its general-kernel launches), `k9_pairs_walked` (0 ms; the count is
  * the number of pairs whose recurrence was walked -- the others fell to the length bound).
  * K11: `k11_join` (the walk of a call), `k11_join_general` (its general-kernel launch), `k11_sort_unpack` (the hits sorted and
- * turned into CSR). */
+ * turned into CSR).
+ * K12: `k12_walk` (the walk of a call, hooks included), `k12_walk_general` (its general-kernel launch), `k12_flatten` (the
+ * forest turned into labels). */
 int pfz_prof_get(pfz_ctx *ctx, const char *name, double *total_ms, int64_t *launches);
 
 /* ---- CSR matrices --------------------------------------------------------
@@ -421,6 +423,30 @@ int pfz_lev_matrix_host(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz
 int pfz_lev_join(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings, int32_t scorer,
                  double min_similarity, int64_t capacity, int64_t *out_row_ptr, int32_t *out_idx, int32_t *out_dist,
                  double *out_sim, int64_t *out_total, int64_t *out_counters);
+
+/* ---- K12: connected components of "Levenshtein / OSA similarity >= t" ----------
+ * Near-duplicate clusters of ONE list: positions i and j share a component iff a chain of pairs, each with
+ * sim >= min_similarity (sim, d, scorer and the float64 comparison as for K11's self-join: equal is a hit), leads from i to j.
+ * "A ~ B and B ~ C put A, B and C together" -- which the reference's greedy single_linkage (polyfuzz/linkage.py:5-53) over a
+ * frame of pairs does not promise.  Equal strings always share a component (they score 1.0).
+ * The pairs are those of pfz_lev_join(ctx, strings, NULL, scorer, min_similarity, ...), found by the same walk, but none is
+ * stored: the lane that finds a hit unites the two positions in a lock-free union-find on the device (csrc/k12_core.h).
+ * Device memory is O(n) whatever the number of hits; there is no capacity and no repeat.
+ * out_label: host buffer int32[n]; out_label[i] = the SMALLEST position in i's component (so out_label[i] <= i, and
+ * out_label[i] == i exactly for the one representative of each component).  Deterministic: the same call gives the same bytes
+ * every time, whatever order the device's atomics took.
+ * *out_pairs: the number of hits, == pfz_lev_join's *out_total for the same arguments.  *out_components: the number of
+ * components (singletons included).  out_counters: NULL, or int64[3] with pfz_lev_join's meaning and, for the same call, its
+ * values.
+ * strings->n == 0: PFZ_OK, *out_pairs = *out_components = 0, nothing else is written (out_label may be NULL).
+ * Limits: K11's packed-hit limits do not apply.  Positions and lengths are 32-bit: more than 2^31 - 65 strings, or a string
+ * of 2^31 - 1 characters or more, is PFZ_ERR_UNSUPPORTED, as is a string beyond 64 characters whose match table in the general
+ * kernel would exceed 8 GiB.  scorer outside {0, 1}, a NaN min_similarity or one outside [0, 1], a NULL out_pairs /
+ * out_components: PFZ_ERR_INVALID.
+ * From-strings of up to 64 characters run in registers; longer ones (and alphabets whose match table exceeds 60 KiB) in a
+ * general -- slow -- kernel.  The preparation is pfz_indel_*'s, cached on the handle.  Blocks. */
+int pfz_lev_components(pfz_ctx *ctx, const pfz_strings *strings, int32_t scorer, double min_similarity, int32_t *out_label,
+                       int64_t *out_pairs, int64_t *out_components, int64_t *out_counters);
 
 /* ---- K10: a candidate table rescored by edit distance ----------------------
  * Blocking, then exact scoring: extends the reference's edit-distance loop (polyfuzz/models/_distance.py:89-102: scorer(from, to)

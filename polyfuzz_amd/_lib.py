@@ -100,6 +100,7 @@ SIGNATURES = {
     "pfz_lev_topn": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp]),
     "pfz_lev_matrix_host": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_vp]),
     "pfz_lev_join": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_f64, c_i64, c_vp, c_vp, c_vp, c_vp, P(c_i64), c_vp]),
+    "pfz_lev_components": (ctypes.c_int, [c_vp, c_vp, c_i32, c_f64, c_vp, P(c_i64), P(c_i64), c_vp]),
     "pfz_pairs_rescore_topn": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
     "pfz_fuzz_extract_one": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "pfz_fuzz_extract_one_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
@@ -852,6 +853,20 @@ def lev_join(ctx, from_dev, to_dev, scorer, min_similarity, capacity=None, count
     assert total.value <= cap                     # (the second call had room for the exact total)
     n = total.value
     out = (row_ptr, idx[:n].copy(), dist[:n].copy(), sim[:n].copy())
+    return out + (dict(zip(LEV_JOIN_COUNTERS, work.tolist())),) if counters else out
+
+
+def lev_components(ctx, dev, scorer, min_similarity, counters=False):
+    """K12: the connected components of "similarity >= min_similarity" over the list `dev` (the pairs of lev_join's self-join,
+    united on the device, never stored) -- (label int32[n], pairs, components): label[i] is the smallest position in i's
+    component, pairs the number of hits (lev_join's total), components the number of components, singletons included.
+    counters=True appends a dict of LEV_JOIN_COUNTERS (the walk is lev_join's: so are the values)."""
+    work = np.zeros(3, np.int64) if counters else None
+    label = np.empty(dev.n, np.int32)
+    pairs, components = c_i64(0), c_i64(0)
+    check(ctx.lib.pfz_lev_components(ctx.h, dev.h, LEV_SCORERS[scorer], float(min_similarity), _ptr(label), ctypes.byref(pairs),
+                                     ctypes.byref(components), _ptr(work)))
+    out = (label, pairs.value, components.value)
     return out + (dict(zip(LEV_JOIN_COUNTERS, work.tolist())),) if counters else out
 
 

@@ -14,6 +14,9 @@ NOT equivalent.  Here:
   its pure-Python twin -- and the three dicts are rebuilt in the reference's insertion order.
 * `group_top1(...)`: the same result for a self-match top-1 device result without building the
   frame first (K6 linkage kernel, csrc/k6_reductions.hip), used by TFIDF-based grouping.
+* `connected_components(strings, model, min_similarity)` / `dicts_from_labels(strings, labels)`: NOT the reference's walk but
+  the clustering it is usually taken for -- the connected components of "similarity >= min_similarity", from the labels
+  EditDistance.components computes on the device (K12) -- in the same three return values.
 """
 from typing import List, Mapping, Tuple
 
@@ -104,6 +107,38 @@ def group_top1(result, strings: List[str], min_similarity: float):
     mapped = np.nonzero(cluster >= 0)[0]
     order = mapped[np.argsort(key[mapped], kind="stable")].astype(np.int32)
     return dicts_from_assignment(strings, cluster, order)
+
+
+def dicts_from_labels(strings, labels):
+    """The three dicts single_linkage returns, from component labels (labels[i] = the smallest position in i's component, as
+    EditDistance.components gives them), in O(n): components of at least two POSITIONS become clusters, numbered 1, 2, ... by
+    their smallest position; clusters[id] lists the component's distinct strings in order of first position;
+    cluster_mapping[s] = id and cluster_name_map[s] = clusters[id][0] for every string of a cluster.  A string alone in its
+    component is in none of them.  Equal strings must share a component (they do at every threshold: they score 1.0), so the
+    string keys are well defined."""
+    labels = np.asarray(labels)
+    size = np.bincount(labels, minlength=len(labels)) if len(labels) else np.zeros(0, np.int64)
+    ids = {}                                             # root position -> cluster id (roots are met in ascending order)
+    clusters, cluster_mapping = {}, {}
+    for s, root in zip(strings, labels.tolist()):
+        if size[root] < 2:
+            continue
+        cid = ids.setdefault(root, len(ids) + 1)
+        if s not in cluster_mapping:
+            cluster_mapping[s] = cid
+            clusters.setdefault(cid, []).append(s)
+    cluster_name_map = {s: clusters[cid][0] for s, cid in cluster_mapping.items()}
+    return clusters, cluster_mapping, cluster_name_map
+
+
+def connected_components(strings: List[str], model,
+                         min_similarity: float = 0.8) -> Tuple[Mapping[int, List[str]], Mapping[str, int], Mapping[str, str]]:
+    """Near-duplicate clusters of `strings` as the CONNECTED COMPONENTS of "similarity >= min_similarity" -- A ~ B and B ~ C put
+    A, B and C together, whatever the order of the list -- in the three return values of single_linkage (which is the
+    reference's greedy, order-dependent walk and not this).  `model`: an EditDistance with scorer "levenshtein" or "osa"; its
+    `components` finds the pairs and unites them on the device (K12), and only one label per string comes back."""
+    strings = list(strings)
+    return dicts_from_labels(strings, model.components(strings, min_similarity))
 
 
 def create_groups(matches: pd.DataFrame, model=None, link_min_similarity: float = 0.75, group_all_strings: bool = False):

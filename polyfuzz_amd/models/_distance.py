@@ -172,7 +172,13 @@ class EditDistance(BaseMatcher):
 
     join (method, "levenshtein" and "osa"): every pair at least `min_similarity` similar instead of each string's best -- the
     threshold form (K11), exact, with a self-join that reports each unordered pair once; see `join`.
+
+    components (method, "levenshtein" and "osa"): the connected components of that self-join's graph as one int32 label per
+    string -- near-duplicate clusters, computed on the device where the pairs are found (K12); see `components`.
     """
+    last_counts = None      # {"pairs", "components"} of the last `components` call
+
+
     def __init__(self,
                  n_jobs: int = 1,
                  scorer: Union[Callable, str, None] = "ratio",
@@ -270,7 +276,8 @@ class EditDistance(BaseMatcher):
         To = from_list[j]; never a string with itself, but equal strings at different positions are a pair.
 
         Scorers "levenshtein" and "osa" only (NotImplementedError otherwise); min_similarity: a number in [0, 1]
-        (ValueError otherwise).  The frame has the columns single_linkage reads. """
+        (ValueError otherwise).  The frame has the columns single_linkage reads; for the clusters of the self-join's graph
+        (its connected components) see `components`, which never builds the frame. """
         if self._scorer_name not in _JOIN_SCORERS:
             raise NotImplementedError(
                 f"EditDistance.join runs on the GPU for the scorers {_JOIN_SCORERS}; scorer {self._scorer_name!r} has no "
@@ -290,6 +297,36 @@ class EditDistance(BaseMatcher):
         matches = pd.DataFrame({"From": gather_column(from_list, frm), "To": gather_column(names, idx), "Similarity": sim}, copy=False)
         self.last_timings = {"device": (t1 - t0) * 1e3, "frame": (time.perf_counter() - t1) * 1e3}
         return matches
+
+    def components(self,
+                   from_list: List[str],
+                   min_similarity: float = 0.8) -> np.ndarray:
+        """ Near-duplicate clusters of from_list (K12): int32 labels, label[i] = the smallest position in i's connected
+        component of the graph whose edges are the pairs `join(from_list, min_similarity=...)` reports -- "A ~ B and B ~ C put A,
+        B and C together".  Equal strings share a component; a string with no partner is its own (label[i] == i).  Exact and
+        deterministic.  The pairs are united on the device where they are found and never stored or downloaded: device memory
+        is O(len(from_list)) whatever their number.  polyfuzz_amd.linkage.connected_components turns the labels into the three
+        dicts single_linkage returns.
+
+        `normalize` is NOT applied: there is no score to rescale.
+
+        Scorers "levenshtein" and "osa" only (NotImplementedError otherwise); min_similarity: a number in [0, 1]
+        (ValueError otherwise).  Sets last_timings and last_counts = {"pairs": hits, "components": components}. """
+        if self._scorer_name not in _JOIN_SCORERS:
+            raise NotImplementedError(
+                f"EditDistance.components runs on the GPU for the scorers {_JOIN_SCORERS}; scorer {self._scorer_name!r} has no "
+                "threshold kernel")
+        if (isinstance(min_similarity, bool) or not isinstance(min_similarity, (int, float, np.integer, np.floating))
+                or not 0.0 <= float(min_similarity) <= 1.0):      # (NaN compares false)
+            raise ValueError(f"min_similarity must be a number in [0, 1], not {min_similarity!r}")
+        from ._rapidfuzz import upload_for
+        t0 = time.perf_counter()
+        ctx = _lib.Context.default()
+        f_dev = upload_for(ctx, self._scorer_name, from_list)
+        label, pairs, components = _lib.lev_components(ctx, f_dev, self._scorer_name, float(min_similarity))
+        self.last_timings = {"device": (time.perf_counter() - t0) * 1e3, "frame": 0.0}
+        self.last_counts = {"pairs": pairs, "components": components}
+        return label
 
     def _best(self, from_list, to_list, reuse_to=False, top_n=None):
         ctx = _lib.Context.default()
