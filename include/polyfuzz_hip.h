@@ -597,18 +597,32 @@ int pfz_dense_rescore_topn_mixed(pfz_ctx *ctx, const pfz_dense *from_exact, cons
  * (ascending, n_thresholds <= 4096) count_ge[k] = #{i : sim[i] >= p_k} and sum_ge[k] = the sum of
  * those similarities (recall = count / n, average precision = sum / count on the host).  NaN
  * similarities are never >= a threshold.  Sums are accumulated in 64-bit fixed point (bit-
- * reproducible; absolute error of a mean below 1e-13 for similarities in [0, 100]).  Blocks. */
+ * reproducible): every value is rounded once to a multiple of 2^(e - 61), with frexp(n * max|sim|) =
+ * (m, e), so a sum of c values is off by at most c * 2^(e - 62) plus its own rounding to a double
+ * (absolute error of a mean below 1e-13 for similarities in [0, 100]).  Thresholds may repeat and be
+ * negative, like the similarities.  PFZ_ERR_INVALID: no or more than 4096 thresholds, thresholds that
+ * descend, an infinite similarity.  Blocks. */
 int pfz_pr_curve_host(pfz_ctx *ctx, const double *sim, int64_t n, const double *thresholds,
                       int32_t n_thresholds, int64_t *count_ge, double *sum_ge);
-/* single_linkage (reference polyfuzz/linkage.py:5-53) of a self-match TOP-1 result, as
- * PolyFuzz._create_groups builds it (polyfuzz.py:468-475: model.match(strings) on unique strings):
+/* single_linkage (reference polyfuzz/linkage.py:5-53) of a TOP-1 result of a list of unique strings
+ * against itself: as PolyFuzz._create_groups builds it (polyfuzz.py:468-475: model.match(strings),
+ * the diagonal excluded), or as a two-list match of the list with itself (model.match(strings,
+ * strings), where a row's best match is usually the string itself).
  * row i = (From i, To = result idx[i][0], Similarity = round(score, 3)), rows with Similarity >
  * min_similarity (>= 0) walked in order with the reference's greedy, order-dependent rule -- cluster 0
- * is falsy, so the first cluster's members are re-assigned when met again.  out_cluster[i] = cluster
+ * is falsy, so the first cluster's members are re-assigned when met again.  A row without a match
+ * (an index outside [0, n_rows), or a Similarity that rounds below 0.001) is not walked.  A kept row
+ * with To == From does what the walk does: if the string is unmapped or in cluster 0 it
+ * founds a cluster with itself, if it is mapped already the row is skipped.  out_cluster[i] = cluster
  * id of string i (-1: in no cluster); out_key[i] = position key of string i in the reference's dicts
  * (ascending key = insertion order; -1 where out_cluster is -1); out_info3 (may be NULL) = {first kept
  * row or -1, fixpoint rounds, clusters founded}.  `result` may hold more than one rank per row; only
- * rank 0 is read.  Blocks. */
+ * rank 0 is read.  Blocks.
+ * PFZ_ERR_INVALID: min_similarity < 0, 2^30 rows or more.  PFZ_ERR_UNSUPPORTED: one of the kernel's two
+ * loops did not settle within its bound -- n_rows + 1 rounds of the activity fixpoint, ceil(log2
+ * n_rows) + 2 rounds of pointer jumping; out_cluster and out_key are then left unwritten.  No input
+ * reaches either bound (every top-1 graph on up to 7 rows is checked); the code is there so that
+ * none can keep the device busy for ever. */
 int pfz_linkage_top1(pfz_ctx *ctx, const pfz_topn *result, double min_similarity,
                      int32_t *out_cluster, int32_t *out_key, int32_t *out_info3);
 

@@ -4,7 +4,9 @@
 //   * single_linkage on a self-match top-1 result (reference polyfuzz/linkage.py:5-53 as called from
 //     PolyFuzz._create_groups, polyfuzz.py:459-484) -- see the second half of this file.
 // Both are a few hundred KB of HBM-resident data: latency-bound, one small kernel each.
+// The per-element decisions of both live in k6_core.h, where a host program checks them without a GPU.
 #include "pfz_internal.h"
+#include "k6_core.h"
 
 #include <math.h>
 #include <string.h>
@@ -31,15 +33,10 @@ __global__ __launch_bounds__(1024) void k_pr_hist(const double *__restrict__ sim
     for (int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 1024) {
         const double v = sim[i];
         if (!(v == v)) continue;                 // NaN is never >= a threshold
-        int lo = 0, hi = n_thr;                  // first threshold > v
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (s_thr[mid] <= v) lo = mid + 1;
-            else hi = mid;
-        }
+        const int lo = pr_bin(s_thr, n_thr, v);  // first threshold > v
         if (lo == 0) continue;
         atomicAdd(&s_cnt[lo], 1ull);
-        atomicAdd((unsigned long long *)&s_sum[lo], (unsigned long long)llrint(v * scale));
+        atomicAdd((unsigned long long *)&s_sum[lo], pr_fixed(v, scale));
     }
     __syncthreads();
     for (int t = threadIdx.x; t <= n_thr; t += 1024) {
@@ -67,7 +64,11 @@ __global__ __launch_bounds__(1024) void k_pr_hist(const double *__restrict__ sim
 //   * string x is mapped before time t  <=>  its own row ran (x in R, x < t)  or an ACTIVE row s < t points to it
 //     (g_s = x), where a row is active when its From was still unmapped:  active[x] <=> no active s < x with
 //     g_s = x.  That recurrence only looks at smaller indices, so iterating it from "all of R active" fixes
-//     index after index (the rounds needed = the longest chain of such forward edges, a handful in practice);
+//     index after index (the rounds needed = the longest chain of such forward edges, a handful in practice; never more
+//     than n + 1);
+//   * a row whose To is its own From (g_s = s: a list matched against itself as TWO lists, where the diagonal stays in) is a
+//     row like any other: skipped when s is mapped, else it founds a cluster with itself.  Its own edge counts in fin (it is
+//     the founding row of s when it is active) but not against its activity -- `s < x` above;
 //   * with fin[x] = first active row pointing to x:  row s founds a cluster  <=>  active[s], fin[g_s] == s and
 //     g_s was not mapped by its own row (g_s not in R or g_s > s);  cluster ids = 1 + rank of the founding
 //     rows in time;  every other active row adopts:  M[s] = M[g_s], resolved by pointer jumping (the chains of
@@ -77,14 +78,9 @@ __global__ __launch_bounds__(1024) void k_pr_hist(const double *__restrict__ sim
 //     their first position even when a later founding re-assigns them.
 // One workgroup: the data is n ints, every pass is a few microseconds, and the passes need a barrier between them.
 constexpr int kLinkT = 1024;
-constexpr int32_t kInf = 0x7fffffff;
 
-__device__ inline bool kept_row(int32_t g, float v, int32_t n, double thr)
-{
-    const double r3 = rint((double)v * 1000.0) / 1000.0;      // np.round(float64(score), 3), the frame's Similarity
-    return g >= 0 && g < n && r3 >= 0.001 && r3 > thr;        // (< 0.001 -> To = None, Similarity = 0: never > thr >= 0)
-}
-
+// info: [0] first kept row or -1, [1] fixpoint rounds, [2] clusters founded, [3] a LinkStatus.  On an overrun of either loop's cap
+// (k6_core.h: no input reaches them) every thread leaves at once, cluster / key are unfinished and the host refuses the result.
 __global__ __launch_bounds__(kLinkT) void k_linkage_top1(const int32_t *__restrict__ idx, const float *__restrict__ val,
                                                          int32_t stride, int32_t n, double thr, int32_t *__restrict__ state,
                                                          int32_t *__restrict__ fin, int32_t *__restrict__ ptr,
@@ -93,7 +89,7 @@ __global__ __launch_bounds__(kLinkT) void k_linkage_top1(const int32_t *__restri
 {
     __shared__ int s_t0, s_changed, s_part[kLinkT];
     const int tid = threadIdx.x;
-    if (tid == 0) s_t0 = kInf;
+    if (tid == 0) s_t0 = kLinkInf;
     __syncthreads();
     for (int i = tid; i < n; i += kLinkT) {
         const bool f = kept_row(idx[(int64_t)i * stride], val[(int64_t)i * stride], n, thr);
@@ -104,28 +100,25 @@ __global__ __launch_bounds__(kLinkT) void k_linkage_top1(const int32_t *__restri
     }
     __syncthreads();
     const int t0 = s_t0;
-    if (t0 == kInf) {
-        if (tid == 0) info[0] = -1, info[1] = 0;
+    if (t0 == kLinkInf) {
+        if (tid == 0) info[0] = -1, info[1] = 0, info[2] = 0, info[3] = kLinkDone;
         return;
     }
     // state: bit 1 = row in R, bit 0 = active (current guess)
-    for (int i = tid; i < n; i += kLinkT) state[i] = (state[i] && i != t0) ? 3 : 0;
+    for (int i = tid; i < n; i += kLinkT) state[i] = link_initial_state(state[i] != 0, i, t0);
     int rounds = 0;
-    for (;;) {
-        for (int i = tid; i < n; i += kLinkT) fin[i] = kInf;
+    for (;;) {      // at most link_round_cap(n) rounds
+        for (int i = tid; i < n; i += kLinkT) fin[i] = kLinkInf;
         if (tid == 0) s_changed = 0;
         __syncthreads();
         for (int s = tid; s < n; s += kLinkT)
             if (state[s] & 1) atomicMin(&fin[idx[(int64_t)s * stride]], s);
         __syncthreads();
         for (int x = tid; x < n; x += kLinkT) {
-            const int st = state[x];
-            if (st & 2) {
-                const int a = fin[x] > x ? 1 : 0;
-                if (a != (st & 1)) {
-                    state[x] = 2 | a;
-                    s_changed = 1;
-                }
+            const int st = state[x], nst = link_active(st, fin[x], x);
+            if (nst != st) {
+                state[x] = nst;
+                s_changed = 1;
             }
         }
         __syncthreads();
@@ -133,6 +126,10 @@ __global__ __launch_bounds__(kLinkT) void k_linkage_top1(const int32_t *__restri
         const int changed = s_changed;
         __syncthreads();
         if (!changed) break;
+        if (rounds >= link_round_cap(n)) {      // (uniform: every thread counts the same rounds)
+            if (tid == 0) info[0] = t0, info[1] = rounds, info[2] = 0, info[3] = kLinkFixpointOverrun;
+            return;
+        }
     }
     // founding rows (0/1 -> exclusive scan = rank in time) and the adoption pointers
     const int per = (n + kLinkT - 1) / kLinkT;
@@ -140,14 +137,11 @@ __global__ __launch_bounds__(kLinkT) void k_linkage_top1(const int32_t *__restri
     int mine = 0;
     for (int s = lo; s < hi; ++s) {
         const int st = state[s];
-        int founding = 0;
-        if (st & 1) {
-            const int g = idx[(int64_t)s * stride];
-            founding = fin[g] == s && !((state[g] & 2) && g < s);
-        }
+        const int g = (st & 1) ? idx[(int64_t)s * stride] : s;
+        const int founding = (st & 1) && link_founding(s, g, fin[g], state[g]);
         scan[s] = founding;
         mine += founding;
-        ptr[s] = (st & 1) ? idx[(int64_t)s * stride] : s;
+        ptr[s] = link_pointer(st, s, g);
     }
     s_part[tid] = mine;
     __syncthreads();
@@ -173,12 +167,13 @@ __global__ __launch_bounds__(kLinkT) void k_linkage_top1(const int32_t *__restri
     // founded strings: x has an active in-edge and was not mapped by its own row before it
     for (int x = tid; x < n; x += kLinkT) {
         const int f = fin[x];
-        if (f != kInf && !((state[x] & 2) && x < f)) {
+        if (link_founded(x, f, state[x])) {
             cluster[x] = 1 + scan[f];
             key[x] = 2 * f;
         }
     }
-    // pointer jumping along the adoption chains
+    // pointer jumping along the adoption chains: at most link_jump_cap(n) rounds
+    int jumps = 0;
     for (;;) {
         if (tid == 0) s_changed = 0;
         __syncthreads();
@@ -190,9 +185,14 @@ __global__ __launch_bounds__(kLinkT) void k_linkage_top1(const int32_t *__restri
             }
         }
         __syncthreads();
+        ++jumps;
         const int changed = s_changed;
         __syncthreads();
         if (!changed) break;
+        if (jumps >= link_jump_cap(n)) {
+            if (tid == 0) info[0] = t0, info[1] = rounds, info[3] = kLinkJumpOverrun;
+            return;
+        }
     }
     for (int x = tid; x < n; x += kLinkT)
         if (state[x] & 1) {
@@ -201,13 +201,10 @@ __global__ __launch_bounds__(kLinkT) void k_linkage_top1(const int32_t *__restri
         }
     __syncthreads();
     if (tid == 0) {     // cluster 0: the first kept row's To and From, wherever they ended up they entered the dict first
-        const int g0 = idx[(int64_t)t0 * stride];
-        if (cluster[g0] < 0) cluster[g0] = 0;
-        if (cluster[t0] < 0) cluster[t0] = 0;
-        key[g0] = 2 * t0;
-        key[t0] = 2 * t0 + 1;
+        link_patch_cluster0(t0, idx[(int64_t)t0 * stride], cluster, key);
         info[0] = t0;
         info[1] = rounds;
+        info[3] = kLinkDone;
     }
 }
 
@@ -231,9 +228,7 @@ int pfz_pr_curve_host(pfz_ctx *ctx, const double *sim, int64_t n, const double *
     }
     PFZ_REQUIRE(max_abs < 1e300, "pfz_pr_curve_host: similarities must be finite");
     // fixed-point scale: n * max|v| * scale < 2^62
-    int e = 0;
-    frexp((double)(n > 0 ? n : 1) * (max_abs > 0.0 ? max_abs : 1.0), &e);
-    const double scale = ldexp(1.0, 61 - e);
+    const double scale = pr_scale(n, max_abs);
     PFZ_HIP(hipSetDevice(ctx->device));
     DevBuf d_sim, d_thr, d_cnt, d_sum;
     PFZ_TRY(d_sim.alloc(ctx, (size_t)(n > 0 ? n : 1) * sizeof(double)));
@@ -273,7 +268,7 @@ int pfz_linkage_top1(pfz_ctx *ctx, const pfz_topn *result, double min_similarity
     PFZ_REQUIRE(min_similarity >= 0.0, "pfz_linkage_top1: min_similarity must be >= 0 (got %g)", min_similarity);
     PFZ_REQUIRE(result->n_rows < ((int64_t)1 << 30), "pfz_linkage_top1: too many rows");
     const int32_t n = (int32_t)result->n_rows;
-    int32_t info[3] = {-1, 0, 0};
+    int32_t info[4] = {-1, 0, 0, kLinkDone};
     if (n > 0) {
         PFZ_HIP(hipSetDevice(ctx->device));
         DevBuf work;
@@ -283,11 +278,16 @@ int pfz_linkage_top1(pfz_ctx *ctx, const pfz_topn *result, double min_similarity
         hipLaunchKernelGGL(k_linkage_top1, dim3(1), dim3(kLinkT), 0, ctx->stream, result->idx, result->val, result->ntop, n,
                            min_similarity, state, fin, ptr, scan, cluster, key, d_info);
         PFZ_HIP(hipGetLastError());
+        PFZ_TRY(copy_d2h(ctx, info, d_info, sizeof(info)));
+        if (info[3] != kLinkDone) {     // a loop of the kernel ran into its cap: nothing is written
+            set_error("pfz_linkage_top1: the %s did not settle within its bound (%d rows, %d rounds)",
+                      info[3] == kLinkFixpointOverrun ? "activity fixpoint" : "pointer jumping", n, info[1]);
+            return PFZ_ERR_UNSUPPORTED;
+        }
         PFZ_TRY(copy_d2h(ctx, out_cluster, cluster, (size_t)n * sizeof(int32_t)));
         PFZ_TRY(copy_d2h(ctx, out_key, key, (size_t)n * sizeof(int32_t)));
-        PFZ_TRY(copy_d2h(ctx, info, d_info, sizeof(info)));
     }
-    if (out_info3) memcpy(out_info3, info, sizeof(info));
+    if (out_info3) memcpy(out_info3, info, 3 * sizeof(int32_t));
     return PFZ_OK;
 }
 

@@ -102,7 +102,10 @@ def group_top1(result, strings: List[str], min_similarity: float):
     """The three dicts of `single_linkage(model.match(strings), min_similarity)` straight from the device-resident
     self-match result of `strings` (a _lib.DeviceTopN; only rank 0 is read): K6's parallel re-statement of the
     greedy walk, no frame in between.  `strings` must be unique (as in PolyFuzz._create_groups, polyfuzz.py:468-471)
-    and min_similarity >= 0; otherwise build the frame and call single_linkage."""
+    and min_similarity >= 0; otherwise build the frame and call single_linkage.  The result of the list matched against
+    itself as two lists -- `model.match_device(strings, strings)`, where a string's best match is usually itself -- is
+    served as well and gives `single_linkage(model.match(strings, strings), min_similarity)`: a row with To == From founds
+    a cluster with itself unless the string is mapped already, as in the walk."""
     cluster, key, _ = _lib.linkage_top1(result.ctx, result, min_similarity)
     mapped = np.nonzero(cluster >= 0)[0]
     order = mapped[np.argsort(key[mapped], kind="stable")].astype(np.int32)
