@@ -27,10 +27,9 @@
 // table in global memory, any length, any alphabet, slow.
 // Bound: integer VALU + LDS look-ups behind a dependent chain of gathered loads (code unit -> lut -> PM) per to-character
 // (measured beside the all-pairs kernels).
+#include "edit_walk.h"
 #include "k10_core.h"
-#include "k4_plan.h"
 #include "k8_core.h"
-#include "k9_core.h"
 #include "topn_wave.h"
 
 #include <algorithm>
@@ -44,17 +43,11 @@ constexpr int kPairsJaroRegLen = 256;          // to-positions whose flags the J
 enum { PAIR_RATIO = 0, PAIR_LEVENSHTEIN = 1, PAIR_OSA = 2, PAIR_JARO = 3, PAIR_JARO_WINKLER = 4 };
 enum { MODE_REG32 = 0, MODE_REG64 = 1, MODE_GENERAL = 2 };
 
-struct PairArgs {
-    const void *a_chars;       // from-strings: code units of a_width bytes
-    int32_t a_width;
-    const int64_t *a_off;      // [n_from + 1]
+struct PairArgs : FromView {   // (the plan's packed groups are not read here)
     const void *b_chars;       // to-strings, the raw list
     int32_t b_width;
     const int64_t *b_off;      // [n_to + 1]
     int64_t n_to;
-    const uint16_t *lut;       // code unit -> symbol rank (0 = not in the to-list's alphabet), lut_len entries
-    uint32_t lut_len;
-    int32_t n_sym1;            // alphabet size + 1 (symbol 0: an empty table entry)
     const int32_t *cand;       // [>= n_from][m] candidate to-indices; anything outside [0, n_to) is skipped
     int32_t m;
     const int32_t *rows;       // the from-rows of this launch (register kernels)
@@ -65,15 +58,6 @@ struct PairArgs {
     int32_t *out_idx;          // [n_from][ntop]
     double *out_score;
 };
-
-__device__ inline int pair_symbol(const void *chars, int width, int64_t at, const PairArgs &A)
-{
-    const uint32_t c = width == 1 ? (uint32_t)((const uint8_t *)chars)[at] : ((const uint32_t *)chars)[at];
-    return c < A.lut_len ? (int)A.lut[c] : 0;
-}
-
-__device__ inline void pair_lds_or(uint32_t *p, uint32_t v) { atomicOr(p, v); }
-__device__ inline void pair_lds_or(uint64_t *p, uint64_t v) { atomicOr((unsigned long long *)p, (unsigned long long)v); }
 
 // lane k of the chunk at c0: its candidate's to-index, or -1 (no candidate: beyond the row, an empty slot, outside the to-list)
 __device__ inline int pair_candidate(const PairArgs &A, int64_t row, int c0)
@@ -98,14 +82,14 @@ __device__ __forceinline__ double pair_score_reg(const PairArgs &A, const WORD *
 {
     if constexpr (FAMILY == PAIR_RATIO) {
         WORD v = (WORD)~(WORD)0;
-        for (int t = 0; t < lb; ++t) lcs_step_reg<WORD>(v, pm[pair_symbol(A.b_chars, A.b_width, b0 + t, A)]);
+        for (int t = 0; t < lb; ++t) lcs_step_reg<WORD>(v, pm[edit_symbol(A, A.b_chars, A.b_width, b0 + t)]);
         const int lcs = __popcll((uint64_t)(WORD)~v);
         return la + lb == 0 ? 100.0 : ratio_of(lcs, (int64_t)la + lb);
     }
     else if constexpr (FAMILY == PAIR_LEVENSHTEIN || FAMILY == PAIR_OSA) {
         LevState<WORD> s;
         lev_begin(s, la);
-        for (int t = 0; t < lb; ++t) lev_step<WORD, FAMILY == PAIR_OSA>(s, pm[pair_symbol(A.b_chars, A.b_width, b0 + t, A)], true);
+        for (int t = 0; t < lb; ++t) lev_step<WORD, FAMILY == PAIR_OSA>(s, pm[edit_symbol(A, A.b_chars, A.b_width, b0 + t)], true);
         return lev_similarity(lev_distance(s.dist, la, lb), la, lb);
     }
     else {
@@ -118,7 +102,7 @@ __device__ __forceinline__ double pair_score_reg(const PairArgs &A, const WORD *
         for (int k = 0; k < NB; ++k) {
             s.fb = 0;
             const int hi = min(lb, (k + 1) * WB);
-            for (int j = k * WB; j < hi; ++j) jaro_match<WORD>(s, pm[pair_symbol(A.b_chars, A.b_width, b0 + j, A)], j, j - k * WB);
+            for (int j = k * WB; j < hi; ++j) jaro_match<WORD>(s, pm[edit_symbol(A, A.b_chars, A.b_width, b0 + j)], j, j - k * WB);
             fb[k] = s.fb;
         }
         const int m = __popcll((uint64_t)s.fa);
@@ -130,7 +114,7 @@ __device__ __forceinline__ double pair_score_reg(const PairArgs &A, const WORD *
                 s.fb = fb[k];
                 const int hi = min(lb, (k + 1) * WB);
                 for (int j = k * WB; j < hi; ++j)
-                    half_t += jaro_transpose<WORD>(s, pm[pair_symbol(A.b_chars, A.b_width, b0 + j, A)], j - k * WB);
+                    half_t += jaro_transpose<WORD>(s, pm[edit_symbol(A, A.b_chars, A.b_width, b0 + j)], j - k * WB);
             }
         }
         return jaro_score(m, half_t, la, lb, prefix, A.scorer == PAIR_JARO_WINKLER);
@@ -145,8 +129,7 @@ __global__ __launch_bounds__(64) void k10_pairs_kernel(PairArgs A)
     WORD *pm = (WORD *)smem_raw;
     const int lane = threadIdx.x;
 
-    for (int p = lane; p < A.n_sym1; p += 64) pm[p] = 0;
-    __syncthreads();
+    pm_reg_zero(A, pm, lane, 64);
 
     for (int r = blockIdx.x; r < A.n_rows; r += gridDim.x) {
         const int64_t row = A.rows[r];
@@ -164,9 +147,7 @@ __global__ __launch_bounds__(64) void k10_pairs_kernel(PairArgs A)
         }
         const int64_t a0 = A.a_off[row];
         const int la = (int)(A.a_off[row + 1] - a0);      // fits the WORD
-        const int my_sym = lane < la ? pair_symbol(A.a_chars, A.a_width, a0 + lane, A) : 0;
-        if (my_sym) pair_lds_or(&pm[my_sym], (WORD)1 << lane);
-        __syncthreads();
+        const int my_sym = pm_reg_set(A, pm, a0, la, lane);
 
         TopnList list = topn_empty();
         for (int c0 = 0; c0 < A.m; c0 += 64) {
@@ -178,8 +159,7 @@ __global__ __launch_bounds__(64) void k10_pairs_kernel(PairArgs A)
             topn_insert(list, A.ntop, j >= 0, sc, j);      // (all 64 lanes: the loop and its bounds are the wave's)
         }
         pair_store_row(A, row, list);
-        if (my_sym) pm[my_sym] = 0;      // clear the entries of this from-string
-        __syncthreads();
+        pm_reg_clear(pm, my_sym);
     }
 }
 
@@ -191,7 +171,7 @@ __device__ __forceinline__ double pair_score_general(const PairArgs &A, const ui
     if (A.scorer == PAIR_RATIO) {
         for (int w = 0; w < W; ++w) s0[(int64_t)w * 64] = ~0ull;
         for (int t = 0; t < lb; ++t) {
-            const uint64_t *pmc = pm + (int64_t)pair_symbol(A.b_chars, A.b_width, b0 + t, A) * WA;
+            const uint64_t *pmc = pm + (int64_t)edit_symbol(A, A.b_chars, A.b_width, b0 + t) * WA;
             uint64_t carry = 0;
             for (int w = 0; w < W; ++w) {
                 uint64_t v = s0[(int64_t)w * 64];
@@ -206,28 +186,14 @@ __device__ __forceinline__ double pair_score_general(const PairArgs &A, const ui
     if (A.scorer == PAIR_LEVENSHTEIN || A.scorer == PAIR_OSA) {
         // s0 / s1 / s2: VP / VN / the previous step's D0
         const bool osa = A.scorer == PAIR_OSA;
-        for (int w = 0; w < W; ++w) {
-            s0[(int64_t)w * 64] = low_ones<uint64_t>(la - 64 * w);
-            s1[(int64_t)w * 64] = 0ull;
-            s2[(int64_t)w * 64] = 0ull;
-        }
+        lev_column_begin(s0, s1, s2, W, la, 64);
         const uint64_t last = la > 0 ? 1ull << ((la - 1) % 64) : 0ull;
         int dist = la;
         int c_prev = 0;                                         // (symbol 0: an empty table entry)
         for (int t = 0; t < lb; ++t) {
-            const int c = pair_symbol(A.b_chars, A.b_width, b0 + t, A);
+            const int c = edit_symbol(A, A.b_chars, A.b_width, b0 + t);
             const uint64_t *eq = pm + (int64_t)c * WA, *eq_prev = pm + (int64_t)c_prev * WA;
-            LevCarry cy = lev_carry_begin();
-            uint64_t hp = 0, hn = 0;
-            for (int w = 0; w < W; ++w) {
-                uint64_t x_vp = s0[(int64_t)w * 64], x_vn = s1[(int64_t)w * 64], x_d0 = osa ? s2[(int64_t)w * 64] : 0ull;
-                if (osa) lev_step_word<true>(x_vp, x_vn, x_d0, eq[w], eq_prev[w], cy, &hp, &hn);
-                else lev_step_word<false>(x_vp, x_vn, x_d0, eq[w], 0ull, cy, &hp, &hn);
-                s0[(int64_t)w * 64] = x_vp;
-                s1[(int64_t)w * 64] = x_vn;
-                if (osa) s2[(int64_t)w * 64] = x_d0;
-            }
-            dist += (int)((hp & last) != 0) - (int)((hn & last) != 0);
+            dist += osa ? lev_column_step<true>(s0, s1, s2, eq, eq_prev, W, last, 64) : lev_column_step<false>(s0, s1, s2, eq, eq_prev, W, last, 64);
             c_prev = c;
         }
         return lev_similarity(lev_distance(dist, la, lb), la, lb);
@@ -240,7 +206,7 @@ __device__ __forceinline__ double pair_score_general(const PairArgs &A, const ui
     int m = 0;
     uint32_t pre = 0;
     for (int t = 0; t < lb; ++t) {
-        const uint64_t *pmc = pm + (int64_t)pair_symbol(A.b_chars, A.b_width, b0 + t, A) * WA;
+        const uint64_t *pmc = pm + (int64_t)edit_symbol(A, A.b_chars, A.b_width, b0 + t) * WA;
         if (t < 4) pre |= (uint32_t)((pmc[0] >> t) & 1) << t;
         const int lo = max(t - range, 0), hi = min(t + range, la - 1);
         for (int w = lo >> 6; w <= hi >> 6 && lo <= hi; ++w) {
@@ -263,7 +229,7 @@ __device__ __forceinline__ double pair_score_general(const PairArgs &A, const ui
             while (cur == 0 && wa + 1 < W) cur = s0[(int64_t)(++wa) * 64];      // (as many flags on either side)
             const uint64_t low = cur & (0 - cur);
             cur ^= low;
-            half_t += !(pm[(int64_t)pair_symbol(A.b_chars, A.b_width, b0 + t, A) * WA + wa] & low);
+            half_t += !(pm[(int64_t)edit_symbol(A, A.b_chars, A.b_width, b0 + t) * WA + wa] & low);
         }
     }
     return jaro_score(m, half_t, la, lb, jaro_prefix(pre), A.scorer == PAIR_JARO_WINKLER);
@@ -286,12 +252,7 @@ __global__ __launch_bounds__(64) void k10_pairs_general_kernel(PairArgs A, int32
         const int64_t a0 = A.a_off[row];
         const int la = (int)(A.a_off[row + 1] - a0);
         const int W = la > 0 ? (la + 63) / 64 : 1;                    // <= WA
-        for (int p = lane; p < la; p += 64) {
-            const int sy = pair_symbol(A.a_chars, A.a_width, a0 + p, A);
-            if (sy) atomicOr((unsigned long long *)&pm[(int64_t)sy * WA + p / 64], 1ull << (p % 64));
-        }
-        __threadfence_block();
-        __syncthreads();
+        pm_global_set(A, pm, WA, a0, la, lane, 64);
 
         TopnList list = topn_empty();
         for (int c0 = 0; c0 < A.m; c0 += 64) {
@@ -303,12 +264,7 @@ __global__ __launch_bounds__(64) void k10_pairs_general_kernel(PairArgs A, int32
             topn_insert(list, A.ntop, j >= 0, sc, j);      // (all 64 lanes: the loop and its bounds are the wave's)
         }
         pair_store_row(A, row, list);
-        for (int p = lane; p < la; p += 64) {
-            const int sy = pair_symbol(A.a_chars, A.a_width, a0 + p, A);
-            if (sy) pm[(int64_t)sy * WA + p / 64] = 0ull;
-        }
-        __threadfence_block();
-        __syncthreads();
+        pm_global_clear(A, pm, WA, a0, la, lane, 64);
     }
 }
 
@@ -341,39 +297,26 @@ static int pairs_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, c
     PFZ_TRY(indel_plan_get(ctx, T, &pl));      // (its code unit -> symbol table; the packed groups are not read here)
 
     const bool jaro = scorer == PAIR_JARO || scorer == PAIR_JARO_WINKLER;
-    const bool lds_fits = (size_t)(pl->n_sym + 1) * sizeof(uint64_t) <= 60 * 1024;
-    std::vector<uint8_t> mode((size_t)n_from);
-    std::vector<int32_t> rows_cls[2];
-    int64_t n_general = 0, longest = 1;
-    for (int64_t i = 0; i < n_from; ++i) {
-        const int64_t la = F->h_off[(size_t)i + 1] - F->h_off[(size_t)i];
-        const int cls = !lds_fits || la > 64 ? MODE_GENERAL : (la > 32 ? MODE_REG64 : MODE_REG32);
-        mode[(size_t)i] = (uint8_t)cls;
-        if (cls == MODE_GENERAL) {
-            ++n_general;
-            longest = std::max(longest, la);
-        }
-        else rows_cls[cls].push_back((int32_t)i);
-    }
+    const RowClasses rc = classify_rows(F, 0, n_from, lds_table_fits(pl));
+    const std::vector<int32_t> (&rows_cls)[3] = rc.rows;
+    std::vector<uint8_t> mode((size_t)n_from);      // MODE_* = the row's class
+    for (int cls = 0; cls < 3; ++cls)
+        for (int32_t i : rows_cls[cls]) mode[(size_t)i] = (uint8_t)cls;
+    const int64_t n_general = (int64_t)rows_cls[MODE_GENERAL].size(), longest = rc.longest;
     // (the Jaro register kernels hand a row with a candidate of more than 256 characters on: only a to-list that has one)
     const bool general = n_general > 0 || (jaro && T->max_len > kPairsJaroRegLen);
 
-    DevBuf d_mode, d_rows[2], d_oidx, d_oscore, d_pm, d_s0, d_s1, d_s2;
+    DevBuf d_mode, d_rows[2], d_oidx, d_oscore;
     PFZ_TRY(d_mode.upload(ctx, mode));
     PFZ_TRY(d_oidx.alloc(ctx, n_out * sizeof(int32_t)));
     PFZ_TRY(d_oscore.alloc(ctx, n_out * sizeof(double)));
 
     PairArgs A;
-    A.a_chars = F->chars;
-    A.a_width = F->char_width;
-    A.a_off = F->offsets;
+    static_cast<FromView &>(A) = from_view(F, pl);
     A.b_chars = T->chars;
     A.b_width = T->char_width;
     A.b_off = T->offsets;
     A.n_to = T->n;
-    A.lut = pl->lut;
-    A.lut_len = pl->lut_len;
-    A.n_sym1 = pl->n_sym + 1;
     A.cand = C->idx;
     A.m = C->ntop;
     A.rows = nullptr;
@@ -405,22 +348,12 @@ static int pairs_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, c
             const int32_t WA = (int32_t)((longest + 63) / 64);
             const int32_t WS = jaro ? (int32_t)std::max<int64_t>(WA, (T->max_len + 63) / 64) : WA;
             int64_t grid = std::min<int64_t>(n_general > 0 && !jaro ? n_general : n_from, max_grid);
-            const size_t pm_per = (size_t)A.n_sym1 * (size_t)WA * sizeof(uint64_t);
-            while (grid > 1 && pm_per * (size_t)grid > ((size_t)2 << 30)) grid /= 2;      // <= 2 GiB of match tables
-            if (pm_per * (size_t)grid > ((size_t)8 << 30)) {
-                set_error("pfz_pairs_rescore_topn: a from-string of %lld characters with %d alphabet symbols needs a %zu-byte match table",
-                          (long long)longest, pl->n_sym, pm_per);
-                return PFZ_ERR_UNSUPPORTED;
-            }
+            PFZ_TRY(general_grid(&grid, A.n_sym1, WA, "pfz_pairs_rescore_topn", "a from-string", longest));
             ProfScope ps(ctx, "k10_pairs_general");
-            const size_t st_bytes = (size_t)grid * (size_t)WS * 64 * sizeof(uint64_t);
-            PFZ_TRY(d_pm.alloc(ctx, pm_per * (size_t)grid));
-            PFZ_TRY(d_s0.alloc(ctx, st_bytes));
-            PFZ_TRY(d_s1.alloc(ctx, st_bytes));
-            PFZ_TRY(d_s2.alloc(ctx, st_bytes));
-            PFZ_HIP(hipMemsetAsync(d_pm.p, 0, pm_per * (size_t)grid, ctx->stream));
-            hipLaunchKernelGGL(k10_pairs_general_kernel, dim3((unsigned)grid), dim3(64), 0, ctx->stream, A, WA, WS, d_pm.as<uint64_t>(),
-                               d_s0.as<uint64_t>(), d_s1.as<uint64_t>(), d_s2.as<uint64_t>());
+            GeneralBufs gb;
+            PFZ_TRY(general_bufs_alloc(ctx, &gb, grid, A.n_sym1, WA, {WS, WS, WS}, 64));
+            hipLaunchKernelGGL(k10_pairs_general_kernel, dim3((unsigned)grid), dim3(64), 0, ctx->stream, A, WA, WS, gb.pm.as<uint64_t>(),
+                               gb.col[0].as<uint64_t>(), gb.col[1].as<uint64_t>(), gb.col[2].as<uint64_t>());
             PFZ_HIP(hipGetLastError());
         }
     }

@@ -78,6 +78,7 @@ __device__ inline void lcs_step(WORD (&V)[W], const WORD *__restrict__ pmc)
 
 __device__ inline void lds_or(uint32_t *p, uint32_t v) { atomicOr(p, v); }
 __device__ inline void lds_or(uint64_t *p, uint64_t v) { atomicOr((unsigned long long *)p, (unsigned long long)v); }
+
 __device__ inline int popc_word(uint32_t v) { return __popc(v); }
 __device__ inline int popc_word(uint64_t v) { return __popcll(v); }
 
@@ -928,8 +929,7 @@ static int indel_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T_c,
         const int32_t W = (int32_t)((longest + 63) / 64);
         int64_t gridg = std::min<int64_t>((int64_t)cls[6].size(), ctx->prop.multiProcessorCount * 2);
         const size_t pm_per = (size_t)(pl->n_sym + 1) * (size_t)W * sizeof(uint64_t);
-        while (gridg > 1 && pm_per * (size_t)gridg > ((size_t)2 << 30)) gridg /= 2;      // <= 2 GiB of match tables
-        if (pm_per * (size_t)gridg > ((size_t)8 << 30)) {
+        if (!general_grid_cap(&gridg, pm_per)) {      // (k4_plan.h: <= 2 GiB of match tables)
             set_error("pfz_indel: a from-string of %lld characters with %d alphabet symbols needs a %zu-byte match table",
                       (long long)longest, pl->n_sym, pm_per);
             return PFZ_ERR_UNSUPPORTED;

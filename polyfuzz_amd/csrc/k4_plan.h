@@ -1,5 +1,6 @@
 // K4's to-side plan -- the to-list's alphabet, its strings sorted by length into groups of 64, their symbols packed per
-// group -- as the kernels that walk it see it: K4 (k4_indel.hip, which builds it) and K8 (k8_jaro.hip).
+// group -- as the kernels that walk it see it: K4 (k4_indel.hip, which builds it), K8 (k8_jaro.hip), K9 (k9_levenshtein.hip), K11
+// (k11_join.hip) and K12 (k12_components.hip) through edit_walk.h's EditView; K10 (k10_pairs.hip) reads its symbol table alone.
 #pragma once
 
 #include "pfz_internal.h"
@@ -25,5 +26,13 @@ namespace pfz {
 
 // the plan of to-list T, built on first use and cached on the handle
 int indel_plan_get(pfz_ctx *ctx, const pfz_strings *T, const pfz_indel_plan **out);
+
+// the grid of a general kernel, halved until its match tables (pm_per bytes per workgroup) stay within 2 GiB; false: a single
+// table is beyond 8 GiB
+inline bool general_grid_cap(int64_t *grid, size_t pm_per)
+{
+    while (*grid > 1 && pm_per * (size_t)*grid > ((size_t)2 << 30)) *grid /= 2;
+    return pm_per * (size_t)*grid <= ((size_t)8 << 30);
+}
 
 }  // namespace pfz

@@ -22,8 +22,9 @@
 // against every to-string, every from-string against the groups of longer to-strings, an alphabet whose table exceeds
 // 60 KiB -- takes the general kernel: flag words and match table in global memory, any length, slow.  Every launch
 // leaves (score, index) records per from-string; k8_merge picks the first maximum of a row over them.
+// The view of the plan, the match table's set / clear, the (score, index) best and its merge are edit_walk.h's, shared with K9 .. K12.
 // Bound: integer VALU + LDS look-ups, two sweeps per pair where K4 has one (measured beside K4).
-#include "k4_plan.h"
+#include "edit_walk.h"
 #include "k8_core.h"
 
 #include <algorithm>
@@ -31,90 +32,26 @@
 
 namespace pfz {
 
-struct JaroRec {
-    double score;
-    int32_t idx, pad;      // idx < 0: no candidate
-};
-
-struct JaroArgs {
-    const void *a_chars;       // from-strings: code units of a_width bytes
-    int32_t a_width;
-    const int64_t *a_off;      // [n_from + 1]
-    const uint16_t *lut;       // code unit -> symbol rank (0 = not in the to-list's alphabet), lut_len entries
-    uint32_t lut_len;
+struct JaroArgs : EditView {
     const int32_t *rows;       // from-rows of this launch
     int32_t n_rows;
-    const uint32_t *b_packed;  // to-strings, groups of 64, [t/PER][lane]
-    const int64_t *g_off;      // [n_groups] dword offset of each group
-    const int32_t *g_steps;    // [n_groups] dwords per lane
-    const int32_t *b_len;      // [n_groups*64]
-    const int32_t *b_orig;     // [n_groups*64] original to-index, -1 = padding lane
     int32_t g_begin, g_end;    // the to-groups of this launch
     const int32_t *skip_idx;   // [n_from] or NULL (decoded: pfz_internal.h decode_skip_codes)
     int32_t skip_up_to;
-    int32_t n_sym1;            // alphabet size + 1 (symbol 0 = padding)
     int32_t winkler;
     int64_t from_begin;
     int64_t n_to;
     double *matrix;            // optional [(from_end-from_begin) * n_to]
     int32_t parts;             // the to-groups of a from-string are split over `parts` workgroups
     int32_t slot0, n_slots;    // part p of row r leaves its best in rec[(r - from_begin) * n_slots + slot0 + p]
-    JaroRec *rec;
+    BestRec *rec;
     unsigned long long *n_scored;   // optional: pairs whose float64 score was computed (the profile's work count)
 };
-
-struct JaroBest {
-    double score;        // -1: nothing yet
-    int idx;
-};
-
-__device__ inline void take(JaroBest &b, double score, int idx)
-{
-    if (score > b.score || (score == b.score && idx < b.idx)) {
-        b.score = score;
-        b.idx = idx;
-    }
-}
-
-// first maximum of the workgroup: (score desc, original index asc); thread 0 writes the record
-__device__ inline void block_best(JaroBest best, double *red_s, int *red_i, JaroRec *dst)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) take(best, __shfl_xor(best.score, d, 64), __shfl_xor(best.idx, d, 64));
-    if (lane == 0) {
-        red_s[wave] = best.score;
-        red_i[wave] = best.idx;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < 4; ++w) take(best, red_s[w], red_i[w]);
-        dst->score = best.score;
-        dst->idx = best.idx == INT_MAX ? -1 : best.idx;
-    }
-}
-
-__device__ inline void count_scored(unsigned long long *n_scored, int mine)
-{
-    if (!n_scored) return;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d, 64);
-    if ((threadIdx.x & 63) == 0) atomicAdd(n_scored, (unsigned long long)mine);
-}
-
-__device__ inline int a_symbol(const JaroArgs &A, int64_t at)
-{
-    const uint32_t c = A.a_width == 1 ? (uint32_t)((const uint8_t *)A.a_chars)[at] : ((const uint32_t *)A.a_chars)[at];
-    return c < A.lut_len ? (int)A.lut[c] : 0;
-}
 
 // what the lane remembers of the pair that holds its best, to recognise a pair of the same score without scoring it
 struct JaroKey {
     int m, t, lb, prefix;
 };
-
-__device__ inline void lds_or(uint32_t *p, uint32_t v) { atomicOr(p, v); }
-__device__ inline void lds_or(uint64_t *p, uint64_t v) { atomicOr((unsigned long long *)p, (unsigned long long)v); }
 
 // WORD: uint32_t (from-strings of <= 32 characters) or uint64_t (<= 64); NB: to-strings of up to NB words' characters --
 // their flags are NB registers, walked stretch by stretch with compile-time indices
@@ -129,8 +66,7 @@ __global__ __launch_bounds__(256) void k8_jaro_kernel(JaroArgs A)
     constexpr int SPW = (int)sizeof(WORD) * 8 / PER;      // dwords per stretch
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
-    for (int p = tid; p < A.n_sym1; p += 256) pm[p] = 0;
-    __syncthreads();
+    pm_reg_zero(A, pm, tid, 256);
 
     const int parts = A.parts;
     for (int u = blockIdx.x; u < A.n_rows * parts; u += gridDim.x) {
@@ -138,13 +74,11 @@ __global__ __launch_bounds__(256) void k8_jaro_kernel(JaroArgs A)
         const int row = A.rows[r];
         const int64_t a0 = A.a_off[row];
         const int la = (int)(A.a_off[row + 1] - a0);      // fits the WORD
-        const int my_sym = tid < la ? a_symbol(A, a0 + tid) : 0;
-        if (my_sym) lds_or(&pm[my_sym], (WORD)1 << tid);
-        __syncthreads();
+        const int my_sym = pm_reg_set(A, pm, a0, la, tid);
 
         const int skip = A.skip_idx ? A.skip_idx[row] : -1;
         const float inv_la = __builtin_amdgcn_rcpf((float)la);
-        JaroBest best = {-1.0, INT_MAX};
+        ScoreBest best = {-1.0, INT_MAX};
         JaroKey key = {-1, 0, 0, 0};
         float best_f = -1.0f;
         int scored = 0;
@@ -207,10 +141,9 @@ __global__ __launch_bounds__(256) void k8_jaro_kernel(JaroArgs A)
                 key = JaroKey{m, half_t / 2, lb, prefix};
             }
         }
-        block_best(best, red_s, red_i, A.rec + ((int64_t)row - A.from_begin) * A.n_slots + A.slot0 + part);
-        count_scored(A.n_scored, scored);
-        if (my_sym) pm[my_sym] = 0;      // clear the entries of this from-string
-        __syncthreads();
+        best_of_block(best, red_s, red_i, A.rec + ((int64_t)row - A.from_begin) * A.n_slots + A.slot0 + part);
+        wave_count(A.n_scored, scored);
+        pm_reg_clear(pm, my_sym);
     }
 }
 
@@ -233,14 +166,9 @@ __global__ __launch_bounds__(256) void k8_jaro_general_kernel(JaroArgs A, int32_
         const int row = A.rows[r];
         const int64_t a0 = A.a_off[row];
         const int la = (int)(A.a_off[row + 1] - a0);
-        for (int p = tid; p < la; p += 256) {
-            const int sy = a_symbol(A, a0 + p);
-            if (sy) atomicOr((unsigned long long *)&pm[(int64_t)sy * WA + p / 64], 1ull << (p % 64));
-        }
-        __threadfence_block();
-        __syncthreads();
+        pm_global_set(A, pm, WA, a0, la, tid, 256);
         const int skip = A.skip_idx ? A.skip_idx[row] : -1;
-        JaroBest best = {-1.0, INT_MAX};
+        ScoreBest best = {-1.0, INT_MAX};
         int scored = 0;
         for (int g = A.g_begin + wave + 4 * part; g < A.g_end; g += 4 * parts) {
             const uint32_t *gp = A.b_packed + A.g_off[g] + lane;
@@ -295,34 +223,21 @@ __global__ __launch_bounds__(256) void k8_jaro_general_kernel(JaroArgs A, int32_
                 const bool out = choice_left_out(orig, skip, A.skip_up_to);
                 const double sc = out ? -1.0 : jaro_score(m, half_t, la, lb, jaro_prefix(pre), A.winkler);
                 if (A.matrix) A.matrix[((int64_t)row - A.from_begin) * A.n_to + orig] = sc;
-                if (!out) take(best, sc, orig);
+                if (!out) best_take(best, sc, orig);
                 scored += !out;
             }
         }
-        block_best(best, red_s, red_i, A.rec + ((int64_t)row - A.from_begin) * A.n_slots + A.slot0 + part);
-        count_scored(A.n_scored, scored);
-        for (int p = tid; p < la; p += 256) {
-            const int sy = a_symbol(A, a0 + p);
-            if (sy) pm[(int64_t)sy * WA + p / 64] = 0ull;
-        }
-        __threadfence_block();
-        __syncthreads();
+        best_of_block(best, red_s, red_i, A.rec + ((int64_t)row - A.from_begin) * A.n_slots + A.slot0 + part);
+        wave_count(A.n_scored, scored);
+        pm_global_clear(A, pm, WA, a0, la, tid, 256);
     }
 }
 
 // the first maximum of every from-string over the records its launches left
-__global__ __launch_bounds__(256) void k8_merge(const JaroRec *__restrict__ rec, int32_t n_slots, int64_t n_rows,
+__global__ __launch_bounds__(256) void k8_merge(const BestRec *__restrict__ rec, int32_t n_slots, int64_t n_rows,
                                                  int32_t *__restrict__ out_idx, double *__restrict__ out_score)
 {
-    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (r >= n_rows) return;
-    JaroBest b = {-1.0, INT_MAX};
-    for (int s = 0; s < n_slots; ++s) {
-        const JaroRec e = rec[r * n_slots + s];
-        if (e.idx >= 0) take(b, e.score, e.idx);
-    }
-    out_idx[r] = b.idx == INT_MAX ? -1 : b.idx;
-    out_score[r] = b.idx == INT_MAX ? 0.0 : b.score;
+    best_merge(rec, n_slots, n_rows, out_idx, out_score);
 }
 
 static int jaro_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, int32_t scorer, const int32_t *skip_idx, int64_t begin,
@@ -347,7 +262,7 @@ static int jaro_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, in
     // groups whose to-strings all have <= 32 in 32-bit words; those from-strings against the groups of up to 256, and the
     // from-strings of 33 .. 64 characters against all groups of up to 256, in 64-bit words (four for a to-string's flags).
     // The groups are sorted by length: the first g32 / g256 of them qualify.
-    const bool lds_fits = (size_t)(pl->n_sym + 1) * sizeof(uint64_t) <= 60 * 1024;
+    const bool lds_fits = lds_table_fits(pl);
     const int32_t n_groups = (int32_t)pl->n_groups;
     auto whole_groups_up_to = [&](int64_t len) {
         int64_t n = 0;
@@ -369,7 +284,7 @@ static int jaro_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, in
     const size_t n32 = rows_reg.size();
     rows_reg.insert(rows_reg.end(), rows_64.begin(), rows_64.end());
 
-    DevBuf d_skip, d_oidx, d_oscore, d_matrix, d_rows_reg, d_rows_long, d_rec, d_pm, d_fa, d_fb, d_scored;
+    DevBuf d_skip, d_oidx, d_oscore, d_matrix, d_rows_reg, d_rows_long, d_rec, d_scored;
     int skip_up_to = 0;
     if (skip_idx) {
         std::vector<int32_t> codes(skip_idx, skip_idx + F->n);
@@ -405,30 +320,20 @@ static int jaro_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, in
         parts_long = (int32_t)std::max<int64_t>(1, std::min(want, cap));
     }
     const int32_t n_slots = std::max(std::max(reg[0].parts + reg[1].parts, reg[2].parts) + 1, parts_long);
-    const size_t rec_bytes = (size_t)n_rows * (size_t)n_slots * sizeof(JaroRec);
+    const size_t rec_bytes = (size_t)n_rows * (size_t)n_slots * sizeof(BestRec);
     PFZ_TRY(d_rec.alloc(ctx, rec_bytes));
     PFZ_HIP(hipMemsetAsync(d_rec.p, 0xff, rec_bytes, ctx->stream));      // idx = -1: no candidate
 
     JaroArgs A;
-    A.a_chars = F->chars;
-    A.a_width = F->char_width;
-    A.a_off = F->offsets;
-    A.lut = pl->lut;
-    A.lut_len = pl->lut_len;
-    A.b_packed = pl->packed;
-    A.g_off = pl->g_off;
-    A.g_steps = pl->g_steps;
-    A.b_len = pl->b_len;
-    A.b_orig = pl->b_orig;
+    static_cast<EditView &>(A) = edit_view(F, pl);
     A.skip_idx = skip_idx ? (const int32_t *)d_skip.p : nullptr;
     A.skip_up_to = skip_up_to;
-    A.n_sym1 = pl->n_sym + 1;
     A.winkler = scorer;
     A.from_begin = begin;
     A.n_to = n_to;
     A.matrix = out_matrix ? (double *)d_matrix.p : nullptr;
     A.n_slots = n_slots;
-    A.rec = (JaroRec *)d_rec.p;
+    A.rec = (BestRec *)d_rec.p;
     A.n_scored = nullptr;
     if (ctx->prof) {          // pfz_prof_get("k8_pairs_scored"): how many pairs the arg-max needed the float64 score of (read after the timed scope)
         PFZ_TRY(d_scored.alloc(ctx, sizeof(unsigned long long)));
@@ -468,27 +373,19 @@ static int jaro_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, in
             A.slot0 = pass == 0 ? n_slots - 1 : 0;
             const int32_t WA = pass == 0 ? 1 : (int32_t)((longest + 63) / 64);
             int64_t grid = std::min<int64_t>((int64_t)rows.size() * A.parts, max_grid);
-            const size_t pm_per = (size_t)A.n_sym1 * (size_t)WA * sizeof(uint64_t);
-            while (grid > 1 && pm_per * (size_t)grid > ((size_t)2 << 30)) grid /= 2;      // <= 2 GiB of match tables
-            if (pm_per * (size_t)grid > ((size_t)8 << 30)) {
-                set_error("pfz_jaro: a from-string of %lld characters with %d alphabet symbols needs a %zu-byte match table",
-                          (long long)longest, pl->n_sym, pm_per);
-                return PFZ_ERR_UNSUPPORTED;
-            }
+            PFZ_TRY(general_grid(&grid, A.n_sym1, WA, "pfz_jaro", "a from-string", longest));
             ProfScope ps(ctx, "k8_jaro_general");
-            PFZ_TRY(d_pm.alloc(ctx, pm_per * (size_t)grid));
-            PFZ_TRY(d_fa.alloc(ctx, (size_t)grid * (size_t)WA * 256 * sizeof(uint64_t)));
-            PFZ_TRY(d_fb.alloc(ctx, (size_t)grid * (size_t)WB * 256 * sizeof(uint64_t)));
-            PFZ_HIP(hipMemsetAsync(d_pm.p, 0, pm_per * (size_t)grid, ctx->stream));
+            GeneralBufs gb;      // (col[0]: the from-flags, col[1]: the to-flags)
+            PFZ_TRY(general_bufs_alloc(ctx, &gb, grid, A.n_sym1, WA, {WA, WB, 0}, 256));
             if (pl->idb == 8)
                 hipLaunchKernelGGL((k8_jaro_general_kernel<8>), dim3((unsigned)grid), dim3(256), 0, ctx->stream, A, WA, WB,
-                                   d_pm.as<uint64_t>(), d_fa.as<uint64_t>(), d_fb.as<uint64_t>());
+                                   gb.pm.as<uint64_t>(), gb.col[0].as<uint64_t>(), gb.col[1].as<uint64_t>());
             else
                 hipLaunchKernelGGL((k8_jaro_general_kernel<16>), dim3((unsigned)grid), dim3(256), 0, ctx->stream, A, WA, WB,
-                                   d_pm.as<uint64_t>(), d_fa.as<uint64_t>(), d_fb.as<uint64_t>());
+                                   gb.pm.as<uint64_t>(), gb.col[0].as<uint64_t>(), gb.col[1].as<uint64_t>());
             PFZ_HIP(hipGetLastError());
         }
-        hipLaunchKernelGGL(k8_merge, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, ctx->stream, (const JaroRec *)d_rec.p, n_slots,
+        hipLaunchKernelGGL(k8_merge, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, ctx->stream, (const BestRec *)d_rec.p, n_slots,
                            n_rows, d_oidx.as<int32_t>(), d_oscore.as<double>());
         PFZ_HIP(hipGetLastError());
     }

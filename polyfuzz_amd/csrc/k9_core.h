@@ -1,7 +1,8 @@
 // K9's per-pair logic: the unit-cost Levenshtein distance and the optimal-string-alignment (OSA) distance as the bit-vector
 // recurrence of Myers / Hyyro, on one 32- or 64-bit word per from-string or on several 64-bit words, and the float64 similarity.
-// Plain integer C++ (and one float64 formula), shared by the HIP kernels (k9_levenshtein.hip) and a host program that checks it
-// against the textbook table on the CPU (tests/k9_core_host.cpp).
+// Plain integer C++ (and one float64 formula), shared by the HIP kernels (k9_levenshtein.hip, k10_pairs.hip, k11_join.hip and
+// k12_components.hip through edit_walk.h) and a host program that checks it against the textbook table on the CPU
+// (tests/k9_core_host.cpp).
 //
 // The definition (rapidfuzz's Levenshtein.normalized_similarity / OSA.normalized_similarity, default arguments, on code points):
 //   d = the fewest unit-cost insertions, deletions and substitutions that turn a into b; OSA also counts the transposition of two
@@ -99,6 +100,37 @@ K9_HD void lev_step_word(uint64_t &vp, uint64_t &vn, uint64_t &d0_io, uint64_t e
     vp = hns | ~(d0 | hps);
     vn = hps & d0;
     d0_io = d0;
+}
+
+// A lane's multi-word column where the general kernels keep it: word w of VP / VN / D0 at vp / vn / d0[w * stride] (stride = the
+// lanes that interleave their columns: 256, or 64 in K10), W words for a from-string of la characters.
+#define K9_HD_FLAT K9_HD __attribute__((always_inline))
+
+K9_HD_FLAT void lev_column_begin(uint64_t *vp, uint64_t *vn, uint64_t *d0, int W, int la, int stride)
+{
+    for (int w = 0; w < W; ++w) {
+        vp[(int64_t)w * stride] = low_ones<uint64_t>(la - 64 * w);
+        vn[(int64_t)w * stride] = 0ull;
+        d0[(int64_t)w * stride] = 0ull;
+    }
+}
+
+// one to-character: eq / eq_prev = the W match words of this and of the previous to-character (eq_prev and d0 are read for OSA
+// alone); returns what dist moves by (`last` = bit la - 1 of the column's last word, 0 for an empty from-string)
+template <bool OSA>
+K9_HD_FLAT int lev_column_step(uint64_t *vp, uint64_t *vn, uint64_t *d0, const uint64_t *eq, const uint64_t *eq_prev, int W,
+                               uint64_t last, int stride)
+{
+    LevCarry cy = lev_carry_begin();
+    uint64_t hp = 0, hn = 0;
+    for (int w = 0; w < W; ++w) {
+        uint64_t x_vp = vp[(int64_t)w * stride], x_vn = vn[(int64_t)w * stride], x_d0 = OSA ? d0[(int64_t)w * stride] : 0ull;
+        lev_step_word<OSA>(x_vp, x_vn, x_d0, eq[w], OSA ? eq_prev[w] : 0ull, cy, &hp, &hn);
+        vp[(int64_t)w * stride] = x_vp;
+        vn[(int64_t)w * stride] = x_vn;
+        if (OSA) d0[(int64_t)w * stride] = x_d0;
+    }
+    return (int)((hp & last) != 0) - (int)((hn & last) != 0);
 }
 
 // float64, the definition's order of operations (a fused multiply-add has no place here, but say so)

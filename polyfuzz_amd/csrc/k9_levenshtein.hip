@@ -5,7 +5,8 @@
 // two as scorer(from, to) for every to-string, np.argmax (first maximum), np.max -- float64 on the 0..1 scale.  The definition and
 // the bit logic of one pair: k9_core.h.
 //
-// Mapping to CDNA4 -- K8's, on K4's to-side plan (k4_plan.h: alphabet of the to-list, to-strings sorted by length in groups of 64,
+// Mapping to CDNA4 -- K8's (the view of the plan, the match table, the row's best and its merge are the one copy in edit_walk.h),
+// on K4's to-side plan (k4_plan.h: alphabet of the to-list, to-strings sorted by length in groups of 64,
 // packed symbols), which is built once per to-list and cached on its handle:
 //   workgroup (4 waves) = one from-string: its match table PM[symbol] (bit i: a[i] == symbol) lives in LDS, built per from-string
 //     and cleared by the positions it set;
@@ -26,8 +27,7 @@
 // test, the same walk order, the same end of a direction.  The waves leave their lists side by side, in a buffer per launch
 // (rows of the class x its parts x 4 x ntop keys); topn_merge picks the row's.
 // Bound: integer VALU + LDS look-ups, one sweep per pair (measured beside K4 and K8).
-#include "k4_plan.h"
-#include "k9_core.h"
+#include "edit_walk.h"
 #include "topn_wave.h"
 
 #include <algorithm>
@@ -35,86 +35,21 @@
 
 namespace pfz {
 
-struct LevRec {
-    double score;
-    int32_t idx, pad;      // idx < 0: no candidate
-};
-
-struct LevArgs {
-    const void *a_chars;       // from-strings: code units of a_width bytes
-    int32_t a_width;
-    const int64_t *a_off;      // [n_from + 1]
-    const uint16_t *lut;       // code unit -> symbol rank (0 = not in the to-list's alphabet), lut_len entries
-    uint32_t lut_len;
+struct LevArgs : EditView {
     const int32_t *rows;       // from-rows of this launch
     int32_t n_rows;
-    const uint32_t *b_packed;  // to-strings, groups of 64, [t/PER][lane]
-    const int64_t *g_off;      // [n_groups] dword offset of each group
-    const int32_t *g_steps;    // [n_groups] dwords per lane
-    const int32_t *b_len;      // [n_groups*64]
-    const int32_t *b_orig;     // [n_groups*64] original to-index, -1 = padding lane
-    int32_t n_groups;
     const int32_t *skip_idx;   // [n_from] or NULL (decoded: pfz_internal.h decode_skip_codes)
     int32_t skip_up_to;
-    int32_t n_sym1;            // alphabet size + 1 (symbol 0 = padding)
     int64_t from_begin;
     int64_t n_to;
     int32_t *matrix;           // optional [(from_end-from_begin) * n_to] distances: every pair is walked
     int32_t parts;             // the to-groups of a from-string are split over `parts` workgroups, each pruning on its own best
     int32_t n_slots;           // part p of row r leaves its best in rec[(r - from_begin) * n_slots + p]
-    LevRec *rec;
+    BestRec *rec;
     unsigned long long *n_walked;   // optional: pairs whose recurrence was walked (the profile's work count)
     int32_t ntop;              // the top-n kernels: wave w of part p of row r leaves its list in
     TopnKey *lists;            // lists[((r * parts + p) * 4 + w) * ntop], r the row's place in `rows`: one buffer per launch
 };
-
-struct LevBest {
-    double score;        // -1: nothing yet
-    int idx;
-};
-
-__device__ inline void lev_take(LevBest &b, double score, int idx)
-{
-    if (score > b.score || (score == b.score && idx < b.idx)) {
-        b.score = score;
-        b.idx = idx;
-    }
-}
-
-// first maximum of the workgroup: (score desc, original index asc); thread 0 writes the record
-__device__ inline void lev_block_best(LevBest best, double *red_s, int *red_i, LevRec *dst)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) lev_take(best, __shfl_xor(best.score, d, 64), __shfl_xor(best.idx, d, 64));
-    if (lane == 0) {
-        red_s[wave] = best.score;
-        red_i[wave] = best.idx;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < 4; ++w) lev_take(best, red_s[w], red_i[w]);
-        dst->score = best.score;
-        dst->idx = best.idx == INT_MAX ? -1 : best.idx;
-    }
-}
-
-__device__ inline void lev_count_walked(unsigned long long *n_walked, int mine)
-{
-    if (!n_walked) return;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d, 64);
-    if ((threadIdx.x & 63) == 0) atomicAdd(n_walked, (unsigned long long)mine);
-}
-
-__device__ inline int lev_a_symbol(const LevArgs &A, int64_t at)
-{
-    const uint32_t c = A.a_width == 1 ? (uint32_t)((const uint8_t *)A.a_chars)[at] : ((const uint32_t *)A.a_chars)[at];
-    return c < A.lut_len ? (int)A.lut[c] : 0;
-}
-
-__device__ inline void lev_lds_or(uint32_t *p, uint32_t v) { atomicOr(p, v); }
-__device__ inline void lev_lds_or(uint64_t *p, uint64_t v) { atomicOr((unsigned long long *)p, (unsigned long long)v); }
 
 constexpr int K9_LDS_HEAD = 16;      // the workgroup's best in front of the match table (which stays 16-byte aligned)
 
@@ -131,8 +66,7 @@ __device__ __forceinline__ void k9_lev_body(const LevArgs &A)
     constexpr int PER = 32 / IDB;  // symbols per dword
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
-    for (int p = tid; p < A.n_sym1; p += 256) pm[p] = 0;
-    __syncthreads();
+    pm_reg_zero(A, pm, tid, 256);
 
     const int parts = A.parts;
     const bool prune = A.matrix == nullptr;
@@ -141,13 +75,14 @@ __device__ __forceinline__ void k9_lev_body(const LevArgs &A)
         const int row = A.rows[r];
         const int64_t a0 = A.a_off[row];
         const int la = (int)(A.a_off[row + 1] - a0);      // fits the WORD
-        const int my_sym = tid < la ? lev_a_symbol(A, a0 + tid) : 0;
-        if (my_sym) lev_lds_or(&pm[my_sym], (WORD)1 << tid);
+        // (pm_reg_set, with the workgroup's best reset in front of its barrier)
+        const int my_sym = tid < la ? edit_symbol(A, A.a_chars, A.a_width, a0 + tid) : 0;
+        if (my_sym) lds_or(&pm[my_sym], (WORD)1 << tid);
         if (tid == 0) *wg_best = 0ull;                     // +0.0: no bound is below it
         __syncthreads();
 
         const int skip = A.skip_idx ? A.skip_idx[row] : -1;
-        LevBest best = {-1.0, INT_MAX};
+        ScoreBest best = {-1.0, INT_MAX};
         TopnList list = topn_empty();
         int walked = 0;
         // this wave's groups: base + stride * k, k < K (wave-uniform: say so, or the loops below get a per-lane trip count)
@@ -211,17 +146,16 @@ __device__ __forceinline__ void k9_lev_body(const LevArgs &A)
             if (A.matrix) A.matrix[((int64_t)row - A.from_begin) * A.n_to + orig] = d;
             if (out) continue;
             const double sc = lev_similarity(d, la, lb);
-            lev_take(best, sc, orig);
+            best_take(best, sc, orig);
             if (prune && sc > wb) atomicMax(wg_best, (unsigned long long)__double_as_longlong(sc));
         }
         if constexpr (TOPN) {
             topn_store(list, A.ntop, A.lists + (((int64_t)r * parts + part) * 4 + wave) * A.ntop);
             __syncthreads();      // (every wave is done with the match table)
         }
-        else lev_block_best(best, red_s, red_i, A.rec + ((int64_t)row - A.from_begin) * A.n_slots + part);
-        lev_count_walked(A.n_walked, walked);
-        if (my_sym) pm[my_sym] = 0;      // clear the entries of this from-string
-        __syncthreads();
+        else best_of_block(best, red_s, red_i, A.rec + ((int64_t)row - A.from_begin) * A.n_slots + part);
+        wave_count(A.n_walked, walked);
+        pm_reg_clear(pm, my_sym);
     }
 }
 
@@ -259,15 +193,10 @@ __device__ __forceinline__ void k9_lev_general_body(const LevArgs &A, int32_t WA
         const int64_t a0 = A.a_off[row];
         const int la = (int)(A.a_off[row + 1] - a0);
         const int W = la > 0 ? (la + 63) / 64 : 1;                    // <= WA
-        for (int p = tid; p < la; p += 256) {
-            const int sy = lev_a_symbol(A, a0 + p);
-            if (sy) atomicOr((unsigned long long *)&pm[(int64_t)sy * WA + p / 64], 1ull << (p % 64));
-        }
-        __threadfence_block();
-        __syncthreads();
+        pm_global_set(A, pm, WA, a0, la, tid, 256);
         const int skip = A.skip_idx ? A.skip_idx[row] : -1;
         const uint64_t last = la > 0 ? 1ull << ((la - 1) % 64) : 0ull;
-        LevBest best = {-1.0, INT_MAX};
+        ScoreBest best = {-1.0, INT_MAX};
         TopnList list = topn_empty();
         int walked = 0;
         for (int g = wave + 4 * part; g < A.n_groups; g += 4 * parts) {
@@ -288,6 +217,7 @@ __device__ __forceinline__ void k9_lev_general_body(const LevArgs &A, int32_t WA
                 for (int q = 0; q < PER; ++q) {
                     if (t * PER + q >= lb) continue;                    // padding behind the string's end
                     const uint32_t c = (pk >> (q * IDB)) & ((1u << IDB) - 1u);
+                    // (lev_column_step, written out: through the helper this kernel's OSA instances need up to four registers more)
                     const uint64_t *eq = pm + (int64_t)c * WA, *eq_prev = pm + (int64_t)c_prev * WA;
                     LevCarry cy = lev_carry_begin();
                     uint64_t hp = 0, hn = 0;
@@ -311,21 +241,16 @@ __device__ __forceinline__ void k9_lev_general_body(const LevArgs &A, int32_t WA
                 ++walked;
                 const int d = lev_distance(dist, la, lb);
                 if (A.matrix) A.matrix[((int64_t)row - A.from_begin) * A.n_to + orig] = d;
-                if (!choice_left_out(orig, skip, A.skip_up_to)) lev_take(best, lev_similarity(d, la, lb), orig);
+                if (!choice_left_out(orig, skip, A.skip_up_to)) best_take(best, lev_similarity(d, la, lb), orig);
             }
         }
         if constexpr (TOPN) {
             topn_store(list, A.ntop, A.lists + (((int64_t)r * parts + part) * 4 + wave) * A.ntop);
             __syncthreads();      // (every wave is done with the match table)
         }
-        else lev_block_best(best, red_s, red_i, A.rec + ((int64_t)row - A.from_begin) * A.n_slots + part);
-        lev_count_walked(A.n_walked, walked);
-        for (int p = tid; p < la; p += 256) {
-            const int sy = lev_a_symbol(A, a0 + p);
-            if (sy) pm[(int64_t)sy * WA + p / 64] = 0ull;
-        }
-        __threadfence_block();
-        __syncthreads();
+        else best_of_block(best, red_s, red_i, A.rec + ((int64_t)row - A.from_begin) * A.n_slots + part);
+        wave_count(A.n_walked, walked);
+        pm_global_clear(A, pm, WA, a0, la, tid, 256);
     }
 }
 
@@ -346,33 +271,19 @@ __global__ __launch_bounds__(256) void k9_lev_general_topn_kernel(LevArgs A, int
 }
 
 // the first maximum of every from-string over the records its launch left
-__global__ __launch_bounds__(256) void k9_merge(const LevRec *__restrict__ rec, int32_t n_slots, int64_t n_rows,
+__global__ __launch_bounds__(256) void k9_merge(const BestRec *__restrict__ rec, int32_t n_slots, int64_t n_rows,
                                                  int32_t *__restrict__ out_idx, double *__restrict__ out_score)
 {
-    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (r >= n_rows) return;
-    LevBest b = {-1.0, INT_MAX};
-    for (int s = 0; s < n_slots; ++s) {
-        const LevRec e = rec[r * n_slots + s];
-        if (e.idx >= 0) lev_take(b, e.score, e.idx);
-    }
-    out_idx[r] = b.idx == INT_MAX ? -1 : b.idx;
-    out_score[r] = b.idx == INT_MAX ? 0.0 : b.score;
+    best_merge(rec, n_slots, n_rows, out_idx, out_score);
 }
 
 template <typename WORD>
 static void launch_reg(const LevArgs &A, int idb, int osa, dim3 grid, size_t lds, hipStream_t st)
 {
-    if (A.ntop > 0) {
-        if (idb == 8 && !osa) hipLaunchKernelGGL((k9_lev_topn_kernel<WORD, 8, false>), grid, dim3(256), lds, st, A);
-        else if (idb == 8) hipLaunchKernelGGL((k9_lev_topn_kernel<WORD, 8, true>), grid, dim3(256), lds, st, A);
-        else if (!osa) hipLaunchKernelGGL((k9_lev_topn_kernel<WORD, 16, false>), grid, dim3(256), lds, st, A);
-        else hipLaunchKernelGGL((k9_lev_topn_kernel<WORD, 16, true>), grid, dim3(256), lds, st, A);
-    }
-    else if (idb == 8 && !osa) hipLaunchKernelGGL((k9_lev_kernel<WORD, 8, false>), grid, dim3(256), lds, st, A);
-    else if (idb == 8) hipLaunchKernelGGL((k9_lev_kernel<WORD, 8, true>), grid, dim3(256), lds, st, A);
-    else if (!osa) hipLaunchKernelGGL((k9_lev_kernel<WORD, 16, false>), grid, dim3(256), lds, st, A);
-    else hipLaunchKernelGGL((k9_lev_kernel<WORD, 16, true>), grid, dim3(256), lds, st, A);
+    dispatch_idb_osa(idb, osa != 0, [&](auto IDB, auto OSA) {
+        if (A.ntop > 0) hipLaunchKernelGGL((k9_lev_topn_kernel<WORD, decltype(IDB)::value, decltype(OSA)::value>), grid, dim3(256), lds, st, A);
+        else hipLaunchKernelGGL((k9_lev_kernel<WORD, decltype(IDB)::value, decltype(OSA)::value>), grid, dim3(256), lds, st, A);
+    });
 }
 
 static int lev_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, int32_t scorer, const int32_t *skip_idx, int64_t begin,
@@ -397,17 +308,10 @@ static int lev_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, int
 
     // The register kernel's share, while the match table fits 60 KiB of LDS (K4's limit): from-strings of <= 32 characters in
     // 32-bit words, of 33 .. 64 in 64-bit words, each against every group.  Everything else is the general kernel's.
-    const bool lds_fits = (size_t)(pl->n_sym + 1) * sizeof(uint64_t) <= 60 * 1024;
-    std::vector<int32_t> rows_cls[3];      // <= 32, 33 .. 64, the general kernel's
-    int64_t longest = 1;
-    for (int64_t i = begin; i < end; ++i) {
-        const int64_t la = F->h_off[(size_t)i + 1] - F->h_off[(size_t)i];
-        const int cls = !lds_fits || la > 64 ? 2 : (la > 32 ? 1 : 0);
-        rows_cls[cls].push_back((int32_t)i);
-        if (cls == 2) longest = std::max(longest, la);
-    }
+    const RowClasses rc = classify_rows(F, begin, end, lds_table_fits(pl));
+    const std::vector<int32_t> (&rows_cls)[3] = rc.rows;      // <= 32, 33 .. 64, the general kernel's
 
-    DevBuf d_skip, d_oidx, d_oscore, d_matrix, d_rows[3], d_lists[3], d_rec, d_pm, d_vp, d_vn, d_d0, d_walked;
+    DevBuf d_skip, d_oidx, d_oscore, d_matrix, d_rows[3], d_lists[3], d_rec, d_walked;
     int skip_up_to = 0;
     if (skip_idx) {
         std::vector<int32_t> codes(skip_idx, skip_idx + F->n);
@@ -436,7 +340,7 @@ static int lev_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, int
         n_slots = std::max(n_slots, parts[c]);
     }
     // (top-n: every class has a list buffer of its own -- rows of the class x ITS parts x 4 waves x ntop keys, all of them written)
-    const size_t rec_bytes = ntop > 0 ? 0 : (size_t)n_rows * (size_t)n_slots * sizeof(LevRec);
+    const size_t rec_bytes = ntop > 0 ? 0 : (size_t)n_rows * (size_t)n_slots * sizeof(BestRec);
     PFZ_TRY(d_rec.alloc(ctx, rec_bytes));
     if (rec_bytes) PFZ_HIP(hipMemsetAsync(d_rec.p, 0xff, rec_bytes, ctx->stream));      // idx = -1: no candidate
     if (ntop > 0)
@@ -444,25 +348,14 @@ static int lev_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, int
             if (parts[c] != 0) PFZ_TRY(d_lists[c].alloc(ctx, rows_cls[c].size() * (size_t)parts[c] * 4 * (size_t)ntop * sizeof(TopnKey)));
 
     LevArgs A;
-    A.a_chars = F->chars;
-    A.a_width = F->char_width;
-    A.a_off = F->offsets;
-    A.lut = pl->lut;
-    A.lut_len = pl->lut_len;
-    A.b_packed = pl->packed;
-    A.g_off = pl->g_off;
-    A.g_steps = pl->g_steps;
-    A.b_len = pl->b_len;
-    A.b_orig = pl->b_orig;
-    A.n_groups = n_groups;
+    static_cast<EditView &>(A) = edit_view(F, pl);
     A.skip_idx = skip_idx ? (const int32_t *)d_skip.p : nullptr;
     A.skip_up_to = skip_up_to;
-    A.n_sym1 = pl->n_sym + 1;
     A.from_begin = begin;
     A.n_to = n_to;
     A.matrix = out_matrix ? (int32_t *)d_matrix.p : nullptr;
     A.n_slots = n_slots;
-    A.rec = (LevRec *)d_rec.p;
+    A.rec = (BestRec *)d_rec.p;
     A.ntop = ntop;
     A.lists = nullptr;
     A.n_walked = nullptr;
@@ -491,36 +384,22 @@ static int lev_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, int
             A.n_rows = (int32_t)rows_cls[2].size();
             A.parts = parts[2];
             A.lists = d_lists[2].as<TopnKey>();
-            const int32_t WA = (int32_t)((longest + 63) / 64);
+            const int32_t WA = (int32_t)((rc.longest + 63) / 64);
             int64_t grid = std::min<int64_t>((int64_t)A.n_rows * A.parts, max_grid);
-            const size_t pm_per = (size_t)A.n_sym1 * (size_t)WA * sizeof(uint64_t);
-            while (grid > 1 && pm_per * (size_t)grid > ((size_t)2 << 30)) grid /= 2;      // <= 2 GiB of match tables
-            if (pm_per * (size_t)grid > ((size_t)8 << 30)) {
-                set_error("pfz_lev: a from-string of %lld characters with %d alphabet symbols needs a %zu-byte match table",
-                          (long long)longest, pl->n_sym, pm_per);
-                return PFZ_ERR_UNSUPPORTED;
-            }
+            PFZ_TRY(general_grid(&grid, A.n_sym1, WA, "pfz_lev", "a from-string", rc.longest));
             ProfScope ps(ctx, "k9_lev_general");
-            const size_t col_bytes = (size_t)grid * (size_t)WA * 256 * sizeof(uint64_t);
-            PFZ_TRY(d_pm.alloc(ctx, pm_per * (size_t)grid));
-            PFZ_TRY(d_vp.alloc(ctx, col_bytes));
-            PFZ_TRY(d_vn.alloc(ctx, col_bytes));
-            PFZ_TRY(d_d0.alloc(ctx, col_bytes));
-            PFZ_HIP(hipMemsetAsync(d_pm.p, 0, pm_per * (size_t)grid, ctx->stream));
-#define PFZ_K9_GENERAL(IDB, OSA)                                                                                             \
-    do {                                                                                                                     \
-        if (ntop > 0)                                                                                                        \
-            hipLaunchKernelGGL((k9_lev_general_topn_kernel<IDB, OSA>), dim3((unsigned)grid), dim3(256), 0, ctx->stream, A,   \
-                               WA, d_pm.as<uint64_t>(), d_vp.as<uint64_t>(), d_vn.as<uint64_t>(), d_d0.as<uint64_t>());      \
-        else                                                                                                                 \
-            hipLaunchKernelGGL((k9_lev_general_kernel<IDB, OSA>), dim3((unsigned)grid), dim3(256), 0, ctx->stream, A, WA,    \
-                               d_pm.as<uint64_t>(), d_vp.as<uint64_t>(), d_vn.as<uint64_t>(), d_d0.as<uint64_t>());          \
-    } while (0)
-            if (pl->idb == 8 && !scorer) PFZ_K9_GENERAL(8, false);
-            else if (pl->idb == 8) PFZ_K9_GENERAL(8, true);
-            else if (!scorer) PFZ_K9_GENERAL(16, false);
-            else PFZ_K9_GENERAL(16, true);
-#undef PFZ_K9_GENERAL
+            GeneralBufs gb;
+            PFZ_TRY(general_bufs_alloc(ctx, &gb, grid, A.n_sym1, WA, {WA, WA, WA}, 256));
+            dispatch_idb_osa(pl->idb, scorer != 0, [&](auto IDB, auto OSA) {
+                if (ntop > 0)
+                    hipLaunchKernelGGL((k9_lev_general_topn_kernel<decltype(IDB)::value, decltype(OSA)::value>), dim3((unsigned)grid), dim3(256), 0,
+                                       ctx->stream, A, WA, gb.pm.as<uint64_t>(), gb.col[0].as<uint64_t>(), gb.col[1].as<uint64_t>(),
+                                       gb.col[2].as<uint64_t>());
+                else
+                    hipLaunchKernelGGL((k9_lev_general_kernel<decltype(IDB)::value, decltype(OSA)::value>), dim3((unsigned)grid), dim3(256), 0,
+                                       ctx->stream, A, WA, gb.pm.as<uint64_t>(), gb.col[0].as<uint64_t>(), gb.col[1].as<uint64_t>(),
+                                       gb.col[2].as<uint64_t>());
+            });
             PFZ_HIP(hipGetLastError());
         }
         if (ntop > 0) {
@@ -530,7 +409,7 @@ static int lev_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, int
                                        d_oidx.as<int32_t>(), d_oscore.as<double>(), ctx->stream));
         }
         else
-            hipLaunchKernelGGL(k9_merge, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, ctx->stream, (const LevRec *)d_rec.p, n_slots,
+            hipLaunchKernelGGL(k9_merge, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, ctx->stream, (const BestRec *)d_rec.p, n_slots,
                                n_rows, d_oidx.as<int32_t>(), d_oscore.as<double>());
         PFZ_HIP(hipGetLastError());
     }

@@ -119,6 +119,36 @@ def test_bit_logic_matches_the_definition(host):
     assert (osa <= lev).all() and (osa < lev).sum() > 50
 
 
+COLUMN_FROM_LENGTHS = (0, 1, 63, 64, 65, 128, 129, 200)
+COLUMN_TO_LENGTHS = (0, 1, 70)
+
+
+@pytest.mark.parametrize("stride", (64, 256))
+def test_shared_column_walk_matches_the_definition(host, stride):
+    """lev_column_begin / lev_column_step -- the one multi-word column all four general kernels walk -- at both lane strides (256:
+    K9, K11, K12; 64: K10), both scorers, from-lengths at every word border, to-lengths 0, 1 and 70 on more lanes than one stride
+    holds, and a match table of WA = 4 words per symbol: W < WA for every from-string but the longest, W == WA for that one
+    (the words beyond W must stay untouched: the host program poisons and checks them)"""
+    rng = np.random.default_rng(94)
+    fl = [s for n in COLUMN_FROM_LENGTHS for s in _rand(rng, "ab", n, n, 2) + _rand(rng, "abcdefghi", n, n, 2)] + ["zq" * 35, "ab" * 100]
+    tl = [""] + list("abz") + _rand(rng, "ab", 70, 70, 30) + _rand(rng, "abcdefghi", 70, 70, 30) + ["ba" * 35, "ab" * 35]
+    tl += [s[:70] for s in fl if len(s) >= 128] + [""]
+    assert set(COLUMN_FROM_LENGTHS) <= {len(s) for s in fl} and {len(s) for s in tl} == set(COLUMN_TO_LENGTHS) and len(tl) > 64
+    rank = {c: k + 1 for k, c in enumerate(sorted({c for s in tl for c in s}))}
+    (a, a_off), (b, b_off) = _symbols(fl, rank), _symbols(tl, rank)
+    p = lambda x: x.ctypes.data_as(ctypes.c_void_p)
+    WA = (max(map(len, fl)) + 63) // 64
+    assert WA == 4 and {(len(s) + 63) // 64 for s in fl} >= {0, 1, 2, 3, 4}
+    for osa, scorer in enumerate(lev_oracle.SCORERS):
+        out = np.empty((len(fl), len(tl)), np.int32)
+        host.k9_host_column.restype = ctypes.c_int
+        rc = host.k9_host_column(osa, stride, WA, ctypes.c_int64(len(fl)), p(a), p(a_off), ctypes.c_int64(len(tl)), p(b), p(b_off),
+                                 len(rank) + 1, p(out))
+        assert rc == 0, rc
+        np.testing.assert_array_equal(out, lev_oracle.matrix(fl, tl, scorer), err_msg=f"{scorer} stride {stride}")
+        np.testing.assert_array_equal(out, _host_distances(host, 0, fl, tl, osa))
+
+
 def test_similarity_formula_and_length_bound(host):
     """k9_core.h's float64 similarity == numpy's for every d <= M < 400; distinct d / M give distinct scores and equal fractions
     equal ones (what lets the kernel order pairs by the float64 values); the length bound is the score of d = | |a| - |b| |, and no

@@ -383,3 +383,68 @@ def test_matcher(ctx, golden):
         assert df["To"].tolist() == [dup[j] for j in s_idx]
         np.testing.assert_array_equal(df["Similarity"].to_numpy(), s_score)
         assert (s_score[:30] == 1.0).all()                  # (the repeats find their twins)
+
+
+FAMILY_LENGTHS = (0, 1, 31, 32, 33, 63, 64, 65, 128, 129)
+
+
+def _family_list(rng, wide):
+    """130 strings -- two full plan groups and a padded one -- 13 of each length of FAMILY_LENGTHS: prefixes of one sentence with
+    a few characters replaced and a few adjacent ones swapped, so that many pairs are near each other.  wide: the replacements
+    come from 400 code points of their own (more than 256 symbols: the plan packs 16 bits per symbol), else from eight letters"""
+    base = "the quick brown fox jumps over the lazy dog and runs far away from home again, and then it sleeps " * 2
+    pool = [chr(0x100 + k) for k in range(400)] if wide else list("abcdefgh")
+    out = []
+    for k in range(13):
+        for n in FAMILY_LENGTHS:
+            s = list(base[k % 3:k % 3 + n])
+            places = rng.choice(n, min(n, int(rng.integers(0, 5)) + (n // 8 if wide else 0)), replace=False) if n else []
+            for p in places:
+                s[p] = pool[int(rng.integers(len(pool)))]
+            out.append(_swapped(rng, "".join(s), int(rng.integers(0, 3))))
+    if wide:      # every code point of the pool is in the list: the alphabet is wider than 8 bits whatever the draws were
+        out[-1] = "".join(pool[:129])
+        out[-2] = "".join(pool[129:257])
+    return out
+
+
+@pytest.mark.parametrize("wide", (False, True), ids=("symbols8", "symbols16"))
+def test_the_four_entries_agree_on_one_list(ctx, wide):
+    """K9's matrix, K11's join (two lists at t = 0, self at t = 0.5), K12's components and K10's rescoring on ONE list of 130
+    strings against the oracle and each other: from-strings of all three row classes (<= 32, 33 .. 64, the general kernel's at two
+    and three words), the general kernels at 256 lanes (K9, K11, K12) and at 64 (K10), 8- and 16-bit symbols, both scorers"""
+    from polyfuzz_amd import _lib
+    sl = _family_list(np.random.default_rng(97 + wide), wide)
+    n = len(sl)
+    assert n == 130 and sorted(set(map(len, sl))) == list(FAMILY_LENGTHS)
+    assert (len({c for s in sl for c in s}) > 256) == wide
+    f, t = _lib.DeviceStrings.upload(ctx, sl), _lib.DeviceStrings.upload(ctx, sl)
+    every = _lib.DeviceTopN.from_host(ctx, np.tile(np.arange(n, dtype=np.int32), (n, 1)), np.zeros((n, n), np.float32))
+    assert n <= _lib.PAIR_MAX_CANDIDATES
+    upper = np.triu(np.ones((n, n), bool), 1)
+    for name in SCORERS:
+        want = lev_oracle.matrix(sl, sl, name)
+        sim = lev_oracle.sim_matrix(sl, sl, want)
+        np.testing.assert_array_equal(_lib.lev_matrix(ctx, f, t, name), want, err_msg=name)
+        # t = 0 over two lists: every pair, with exactly those distances
+        row_ptr, idx, dist, got_sim = _lib.lev_join(ctx, f, t, name, 0.0, capacity=n * n)
+        np.testing.assert_array_equal(row_ptr, np.arange(n + 1, dtype=np.int64) * n, err_msg=name)
+        np.testing.assert_array_equal(idx.reshape(n, n), np.tile(np.arange(n, dtype=np.int32), (n, 1)), err_msg=name)
+        np.testing.assert_array_equal(dist.reshape(n, n), want, err_msg=name)
+        np.testing.assert_array_equal(got_sim.reshape(n, n), sim, err_msg=name)
+        # t = 0.5 over the list itself: the unordered pairs, and K12 walks what K11 walks
+        hits = int((upper & (sim >= 0.5)).sum())
+        assert 100 < hits < upper.sum()
+        row_ptr, idx, dist, _, work = _lib.lev_join(ctx, f, None, name, 0.5, counters=True)
+        assert row_ptr[-1] == hits == len(idx), name
+        rows = np.repeat(np.arange(n), np.diff(row_ptr))
+        assert (rows < idx).all() and (sim[rows, idx] >= 0.5).all()
+        np.testing.assert_array_equal(dist, want[rows, idx], err_msg=name)
+        label, pairs, components, comp_work = _lib.lev_components(ctx, f, name, 0.5, counters=True)
+        assert pairs == hits and comp_work == work, (name, pairs, hits, comp_work, work)
+        assert 1 <= components <= n and (label <= np.arange(n)).all() and (label[rows] == label[idx]).all()
+        # K10 over every to-index as a candidate: the row's eight best, (score descending, index ascending)
+        order = np.argsort(-sim, axis=1, kind="stable")[:, :8]
+        got_idx, got_score = _lib.pairs_rescore_topn(ctx, f, t, every, name, 8)
+        np.testing.assert_array_equal(got_idx, order.astype(np.int32), err_msg=name)
+        np.testing.assert_array_equal(got_score, np.take_along_axis(sim, order, axis=1), err_msg=name)
