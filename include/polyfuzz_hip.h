@@ -448,6 +448,42 @@ int pfz_lev_join(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_string
 int pfz_lev_components(pfz_ctx *ctx, const pfz_strings *strings, int32_t scorer, double min_similarity, int32_t *out_label,
                        int64_t *out_pairs, int64_t *out_components, int64_t *out_counters);
 
+/* ---- K13: all pairs at or above an Indel similarity, and their components ------
+ * The threshold form of K4's metric on the 0..1 scale: rapidfuzz.distance.Indel.normalized_similarity, default arguments, on
+ * code points.  lcs = the length of the longest common subsequence of a and b, S = |a| + |b|, d = S - 2 lcs (the fewest
+ * insertions and deletions that turn a into b);  sim = 1.0 - (double)d / (double)S, 1.0 when S = 0 -- one division, one
+ * subtraction, not fused.  rapidfuzz.fuzz.ratio (pfz_indel_argmax) is this value times 100.
+ * pfz_indel_join: every pair (from i, to j) with sim(i, j) >= min_similarity, float64 against float64 (equal is a hit).  The
+ * contract is pfz_lev_join's, word for word, without the scorer argument: to_strings == NULL or the from-list's own handle is
+ * the self-join (every unordered pair i < j once, as row i, to-index j; never (i, i)); the output is CSR over the from-rows in
+ * host buffers, the to-index ascending within a row, out_dist[p] = d = S - 2 lcs, out_sim[p] = sim; the same call gives the same
+ * bytes every time.  capacity: the hits the three arrays have room for (they may be NULL when it is 0); *out_total is always
+ * the exact number of hits; when it exceeds `capacity` the call returns PFZ_OK, has written NONE of the four output arrays (the
+ * device never writes a hit past the capacity either) and is to be repeated with capacity >= *out_total.  out_counters: NULL,
+ * or int64[3] with pfz_lev_join's meaning -- [0] pairs inside the length window, [1] those walked to their end, [2] recurrence
+ * steps of live lanes.
+ * Exact: a pair is left unwalked or abandoned only where the formula, applied to an upper bound of lcs -- min(|a|, |b|), or the
+ * LCS so far plus the to-characters still to come --, is < min_similarity (csrc/k13_core.h).
+ * From-strings of up to 64 characters run in registers; longer ones (and alphabets whose match table exceeds 60 KiB) in a
+ * general -- slow -- kernel.  The to-side preparation is pfz_indel_*'s, cached on the to-list's handle.
+ * Limits of the packed hit (row, to-index, lcs; PFZ_ERR_UNSUPPORTED beyond): lists of at most 2^24 strings, strings of at most
+ * 65 535 characters.  A NaN min_similarity or one outside [0, 1], capacity < 0: PFZ_ERR_INVALID.  Blocks. */
+int pfz_indel_join(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings, double min_similarity,
+                   int64_t capacity, int64_t *out_row_ptr, int32_t *out_idx, int32_t *out_dist, double *out_sim,
+                   int64_t *out_total, int64_t *out_counters);
+/* The connected components of "Indel similarity >= min_similarity" over ONE list; the contract is pfz_lev_components's without
+ * the scorer argument.  The pairs are those of pfz_indel_join(ctx, strings, NULL, min_similarity, ...), found by the same walk
+ * and united where they are found in the lock-free union-find of csrc/k12_core.h: O(n) device memory, no pair is stored or
+ * downloaded.  out_label: host buffer int32[n], out_label[i] = the SMALLEST position in i's component; deterministic.
+ * *out_pairs == pfz_indel_join's *out_total; *out_components counts singletons too; out_counters as above.
+ * strings->n == 0: PFZ_OK, *out_pairs = *out_components = 0, nothing else is written (out_label may be NULL).
+ * Limits: the packed-hit limits do not apply.  Positions and the sum of two lengths are 32-bit: more than 2^31 - 65 strings, or
+ * a string of 2^30 characters or more, is PFZ_ERR_UNSUPPORTED, as is a string beyond 64 characters whose match table in the
+ * general kernel would exceed 8 GiB.  A NaN min_similarity or one outside [0, 1], a NULL out_pairs / out_components:
+ * PFZ_ERR_INVALID.  Blocks. */
+int pfz_indel_components(pfz_ctx *ctx, const pfz_strings *strings, double min_similarity, int32_t *out_label,
+                         int64_t *out_pairs, int64_t *out_components, int64_t *out_counters);
+
 /* ---- K10: a candidate table rescored by edit distance ----------------------
  * Blocking, then exact scoring: extends the reference's edit-distance loop (polyfuzz/models/_distance.py:89-102: scorer(from, to)
  * for every to-string, then the best) restricted to the candidates a cheap matcher left per from-string (the top_n table of

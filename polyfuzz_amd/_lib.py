@@ -101,6 +101,8 @@ SIGNATURES = {
     "pfz_lev_matrix_host": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_vp]),
     "pfz_lev_join": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_f64, c_i64, c_vp, c_vp, c_vp, c_vp, P(c_i64), c_vp]),
     "pfz_lev_components": (ctypes.c_int, [c_vp, c_vp, c_i32, c_f64, c_vp, P(c_i64), P(c_i64), c_vp]),
+    "pfz_indel_join": (ctypes.c_int, [c_vp, c_vp, c_vp, c_f64, c_i64, c_vp, c_vp, c_vp, c_vp, P(c_i64), c_vp]),
+    "pfz_indel_components": (ctypes.c_int, [c_vp, c_vp, c_f64, c_vp, P(c_i64), P(c_i64), c_vp]),
     "pfz_pairs_rescore_topn": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
     "pfz_fuzz_extract_one": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "pfz_fuzz_extract_one_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
@@ -866,6 +868,68 @@ def lev_components(ctx, dev, scorer, min_similarity, counters=False):
     pairs, components = c_i64(0), c_i64(0)
     check(ctx.lib.pfz_lev_components(ctx.h, dev.h, LEV_SCORERS[scorer], float(min_similarity), _ptr(label), ctypes.byref(pairs),
                                      ctypes.byref(components), _ptr(work)))
+    out = (label, pairs.value, components.value)
+    return out + (dict(zip(LEV_JOIN_COUNTERS, work.tolist())),) if counters else out
+
+
+# K13: rapidfuzz.distance.Indel.normalized_similarity (K4's metric on the 0..1 scale), the definition of include/polyfuzz_hip.h
+
+def indel_similarity(lcs, total_len):
+    """1.0 - (S - 2 lcs) / S in float64 (one division, one subtraction), 1.0 where S = |a| + |b| is 0; arrays broadcast"""
+    lcs, s = np.asarray(lcs, np.int64), np.asarray(total_len, np.int64)
+    pos = s > 0
+    return np.where(pos, 1.0 - (s - 2 * lcs).astype(np.float64) / np.where(pos, s, 1).astype(np.float64), 1.0)
+
+
+def indel_lcs_of_ratio(ratio, total_len):
+    """The integer LCS behind K4's float64 ratio (0..100) of pairs whose two lengths sum to total_len: the integer near
+    ratio * S / 200 (or one beside it) whose (1.0 - (S - 2 lcs) / S) * 100.0 reproduces the ratio's bits.  Raises ValueError
+    where no such integer exists -- then the ratio is not K4's for these lengths.  Vectorised; no per-character work."""
+    ratio, s = np.asarray(ratio, np.float64), np.asarray(total_len, np.int64)
+    ratio, s = np.broadcast_arrays(ratio, s)
+    guess = np.rint(ratio * s / 200.0).astype(np.int64)
+    lcs = np.full(ratio.shape, -1, np.int64)
+    for cand in (guess, guess - 1, guess + 1):
+        cand = np.clip(cand, 0, s // 2)
+        ok = (lcs < 0) & (indel_similarity(cand, s) * 100.0 == ratio)
+        lcs[ok] = cand[ok]
+    if (lcs < 0).any():
+        bad = int(np.flatnonzero((lcs < 0).reshape(-1))[0])
+        raise ValueError(f"ratio {ratio.reshape(-1)[bad]!r} is no Indel ratio of two strings of {int(s.reshape(-1)[bad])} characters in all")
+    return lcs
+
+
+def indel_join(ctx, from_dev, to_dev, min_similarity, capacity=None, counters=False):
+    """K13: lev_join's twin under the Indel similarity (rapidfuzz.distance.Indel.normalized_similarity): every pair with
+    similarity >= min_similarity as CSR over the from-rows -- (row_ptr int64[n + 1], to-index int32[hits] ascending within a
+    row, Indel distance |a| + |b| - 2 lcs int32[hits], similarity float64[hits]).  to_dev None (or from_dev itself): the
+    self-join, i < j.  capacity and the ONE repeat as in lev_join; counters=True appends a dict of LEV_JOIN_COUNTERS."""
+    work = np.zeros(3, np.int64) if counters else None
+    total = c_i64(0)
+    to_h = None if to_dev is None else to_dev.h
+    cap = max(4096, 4 * int(from_dev.n)) if capacity is None else int(capacity)
+    for _ in range(2):
+        row_ptr = np.empty(from_dev.n + 1, np.int64)
+        idx, dist, sim = np.empty(cap, np.int32), np.empty(cap, np.int32), np.empty(cap, np.float64)
+        check(ctx.lib.pfz_indel_join(ctx.h, from_dev.h, to_h, float(min_similarity), cap, _ptr(row_ptr), _ptr(idx), _ptr(dist),
+                                     _ptr(sim), ctypes.byref(total), _ptr(work)))
+        if total.value <= cap:
+            break
+        cap = total.value
+    assert total.value <= cap                     # (the second call had room for the exact total)
+    n = total.value
+    out = (row_ptr, idx[:n].copy(), dist[:n].copy(), sim[:n].copy())
+    return out + (dict(zip(LEV_JOIN_COUNTERS, work.tolist())),) if counters else out
+
+
+def indel_components(ctx, dev, min_similarity, counters=False):
+    """K13: lev_components's twin under the Indel similarity -- (label int32[n], pairs, components), the pairs of indel_join's
+    self-join united on the device, never stored.  counters=True appends a dict of LEV_JOIN_COUNTERS."""
+    work = np.zeros(3, np.int64) if counters else None
+    label = np.empty(dev.n, np.int32)
+    pairs, components = c_i64(0), c_i64(0)
+    check(ctx.lib.pfz_indel_components(ctx.h, dev.h, float(min_similarity), _ptr(label), ctypes.byref(pairs), ctypes.byref(components),
+                                       _ptr(work)))
     out = (label, pairs.value, components.value)
     return out + (dict(zip(LEV_JOIN_COUNTERS, work.tolist())),) if counters else out
 

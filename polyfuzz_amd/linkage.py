@@ -138,8 +138,8 @@ def connected_components(strings: List[str], model,
                          min_similarity: float = 0.8) -> Tuple[Mapping[int, List[str]], Mapping[str, int], Mapping[str, str]]:
     """Near-duplicate clusters of `strings` as the CONNECTED COMPONENTS of "similarity >= min_similarity" -- A ~ B and B ~ C put
     A, B and C together, whatever the order of the list -- in the three return values of single_linkage (which is the
-    reference's greedy, order-dependent walk and not this).  `model`: an EditDistance with scorer "levenshtein" or "osa"; its
-    `components` finds the pairs and unites them on the device (K12), and only one label per string comes back."""
+    reference's greedy, order-dependent walk and not this).  `model`: an EditDistance with scorer "levenshtein", "osa" or "indel"; its
+    `components` finds the pairs and unites them on the device (K12; "indel": K13), and only one label per string comes back."""
     strings = list(strings)
     return dicts_from_labels(strings, model.components(strings, min_similarity))
 

@@ -10,7 +10,8 @@ WRatio / partial_ratio / token_set_ratio / token_ratio / partial_token_* through
 or jellyfish.jaro_similarity / jaro_winkler_similarity (the scorer of the reference's
 custom-model tutorial, docs/tutorial/models/models.md:46-58), which run through K8;
 or rapidfuzz's Levenshtein.normalized_similarity / OSA.normalized_similarity, which run
-through K9; any other callable raises -- there is no CPU path to fall back to.
+through K9; or rapidfuzz's Indel.normalized_similarity ("indel": the default ratio on the 0..1 scale), whose best matches are
+K4's and whose threshold forms run through K13; any other callable raises -- there is no CPU path to fall back to.
 """
 import time
 from typing import Callable, List, Union
@@ -72,6 +73,27 @@ def _lev_scorer(scorer) -> str:
     return ""
 
 
+_INDEL_NAMES = ("indel", "indel_normalized_similarity")
+
+
+def _indel_scorer(scorer) -> str:
+    """"indel" when `scorer` stands for rapidfuzz.distance.Indel.normalized_similarity, else '': one of the two names; that very
+    object (by identity); or a callable named `normalized_similarity` whose module is rapidfuzz.distance.Indel or .Indel_py.
+    The rules, and what stays refused (distance, similarity, normalized_distance, partials), are _lev_scorer's."""
+    if isinstance(scorer, str):
+        return "indel" if scorer in _INDEL_NAMES else ""
+    try:
+        from rapidfuzz.distance import Indel
+        if getattr(Indel, "normalized_similarity", None) is scorer:
+            return "indel"
+    except ImportError:
+        pass
+    module = getattr(scorer, "__module__", "") or ""
+    if getattr(scorer, "__name__", "") == "normalized_similarity" and module in ("rapidfuzz.distance.Indel", "rapidfuzz.distance.Indel_py"):
+        return "indel"
+    return ""
+
+
 def _device_scorer(scorer) -> str:
     """Name of the rapidfuzz.fuzz scorer (or K8's name of the jellyfish scorer, or K9's of the rapidfuzz.distance scorer)
     `scorer` stands for, or '' when it has no kernel."""
@@ -82,6 +104,8 @@ def _device_scorer(scorer) -> str:
         return _jaro_scorer(scorer)
     if _lev_scorer(scorer):
         return _lev_scorer(scorer)
+    if _indel_scorer(scorer):
+        return _indel_scorer(scorer)
     name = scorer if isinstance(scorer, str) else getattr(scorer, "__name__", "")
     if not isinstance(scorer, str) and "rapidfuzz" not in (getattr(scorer, "__module__", "") or ""):
         return ""
@@ -90,9 +114,9 @@ def _device_scorer(scorer) -> str:
 
 # the scorers whose kernels have a top-n form (K4 on one fixed string per list element, K9); Jaro (K8) and the per-pair scorers
 # (K7) prune around a single best and keep their arg-max only
-_TOP_N_SCORERS = ("ratio", "QRatio", "token_sort_ratio", "levenshtein", "osa")
+_TOP_N_SCORERS = ("ratio", "QRatio", "token_sort_ratio", "levenshtein", "osa", "indel")
 _TOP_N_MAX = 64                 # one list entry per lane of a wave (csrc/topn_wave.h)
-_JOIN_SCORERS = ("levenshtein", "osa")      # the scorers with a threshold kernel (K11)
+_JOIN_SCORERS = ("levenshtein", "osa", "indel")      # the scorers with a threshold kernel (K11; "indel": K13)
 
 
 def _top_n_choices(ctx, name, from_list, names, skip, self_match, to_dev, ntop):
@@ -104,6 +128,11 @@ def _top_n_choices(ctx, name, from_list, names, skip, self_match, to_dev, ntop):
     if name in _lib.LEV_SCORERS:
         return _lib.lev_topn(ctx, f_dev, t_dev, name, ntop, skip)
     idx, score = _lib.indel_topn(ctx, f_dev, t_dev, ntop, skip)
+    if name == "indel":
+        # K4's order is this scorer's (indel_similarity and the ratio compare every two pairs alike, ties included:
+        # tests/test_indel_join_cpu.py); the scores go from the 0..100 scale to the definition's 0..1, bit for bit
+        from ._rapidfuzz import indel_scores
+        return idx, indel_scores(from_list, names, idx, score)
     if name == "QRatio":
         # QRatio differs from ratio only when BOTH strings are empty (0 instead of 100): an empty from-string scores 0 against
         # every choice, so its columns are simply its first choices
@@ -132,6 +161,8 @@ class EditDistance(BaseMatcher):
                 "jaro_similarity", "jaro_winkler", "jaro_winkler_similarity".  Or
                 rapidfuzz.distance.Levenshtein.normalized_similarity / rapidfuzz.distance.OSA.normalized_similarity, or
                 one of the names "levenshtein", "levenshtein_normalized_similarity", "osa", "osa_normalized_similarity".
+                Or rapidfuzz.distance.Indel.normalized_similarity, or one of the names "indel",
+                "indel_normalized_similarity".
                 Other callables -- a functools.partial of these included -- have no kernel (NotImplementedError).
         model_id: The name of the particular instance, used when comparing models
         normalize: Whether to min-max normalize the similarity scores (_distance.py:83-86)
@@ -159,22 +190,28 @@ class EditDistance(BaseMatcher):
     the scorers are the restatement of its definition in include/polyfuzz_hip.h (tests/test_levenshtein_cpu.py compares with
     rapidfuzz itself wherever it is installed).
 
+    Indel ("indel"): Similarity is rapidfuzz.distance.Indel.normalized_similarity, 1 - (|from| + |to| - 2 lcs) / (|from| + |to|)
+    as float64 on the 0..1 scale (1.0 for two empty strings), unscaled -- rapidfuzz.fuzz.ratio divided by 100, computed by its own
+    formula.  `match` and `top_n` are K4's passes (the two scales order every two pairs alike, ties included); the host turns
+    each score into the definition's float64 from the integer LCS it recovers from K4's ratio and the two lengths, verified bit
+    for bit.  `join` and `components` run through K13.
+
     top_n (attribute, default 1; the constructor keeps the reference's signature: `m = EditDistance(scorer="osa"); m.top_n = 5`):
     the number of best choices per from-string.  The reference's facade has it for TFIDF and Embeddings only (polyfuzz.py:100),
     its edit-distance loop cannot afford more than the one np.argmax (_distance.py:89-102); here the columns To, Similarity,
     To_2, Similarity_2, ... (the layout of cosine_similarity's frame) are the choices in the order np.argsort(-scores,
     kind="stable") gives: score descending, equal scores in list order, exact, on the device -- for "ratio", "QRatio",
-    "token_sort_ratio" (K4), "levenshtein" and "osa" (K9).  The scores are the scorer's own float64, unrounded; `normalize` takes
+    "token_sort_ratio", "indel" (K4), "levenshtein" and "osa" (K9).  The scores are the scorer's own float64, unrounded; `normalize` takes
     ONE minimum and maximum over all Similarity columns.  top_n is clipped to the number of choices every row has (the
     reference's clip, _utils.py:55-56); more than 64 after clipping raises _lib.PfzUnsupported; the Jaro scorers and the
     per-pair scorers (K7) raise NotImplementedError from `match` -- their kernels keep a single best.  An int >= 1, else
     ValueError; kept through pickling.
 
-    join (method, "levenshtein" and "osa"): every pair at least `min_similarity` similar instead of each string's best -- the
-    threshold form (K11), exact, with a self-join that reports each unordered pair once; see `join`.
+    join (method, "levenshtein", "osa" and "indel"): every pair at least `min_similarity` similar instead of each string's best --
+    the threshold form (K11; "indel": K13), exact, with a self-join that reports each unordered pair once; see `join`.
 
-    components (method, "levenshtein" and "osa"): the connected components of that self-join's graph as one int32 label per
-    string -- near-duplicate clusters, computed on the device where the pairs are found (K12); see `components`.
+    components (method, "levenshtein", "osa" and "indel"): the connected components of that self-join's graph as one int32 label
+    per string -- near-duplicate clusters, computed on the device where the pairs are found (K12; "indel": K13); see `components`.
     """
     last_counts = None      # {"pairs", "components"} of the last `components` call
 
@@ -189,8 +226,8 @@ class EditDistance(BaseMatcher):
         self._scorer_name = _device_scorer(scorer)
         if not self._scorer_name:
             raise NotImplementedError(
-                "polyfuzz_amd.EditDistance runs the rapidfuzz.fuzz scorers, jellyfish's two Jaro scorers and rapidfuzz's Levenshtein / OSA "
-                "normalized_similarity on the GPU; "
+                "polyfuzz_amd.EditDistance runs the rapidfuzz.fuzz scorers, jellyfish's two Jaro scorers and rapidfuzz's Levenshtein / OSA / "
+                "Indel normalized_similarity on the GPU; "
                 f"scorer {scorer!r} has no HIP kernel and there is no CPU fallback")
         self.scorer = scorer
         self.normalize = normalize
@@ -265,7 +302,7 @@ class EditDistance(BaseMatcher):
              from_list: List[str],
              to_list: List[str] = None,
              min_similarity: float = 0.8) -> pd.DataFrame:
-        """ Every pair at least `min_similarity` similar (K11): the frame From, To, Similarity with one row per pair, ordered by
+        """ Every pair at least `min_similarity` similar (K11; scorer "indel": K13): the frame From, To, Similarity with one row per pair, ordered by
         from-index, then to-index.  A from-string without a partner has no row.  Similarity is the scorer's own float64,
         unrounded, and a pair is kept iff that float64 is >= min_similarity (rapidfuzz's score_cutoff: equal is kept).
         Exact: every such pair is found, whatever their number.
@@ -275,7 +312,8 @@ class EditDistance(BaseMatcher):
         to_list None: the self-join of from_list -- every unordered pair of positions i < j once, as From = from_list[i],
         To = from_list[j]; never a string with itself, but equal strings at different positions are a pair.
 
-        Scorers "levenshtein" and "osa" only (NotImplementedError otherwise); min_similarity: a number in [0, 1]
+        Scorers "levenshtein", "osa" and "indel" only (NotImplementedError otherwise; "ratio" under its own name lives on the
+        0..100 scale and has no join: "indel" is the same metric on 0..1); min_similarity: a number in [0, 1]
         (ValueError otherwise).  The frame has the columns single_linkage reads; for the clusters of the self-join's graph
         (its connected components) see `components`, which never builds the frame. """
         if self._scorer_name not in _JOIN_SCORERS:
@@ -291,7 +329,10 @@ class EditDistance(BaseMatcher):
         names = from_list if to_list is None else to_list
         f_dev = upload_for(ctx, self._scorer_name, from_list)
         t_dev = None if to_list is None else upload_for(ctx, self._scorer_name, to_list)
-        row_ptr, idx, _, sim = _lib.lev_join(ctx, f_dev, t_dev, self._scorer_name, float(min_similarity))
+        if self._scorer_name == "indel":
+            row_ptr, idx, _, sim = _lib.indel_join(ctx, f_dev, t_dev, float(min_similarity))
+        else:
+            row_ptr, idx, _, sim = _lib.lev_join(ctx, f_dev, t_dev, self._scorer_name, float(min_similarity))
         t1 = time.perf_counter()
         frm = np.repeat(np.arange(len(from_list), dtype=np.int32), np.diff(row_ptr))
         matches = pd.DataFrame({"From": gather_column(from_list, frm), "To": gather_column(names, idx), "Similarity": sim}, copy=False)
@@ -301,7 +342,7 @@ class EditDistance(BaseMatcher):
     def components(self,
                    from_list: List[str],
                    min_similarity: float = 0.8) -> np.ndarray:
-        """ Near-duplicate clusters of from_list (K12): int32 labels, label[i] = the smallest position in i's connected
+        """ Near-duplicate clusters of from_list (K12; scorer "indel": K13): int32 labels, label[i] = the smallest position in i's connected
         component of the graph whose edges are the pairs `join(from_list, min_similarity=...)` reports -- "A ~ B and B ~ C put A,
         B and C together".  Equal strings share a component; a string with no partner is its own (label[i] == i).  Exact and
         deterministic.  The pairs are united on the device where they are found and never stored or downloaded: device memory
@@ -310,7 +351,7 @@ class EditDistance(BaseMatcher):
 
         `normalize` is NOT applied: there is no score to rescale.
 
-        Scorers "levenshtein" and "osa" only (NotImplementedError otherwise); min_similarity: a number in [0, 1]
+        Scorers "levenshtein", "osa" and "indel" only (NotImplementedError otherwise); min_similarity: a number in [0, 1]
         (ValueError otherwise).  Sets last_timings and last_counts = {"pairs": hits, "components": components}. """
         if self._scorer_name not in _JOIN_SCORERS:
             raise NotImplementedError(
@@ -323,7 +364,10 @@ class EditDistance(BaseMatcher):
         t0 = time.perf_counter()
         ctx = _lib.Context.default()
         f_dev = upload_for(ctx, self._scorer_name, from_list)
-        label, pairs, components = _lib.lev_components(ctx, f_dev, self._scorer_name, float(min_similarity))
+        if self._scorer_name == "indel":
+            label, pairs, components = _lib.indel_components(ctx, f_dev, float(min_similarity))
+        else:
+            label, pairs, components = _lib.lev_components(ctx, f_dev, self._scorer_name, float(min_similarity))
         self.last_timings = {"device": (time.perf_counter() - t0) * 1e3, "frame": 0.0}
         self.last_counts = {"pairs": pairs, "components": components}
         return label

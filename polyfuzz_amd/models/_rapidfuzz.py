@@ -110,7 +110,24 @@ def best_choice_async(ctx, name, from_list, names, skip, self_match, to_dev=None
                 for i in [i for i, s in enumerate(from_list) if len(s) == 0]:
                     first_choice = next((j for j in range(len(names)) if not (skip is not None and _left_out(j, int(skip[i])))), -1)
                     idx[i], score[i] = first_choice, 0.0
+        elif name == "indel":                 # (EditDistance only: K4's arg-max -- the order is the same --, its score on the 0..1 scale)
+            def fix(idx, score):
+                score[:] = indel_scores(from_list, names, idx, score)
     return _PendingBest(out, n, fix)
+
+
+def indel_scores(from_list, names, idx, ratio):
+    """K4's float64 ratios (0..100) of the pairs (from_list[i], names[idx[i, ...]]) as Indel.normalized_similarity (0..1): the
+    integer LCS is recovered from each ratio and the two lengths (_lib.indel_lcs_of_ratio: verified bit for bit, ValueError
+    otherwise) and put through the definition.  idx < 0 (no choice) keeps 0.0.  idx / ratio: [n] or [n, k]."""
+    idx, ratio = np.asarray(idx), np.asarray(ratio, np.float64)
+    la = np.fromiter(map(len, from_list), np.int64, len(from_list))
+    lb = np.fromiter(map(len, names), np.int64, len(names))
+    some = idx >= 0
+    s = la.reshape((-1,) + (1,) * (idx.ndim - 1)) + lb[np.where(some, idx, 0)] if len(names) else np.zeros(idx.shape, np.int64)
+    out = np.zeros(idx.shape, np.float64)
+    out[some] = _lib.indel_similarity(_lib.indel_lcs_of_ratio(ratio[some], s[some]), s[some])
+    return out
 
 
 def best_choice(ctx, name, from_list, names, skip, self_match, to_dev=None):
