@@ -87,7 +87,9 @@ int pfz_prof_reset(pfz_ctx *ctx);
  * K11: `k11_join` (the walk of a call), `k11_join_general` (its general-kernel launch), `k11_sort_unpack` (the hits sorted and
  * turned into CSR).
  * K12: `k12_walk` (the walk of a call, hooks included), `k12_walk_general` (its general-kernel launch), `k12_flatten` (the
- * forest turned into labels). */
+ * forest turned into labels).
+ * K14: `k14_join` (the tile kernel of a call), `k14_sort_unpack` (the hits sorted with their scores and turned into CSR),
+ * `k14_components` (forest, tile kernel with its hooks, labels). */
 int pfz_prof_get(pfz_ctx *ctx, const char *name, double *total_ms, int64_t *launches);
 
 /* ---- CSR matrices --------------------------------------------------------
@@ -627,6 +629,42 @@ int pfz_dense_rescore_topn(pfz_ctx *ctx, const pfz_dense *from_exact, const pfz_
  * 1024 candidates per row.  No from-rows: PFZ_OK, nothing is done. */
 int pfz_dense_rescore_topn_mixed(pfz_ctx *ctx, const pfz_dense *from_exact, const pfz_dense *to_coarse, const pfz_topn *candidates,
                                  int32_t ntop, float lower_bound, pfz_topn *out);
+
+/* ---- K14: all pairs at or above a cosine, and their components ------------------
+ * The threshold form of K5, what near-duplicate mining and semantic de-duplication ask of the cosine matrix of the reference's
+ * Embeddings matcher (polyfuzz/models/_utils.py:74-77): every pair (from i, to j) whose cosine is >= min_similarity.  The score
+ * of a pair is the float32 pfz_dense_topn computes for it, bit for bit -- dot product of the stored rows times 1 / ||a|| times
+ * 1 / ||b|| -- and the comparison is (double)score >= min_similarity: equal is a hit.  fp32 operands uploaded with normalize = 1
+ * (pfz_dense_upload) only: 16-bit, int8 and 1-bit handles, and handles uploaded without normalize, are PFZ_ERR_INVALID.
+ * to == NULL, or the from-vectors' own handle: the self-join.  Only the tiles on or above the diagonal are computed; every
+ * unordered pair i < j is reported once, as row i, to-index j, with the score of (i, j) (that of (j, i) may differ in the last bit
+ * and is never computed); never (i, i); equal vectors at different positions are pairs.  A row of zeros scores 0 with everything.
+ * Output, host buffers: CSR over the from-rows.  out_row_ptr int64[n_from + 1]; hit p of row i, out_row_ptr[i] <= p <
+ * out_row_ptr[i + 1]: out_idx[p] the to-index (ascending within a row), out_sim[p] the score.  The same call gives the same bytes
+ * every time.
+ * capacity: the hits out_idx / out_sim have room for (they may be NULL when it is 0).  *out_total is always the exact number of
+ * hits.  When it exceeds `capacity` the call still returns PFZ_OK, has written NONE of the three output arrays (the device never
+ * writes a hit past the capacity either) and is to be repeated with capacity >= *out_total.
+ * out_counters: NULL, or int64[2] of work counts -- [0] the 128 x 128 tiles executed (a self-join of T = ceil(n / 128) row tiles:
+ * T (T + 1) / 2), [1] the 64 x 64 wave corners that contained a hit (the others left without touching memory).
+ * No score panel is written: device memory beyond the operands is 12 bytes per hit of capacity plus the sort's copy.
+ * An empty list on either side: PFZ_OK, *out_total = 0, out_row_ptr all zero.
+ * Limits (PFZ_ERR_UNSUPPORTED beyond): at most 2^31 tiles in one call (two lists of 5.9 million rows each, a self-join of 8.3
+ * million), fewer than 2^31 rows per list; a call of 2^24 workgroups or more (a self-join of 740 000 rows) is several launches.  A NaN min_similarity or one outside [0, 1], capacity < 0, unequal widths, another
+ * operand type: PFZ_ERR_INVALID.  Profiling scopes: `k14_join` (the tile kernel), `k14_sort_unpack`.  Blocks. */
+int pfz_dense_join(pfz_ctx *ctx, const pfz_dense *from_vectors, const pfz_dense *to_vectors, double min_similarity,
+                   int64_t capacity, int64_t *out_row_ptr, int32_t *out_idx, float *out_sim, int64_t *out_total,
+                   int64_t *out_counters);
+/* The connected components of "cosine >= min_similarity" over ONE list: the pairs of pfz_dense_join(ctx, vectors, NULL,
+ * min_similarity, ...), found by the same tiles, but none is stored -- the lane that finds a hit unites the two positions in the
+ * lock-free union-find of csrc/k12_core.h.  Device memory beyond the operands is O(n) whatever the number of hits; there is no
+ * capacity and no repeat.  out_label: host buffer int32[n], out_label[i] = the SMALLEST position in i's component (so
+ * out_label[i] <= i); deterministic, whatever order the device's atomics took.  *out_pairs == pfz_dense_join's *out_total;
+ * *out_components counts singletons too; out_counters as above.  vectors->n == 0: PFZ_OK, *out_pairs = *out_components = 0,
+ * nothing else is written (out_label may be NULL).  Operands, limits and errors as pfz_dense_join, and a NULL out_pairs /
+ * out_components is PFZ_ERR_INVALID.  Profiling scope: `k14_components` (forest, tile kernel and labels).  Blocks. */
+int pfz_dense_components(pfz_ctx *ctx, const pfz_dense *vectors, double min_similarity, int32_t *out_label,
+                         int64_t *out_pairs, int64_t *out_components, int64_t *out_counters);
 
 /* ---- K6: reductions on the hot path's output --------------------------------
  * precision_recall_curve (reference polyfuzz/metrics.py:12-53): for every threshold p_k

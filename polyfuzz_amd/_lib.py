@@ -121,6 +121,8 @@ SIGNATURES = {
     "pfz_dense_topn": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_f32, c_i32, c_i64, c_vp]),
     "pfz_dense_rescore_topn": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_f32, c_vp]),
     "pfz_dense_rescore_topn_mixed": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_f32, c_vp]),
+    "pfz_dense_join": (ctypes.c_int, [c_vp, c_vp, c_vp, c_f64, c_i64, c_vp, c_vp, c_vp, P(c_i64), c_vp]),
+    "pfz_dense_components": (ctypes.c_int, [c_vp, c_vp, c_f64, c_vp, P(c_i64), P(c_i64), c_vp]),
     "pfz_pr_curve_host": (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp]),
     "pfz_linkage_top1": (ctypes.c_int, [c_vp, c_vp, c_f64, c_vp, c_vp, c_vp]),
     "pfz_comm_unique_id": (ctypes.c_int, [c_vp]),
@@ -1168,6 +1170,71 @@ def dense_topn(ctx, from_dev, to_dev, ntop, lower_bound, exclude_diag=False, dia
     check(ctx.lib.pfz_dense_topn(ctx.h, from_dev.h, to_dev.h, int(ntop), float(lower_bound), int(bool(exclude_diag)),
                                  int(diag_offset), out.h))
     return out
+
+
+# ---- K14: the cosine threshold join and its components ---------------------------------------------------------------
+
+DENSE_JOIN_COUNTERS = ("tiles", "hit_corners")      # pfz_dense_join's out_counters, in order
+
+
+def dense_threshold32(t):
+    """The smallest float32 >= t (a float64): a float32 score s satisfies float64(s) >= t exactly when s >= this value --
+    the comparison K14 makes on the device.  Pure numpy."""
+    t = np.float64(t)
+    r = np.float32(t)                              # (to nearest: at most one step below t)
+    return np.nextafter(r, np.float32(np.inf)) if np.float64(r) < t else r
+
+
+def _dense_join_operand(dev, what):
+    if dev.dtype != "float32" or not dev.normalize:
+        raise ValueError(f"{what} are {dev.dtype} vectors uploaded with normalize={dev.normalize}: the cosine threshold kernels "
+                         "take fp32 operands uploaded with normalize=True (DeviceDense.upload)")
+
+
+def dense_join(ctx, from_dev, to_dev, min_similarity, capacity=None, counters=False):
+    """K14: every pair of rows whose cosine -- dense_topn's float32, bit for bit -- is >= min_similarity (as float64: equal is a
+    hit), as CSR over the from-rows: (row_ptr int64[n + 1], to-index int32[hits] ascending within a row, similarity
+    float32[hits], counts).  to_dev None (or from_dev itself): the self-join, every unordered pair once as (i, j), i < j, only
+    the tiles on or above the diagonal computed.  fp32 operands uploaded with normalize=True only.  capacity: the hits the first
+    call's buffers have room for (None: a modest guess, four per from-row); when the exact total the call returns exceeds it
+    the call is repeated ONCE with room for that total, never more often.  counts: {"pairs": hits}, with counters=True also
+    DENSE_JOIN_COUNTERS (the last call's)."""
+    _dense_join_operand(from_dev, "the from-vectors")
+    if to_dev is not None:
+        _dense_join_operand(to_dev, "the to-vectors")
+    work = np.zeros(2, np.int64) if counters else None
+    total = c_i64(0)
+    to_h = None if to_dev is None else to_dev.h
+    cap = max(4096, 4 * int(from_dev.n)) if capacity is None else int(capacity)
+    for _ in range(2):
+        row_ptr = np.empty(from_dev.n + 1, np.int64)
+        idx, sim = np.empty(cap, np.int32), np.empty(cap, np.float32)
+        check(ctx.lib.pfz_dense_join(ctx.h, from_dev.h, to_h, float(min_similarity), cap, _ptr(row_ptr), _ptr(idx), _ptr(sim),
+                                     ctypes.byref(total), _ptr(work)))
+        if total.value <= cap:
+            break
+        cap = total.value
+    assert total.value <= cap                     # (the second call had room for the exact total)
+    n = total.value
+    counts = {"pairs": n}
+    if counters:
+        counts.update(zip(DENSE_JOIN_COUNTERS, work.tolist()))
+    return row_ptr, idx[:n].copy(), sim[:n].copy(), counts
+
+
+def dense_components(ctx, dev, min_similarity, counters=False):
+    """K14: the connected components of "cosine >= min_similarity" over the rows of `dev` (the pairs of dense_join's self-join,
+    united on the device, never stored) -- (label int32[n], pairs, components): label[i] is the smallest position in i's
+    component, pairs the number of hits (dense_join's total), components the number of components, singletons included.
+    counters=True appends a dict of DENSE_JOIN_COUNTERS."""
+    _dense_join_operand(dev, "the vectors")
+    work = np.zeros(2, np.int64) if counters else None
+    label = np.empty(dev.n, np.int32)
+    pairs, components = c_i64(0), c_i64(0)
+    check(ctx.lib.pfz_dense_components(ctx.h, dev.h, float(min_similarity), _ptr(label), ctypes.byref(pairs), ctypes.byref(components),
+                                       _ptr(work)))
+    out = (label, pairs.value, components.value)
+    return out + (dict(zip(DENSE_JOIN_COUNTERS, work.tolist())),) if counters else out
 
 
 # ---- exact rescoring of a 16-bit / int8 top-n (k5_rescore_topn) ------------------------------------------------------

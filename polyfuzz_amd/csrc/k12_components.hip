@@ -32,22 +32,6 @@ struct CompArgs : WalkArgs {   // (n_to: the list's own length)
     int32_t *parent;           // [n] the forest (k12_core.h)
 };
 
-// parent as the walk kernels touch it: relaxed, agent scope, nothing else
-struct UfDeviceOps {
-    __device__ static int32_t load(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    __device__ static void store(int32_t *p, int32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    __device__ static int32_t cas(int32_t *p, int32_t expected, int32_t desired)
-    {
-        __hip_atomic_compare_exchange_strong(p, &expected, desired, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return expected;
-    }
-};
-
-// the finished forest, behind the kernel boundary: plain loads
-struct UfPlainOps {
-    __device__ static int32_t load(const int32_t *p) { return *p; }
-};
-
 // the walk's hit sink: the hits of one wave and group counted with one atomic, and each hit lane hooks its pair into the forest
 struct CompHook {
     const CompArgs &A;
@@ -147,6 +131,23 @@ __global__ __launch_bounds__(256) void k12_flatten(const int32_t *__restrict__ p
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(n_roots, (unsigned long long)__popcll(m));
 }
 
+// the two ends of a forest for the other kernels that hook into one (K14, pfz_internal.h): every position its own root, on the
+// context's stream ...
+int k12_forest_begin(pfz_ctx *ctx, int32_t n, int32_t *parent)
+{
+    hipLaunchKernelGGL(k12_begin, dim3((unsigned)(((int64_t)n + 255) / 256)), dim3(256), 0, ctx->stream, 0.0, 0, (int32_t *)nullptr, n, parent);
+    PFZ_HIP(hipGetLastError());
+    return PFZ_OK;
+}
+
+// ... and, behind the kernels that hooked, the labels and the number of roots added to *n_roots
+int k12_forest_flatten(pfz_ctx *ctx, const int32_t *parent, int32_t n, int32_t *label, unsigned long long *n_roots)
+{
+    hipLaunchKernelGGL(k12_flatten, dim3((unsigned)(((int64_t)n + 255) / 256)), dim3(256), 0, ctx->stream, parent, n, label, n_roots);
+    PFZ_HIP(hipGetLastError());
+    return PFZ_OK;
+}
+
 static int comp_run(pfz_ctx *ctx, const pfz_strings *F, int32_t scorer, double t, int32_t *out_label, int64_t *out_pairs,
                     int64_t *out_components, int64_t *out_counters)
 {
@@ -224,9 +225,7 @@ static int comp_run(pfz_ctx *ctx, const pfz_strings *F, int32_t scorer, double t
     }
     {
         ProfScope ps(ctx, "k12_flatten");
-        hipLaunchKernelGGL(k12_flatten, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_parent.as<int32_t>(), (int32_t)n,
-                           d_label.as<int32_t>(), d_state.as<unsigned long long>() + 4);
-        PFZ_HIP(hipGetLastError());
+        PFZ_TRY(k12_forest_flatten(ctx, d_parent.as<int32_t>(), (int32_t)n, d_label.as<int32_t>(), d_state.as<unsigned long long>() + 4));
     }
     unsigned long long state[5];
     PFZ_TRY(copy_d2h(ctx, state, d_state.p, sizeof(state)));

@@ -79,6 +79,24 @@ template <class Ops> K12_HD int32_t uf_root(const int32_t *parent, int32_t x)
     }
 }
 
+#if defined(__HIPCC__)
+// parent as the kernels that hook touch it (K12's walk, K14's tile epilogue): relaxed, agent scope, nothing else
+struct UfDeviceOps {
+    __device__ static int32_t load(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    __device__ static void store(int32_t *p, int32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    __device__ static int32_t cas(int32_t *p, int32_t expected, int32_t desired)
+    {
+        __hip_atomic_compare_exchange_strong(p, &expected, desired, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return expected;
+    }
+};
+
+// the finished forest, behind the kernel boundary: plain loads
+struct UfPlainOps {
+    __device__ static int32_t load(const int32_t *p) { return *p; }
+};
+#endif
+
 #if !defined(__HIP_DEVICE_COMPILE__)
 // the host's atomics: what tests/k12_core_host.cpp races its threads through
 struct UfHostOps {

@@ -349,5 +349,14 @@ int best_to_topn(pfz_ctx *ctx, const int32_t *d_idx, const double *d_score, int6
 
 int64_t sort_codes_capacity(int64_t n);
 int sort_codes_u64(pfz_ctx *ctx, const uint64_t *in, uint64_t *out, int64_t n);
+// the same sort with a 32-bit payload beside every key (K14: a hit's score); out and vout hold sort_codes_capacity(n) entries,
+// no key is ~0
+int sort_pairs_u64(pfz_ctx *ctx, const uint64_t *in, const uint32_t *vin, uint64_t *out, uint32_t *vout, int64_t n);
+
+// K12's forest for other kernels that hook pairs into one with uf_unite<UfDeviceOps> (k12_core.h): parent[i] = i for i < n, and,
+// behind the hooking kernels, label[i] = the smallest position of i's tree with the number of trees added to *n_roots (device).
+// Both enqueue on ctx->stream (k12_components.hip: k12_begin, k12_flatten).
+int k12_forest_begin(pfz_ctx *ctx, int32_t n, int32_t *parent);
+int k12_forest_flatten(pfz_ctx *ctx, const int32_t *parent, int32_t n, int32_t *label, unsigned long long *n_roots);
 
 }  // namespace pfz

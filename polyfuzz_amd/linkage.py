@@ -135,13 +135,17 @@ def dicts_from_labels(strings, labels):
 
 
 def connected_components(strings: List[str], model,
-                         min_similarity: float = 0.8) -> Tuple[Mapping[int, List[str]], Mapping[str, int], Mapping[str, str]]:
+                         min_similarity: float = 0.8,
+                         embeddings=None) -> Tuple[Mapping[int, List[str]], Mapping[str, int], Mapping[str, str]]:
     """Near-duplicate clusters of `strings` as the CONNECTED COMPONENTS of "similarity >= min_similarity" -- A ~ B and B ~ C put
     A, B and C together, whatever the order of the list -- in the three return values of single_linkage (which is the
     reference's greedy, order-dependent walk and not this).  `model`: an EditDistance with scorer "levenshtein", "osa" or "indel"; its
-    `components` finds the pairs and unites them on the device (K12; "indel": K13), and only one label per string comes back."""
+    `components` finds the pairs and unites them on the device (K12; "indel": K13), and only one label per string comes back.
+    Or an Embeddings model (K14, the cosine of the vectors); `embeddings`, when given, are the strings' ready-made row vectors
+    and are handed to its `components` -- equal strings must then have equal vectors."""
     strings = list(strings)
-    return dicts_from_labels(strings, model.components(strings, min_similarity))
+    extra = {} if embeddings is None else {"embeddings": embeddings}
+    return dicts_from_labels(strings, model.components(strings, min_similarity, **extra))
 
 
 def create_groups(matches: pd.DataFrame, model=None, link_min_similarity: float = 0.75, group_all_strings: bool = False):

@@ -9,6 +9,7 @@ embeddings_from=..., embeddings_to=..., re_train=...)` with the reference's argu
 may be any callable `list[str] -> ndarray[n, d]` (the rows are L2-normalised like _embeddings.py:145);
 without one, the embeddings must be passed in.
 """
+import time
 from typing import Callable, List, Optional
 
 import numpy as np
@@ -16,7 +17,7 @@ import pandas as pd
 
 from .. import _lib
 from ._base import BaseMatcher
-from ._utils import topn_to_frame, clip_top_n, _METHODS
+from ._utils import gather_column, topn_to_frame, clip_top_n, _METHODS
 
 
 class Embeddings(BaseMatcher):
@@ -96,6 +97,9 @@ class Embeddings(BaseMatcher):
                    itself -- a corpus that exists only in quantised form.  Validated when set, kept through pickling; the
                    to-side of the rescoring is resident like the coarse one and re-made when `rescore_to` or the to-side
                    changes.
+
+    Beside `match` (each string's best): `join` -- every pair whose cosine is at least a threshold -- and `components` -- the
+    near-duplicate clusters of one list -- on fp32 vectors (K14); see the two methods.
     """
     def __init__(self,
                  embedding_method: Optional[Callable[[List[str]], np.ndarray]] = None,
@@ -262,6 +266,93 @@ class Embeddings(BaseMatcher):
             idx, val = _lib.dense_topn(ctx, from_dev, self._dev_to, max(top_n, 1), lower, exclude_diag=self_match).download()
         self.embeddings_to = embeddings_to
         return topn_to_frame(idx, val, from_list, from_list if self_match else to_list, top_n)
+
+    def _threshold_operands_only(self, what, min_similarity):
+        """join and components run K14: fp32 operands, the true cosine.  Everything that names another operand type or a
+        second pass is refused here, before any device call."""
+        if (isinstance(min_similarity, bool) or not isinstance(min_similarity, (int, float, np.integer, np.floating))
+                or not 0.0 <= float(min_similarity) <= 1.0):      # (NaN compares false)
+            raise ValueError(f"min_similarity must be a number in [0, 1], not {min_similarity!r}")
+        for name, value in (("precision", self.precision), ("binary", self.binary), ("rescore_multiplier", self.rescore_multiplier),
+                            ("rescore_to", self.rescore_to)):
+            if value is not None:
+                raise ValueError(f"Embeddings.{what} compares the fp32 cosine with the threshold on the GPU; {name}={value!r} is "
+                                 f"set, which has no threshold kernel (leave {name} at None)")
+        if _lib.check_compute_dtype(self.compute_dtype) != "float32":
+            raise ValueError(f"Embeddings.{what} compares the fp32 cosine with the threshold on the GPU; "
+                             f"compute_dtype={self.compute_dtype!r} is set, which has no threshold kernel (leave compute_dtype at None)")
+
+    def _vectors(self, strings, embeddings, side):
+        vec = embeddings if isinstance(embeddings, np.ndarray) else self._embed(strings)
+        if vec.ndim != 2 or vec.shape[0] != len(strings):
+            raise ValueError(f"{side} has shape {vec.shape} for {len(strings)} strings")
+        return vec
+
+    def join(self,
+             from_list: List[str],
+             to_list: List[str] = None,
+             min_similarity: float = 0.8,
+             embeddings_from: np.ndarray = None,
+             embeddings_to: np.ndarray = None) -> pd.DataFrame:
+        """ Every pair whose cosine is at least `min_similarity` (K14): the frame From, To, Similarity with one row per pair,
+        ordered by from-index, then to-index.  A from-string without a partner has no row.  Similarity is the float32 cosine
+        `match` computes for the pair (cosine_method "hip"), and a pair is kept iff that value, as float64, is >=
+        min_similarity: equal is kept.  Exact in that sense: every such pair is found, whatever their number -- there is no top_n
+        to guess, and no score matrix is written.
+
+        Always the true cosine, whatever `cosine_method` says: a threshold in [0, 1] means a cosine.  `min_similarity` of the
+        constructor and `top_n` play no part.
+
+        to_list None: the self-join of from_list -- every unordered pair of positions i < j once, as From = from_list[i],
+        To = from_list[j]; never a string with itself, but equal vectors at different positions are a pair.  Only the half of
+        the similarity matrix above the diagonal is computed.
+
+        embeddings_from / embeddings_to: ready-made row vectors (any float dtype; computed in float32), else the
+        embedding_method embeds the lists.  min_similarity: a number in [0, 1] (ValueError otherwise).  `precision`, `binary`,
+        a 16-bit `compute_dtype`, `rescore_multiplier` and `rescore_to` must be unset (ValueError): the threshold kernels take
+        fp32 operands only.  The frame has the columns single_linkage reads; for the clusters of the self-join's graph see
+        `components`, which never builds the frame.  Sets last_timings and last_counts = {"pairs": hits}. """
+        self._threshold_operands_only("join", min_similarity)
+        if to_list is None and isinstance(embeddings_to, np.ndarray):
+            raise ValueError("embeddings_to is given without a to_list: the self-join has one list and one matrix, embeddings_from")
+        vec_from = self._vectors(from_list, embeddings_from, "embeddings_from")
+        vec_to = None if to_list is None else self._vectors(to_list, embeddings_to, "embeddings_to")
+        if vec_to is not None and vec_to.shape[1] != vec_from.shape[1]:
+            raise ValueError(f"dense cosine needs two 2-D arrays with equal width, got {vec_from.shape[1]} and {vec_to.shape[1]}")
+        t0 = time.perf_counter()
+        ctx = _lib.Context.default()
+        f_dev = _lib.DeviceDense.upload(ctx, vec_from, True)
+        t_dev = None if vec_to is None else _lib.DeviceDense.upload(ctx, vec_to, True)
+        row_ptr, idx, sim, counts = _lib.dense_join(ctx, f_dev, t_dev, float(min_similarity))
+        t1 = time.perf_counter()
+        names = from_list if to_list is None else to_list
+        frm = np.repeat(np.arange(len(from_list), dtype=np.int32), np.diff(row_ptr))
+        matches = pd.DataFrame({"From": gather_column(from_list, frm), "To": gather_column(names, idx), "Similarity": sim}, copy=False)
+        self.last_timings = {"device": (t1 - t0) * 1e3, "frame": (time.perf_counter() - t1) * 1e3}
+        self.last_counts = counts
+        return matches
+
+    def components(self,
+                   strings: List[str],
+                   min_similarity: float = 0.8,
+                   embeddings: np.ndarray = None) -> np.ndarray:
+        """ Near-duplicate clusters of `strings` (K14): int32 labels, label[i] = the smallest position in i's connected component
+        of the graph whose edges are the pairs `join(strings, min_similarity=...)` reports -- "A ~ B and B ~ C put A, B and C
+        together".  A string with no partner is its own component (label[i] == i).  Exact and deterministic.  The pairs are
+        united on the device where they are found and never stored or downloaded: device memory beyond the vectors is
+        O(len(strings)) whatever their number.  polyfuzz_amd.linkage.connected_components turns the labels into the three dicts
+        single_linkage returns.
+
+        embeddings: ready-made row vectors, else the embedding_method embeds the list.  Refusals as `join`.  Sets last_timings
+        and last_counts = {"pairs": hits, "components": components}. """
+        self._threshold_operands_only("components", min_similarity)
+        vec = self._vectors(strings, embeddings, "embeddings")
+        t0 = time.perf_counter()
+        ctx = _lib.Context.default()
+        label, pairs, components = _lib.dense_components(ctx, _lib.DeviceDense.upload(ctx, vec, True), float(min_similarity))
+        self.last_timings = {"device": (time.perf_counter() - t0) * 1e3, "frame": 0.0}
+        self.last_counts = {"pairs": pairs, "components": components}
+        return label
 
     # a matcher is pickled by joblib (reference polyfuzz.py:429-457): the device copy stays behind
     def __getstate__(self):

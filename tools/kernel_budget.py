@@ -47,9 +47,11 @@ def kernel_metadata(lib):
                 if not m:
                     continue
                 key, val = m.group(1), m.group(2).strip().strip("'")
-                if key in ("group_segment_fixed_size", "private_segment_fixed_size", "sgpr_count", "vgpr_count"):
+                if key in ("group_segment_fixed_size", "private_segment_fixed_size", "sgpr_count", "vgpr_count", "agpr_count"):
+                    # (vgpr_count is the lane's whole unified register file, the accumulation registers included; agpr_count
+                    # says how many of them are accumulation registers)
                     cur[{"group_segment_fixed_size": "lds", "private_segment_fixed_size": "scratch", "sgpr_count": "sgpr",
-                         "vgpr_count": "vgpr"}[key]] = int(val)
+                         "vgpr_count": "vgpr", "agpr_count": "agpr"}[key]] = int(val)
                 elif key == "name":
                     cur["name"] = val
                 elif key == "wavefront_size":           # (the last key of a kernel's record)
@@ -98,9 +100,9 @@ if __name__ == "__main__":
         sys.exit(0)
     md = kernel_metadata(lib)
     names = sorted(md)
-    print(f"{'vgpr':>5} {'sgpr':>5} {'lds B':>7} {'scratch':>7}  kernel")
+    print(f"{'vgpr':>5} {'agpr':>5} {'sgpr':>5} {'lds B':>7} {'scratch':>7}  kernel")
     for n, pretty in zip(names, demangled(names)):
         if flt and not any(f in pretty for f in flt):
             continue
         v = md[n]
-        print(f"{v.get('vgpr', -1):5d} {v.get('sgpr', -1):5d} {v.get('lds', -1):7d} {v.get('scratch', -1):7d}  {pretty[:110]}")
+        print(f"{v.get('vgpr', -1):5d} {v.get('agpr', 0):5d} {v.get('sgpr', -1):5d} {v.get('lds', -1):7d} {v.get('scratch', -1):7d}  {pretty[:110]}")
