@@ -156,7 +156,10 @@ int pfz_topn_device_ptrs(const pfz_topn *t, void **idx_dev, void **val_dev, int6
  * A[i][k] * B[j][k] with C[i][j] > lower_bound (strict, as sparse_dot_topn),
  * ordered by (score desc, j asc).  Every product is computed in fp32, scaled by
  * 2^30 / (norm bound) and truncated to int32; the sums are int32 (order-
- * independent, bit-reproducible; |error| ~ 3e-8).  exclude_diag != 0 drops j == i + diag_offset (self-match,
+ * independent, bit-reproducible).  Truncation makes the error one-sided and lets it grow with the rows: a score is at
+ * most c * 2^-30 * (norm bound) + 3e-7 below the exact one for a pair with c columns in common -- ~1e-8 for company
+ * names (c ~ 13), inside 1e-5 up to about 10 000 shared n-grams per pair, beyond it for longer documents
+ * (docs/K3_DOCUMENT_ROWS.md).  exclude_diag != 0 drops j == i + diag_offset (self-match,
  * _utils.py:84-87; diag_offset = global index of from-row 0 when the from
  * side is a row shard).  lower_bound < 0 is treated as 0 (non-positive scores
  * are "no match" in the reference's output contract, _utils.py:122-123).

@@ -24,8 +24,14 @@
 // not depend on the order in which postings arrive: results are bit-reproducible,
 // exact ties (duplicate to-strings) stay exact ties, and the kernel is free to
 // process postings in whatever order fills the lanes best -- and a padding entry
-// (value 0) adds nothing.  |sum/S - exact| is below 13 * 2^-30 + fp32 product
-// rounding (~3e-8), far inside the 1e-5 budget.
+// (value 0) adds nothing.  Every product is TRUNCATED, so a score is never too
+// high by more than rounding and at most one step 1/S too low per n-gram the two
+// rows share: |sum/S - exact| <= c * 2^-30 * (norm bound) + 3e-7 for c shared
+// n-grams (3e-7: fp32 storage of the two values, the fp32 product, the final
+// int -> float conversion).  About half of that in practice (the mean truncation
+// is half a step).  Company names share ~13 n-grams: 1e-8.  Documents share
+// thousands: the 1e-5 budget holds up to about 10 000 shared n-grams per pair
+// and not beyond (docs/K3_DOCUMENT_ROWS.md, tests/test_documents_gpu.py).
 // (Measured on MI355X, tools/ubench/lds_atomic.hip: ds_add_u32 6.6 lanes/clk/CU,
 // plain LDS read+fadd+write 3.6, ds_add_f32 0.31 -- the float atomic is unusable.)
 //
