@@ -89,7 +89,9 @@ int pfz_prof_reset(pfz_ctx *ctx);
  * K12: `k12_walk` (the walk of a call, hooks included), `k12_walk_general` (its general-kernel launch), `k12_flatten` (the
  * forest turned into labels).
  * K14: `k14_join` (the tile kernel of a call), `k14_sort_unpack` (the hits sorted with their scores and turned into CSR),
- * `k14_components` (forest, tile kernel with its hooks, labels). */
+ * `k14_components` (forest, tile kernel with its hooks, labels).
+ * K15: `k15_join` (the row walk of a call), `k15_sort_unpack` (the hits sorted with their scores and turned into CSR),
+ * `k15_components` (forest, row walk with its hooks, labels). */
 int pfz_prof_get(pfz_ctx *ctx, const char *name, double *total_ms, int64_t *launches);
 
 /* ---- CSR matrices --------------------------------------------------------
@@ -668,6 +670,48 @@ int pfz_dense_join(pfz_ctx *ctx, const pfz_dense *from_vectors, const pfz_dense 
  * out_components is PFZ_ERR_INVALID.  Profiling scope: `k14_components` (forest, tile kernel and labels).  Blocks. */
 int pfz_dense_components(pfz_ctx *ctx, const pfz_dense *vectors, double min_similarity, int32_t *out_label,
                          int64_t *out_pairs, int64_t *out_components, int64_t *out_counters);
+
+/* ---- K15: all pairs at or above a sparse cosine, and their components -----------
+ * The threshold form of K3, what de-duplication asks of the reference's TF-IDF matcher: every pair (from-row i, to-row j) whose
+ * cosine is >= min_similarity, however many partners a row has -- no top_n to guess, no n x top_n table.  to_index is the
+ * inverted index of the to-side (pfz_index_build), from_matrix the from-rows (CSR, the same vocabulary).
+ * The hit rule: the score of a pair is the float32 pfz_cossim_topn reports for it, bit for bit -- (float)sum * 2^-k of K3's
+ * fixed-point sum -- and the comparison is (double)score >= min_similarity: equal is a hit.  A pair that shares no n-gram
+ * (sum 0) is never a hit, also at min_similarity = 0.  That score is at most c * 2^-30 * (norm bound) + 3e-7 below the exact
+ * cosine of a pair with c shared n-grams, so at min_similarity = 1.0 equal strings are hits only where their truncated sum
+ * still rounds to 1.0.  The device compares integers: the host finds the smallest passing sum by evaluating the rule.
+ * self_join != 0: from_matrix must be the matrix to_index was built from (its serial is compared; PFZ_ERR_INVALID otherwise).
+ * Every unordered pair i < j is reported once, as row i, to-index j -- K3's sums are symmetric bit for bit, row i walks the
+ * to-blocks from its own on --; never (i, i); equal rows at different positions are pairs.  self_join == 0: every (i, j), also
+ * where both lists hold the same strings.
+ * Output, host buffers: CSR over the from-rows.  out_row_ptr int64[n_from + 1]; hit p of row i, out_row_ptr[i] <= p <
+ * out_row_ptr[i + 1]: out_idx[p] the to-index (ascending within a row), out_sim[p] the score.  The same call gives the same bytes
+ * every time.
+ * capacity: the hits out_idx / out_sim have room for (they may be NULL when it is 0).  *out_total is always the exact number of
+ * hits.  When it exceeds `capacity` the call still returns PFZ_OK, has written NONE of the three output arrays (the device never
+ * writes a hit past the capacity either) and is to be repeated with capacity >= *out_total.
+ * out_counters: NULL, or int64[3] of work counts -- [0] the (from-row, to-block) visits that had postings, [1] those of them an
+ * exact upper bound of the block's sums skipped (rows of at most 64 n-grams only; longer rows go unpruned), [2] the sweep steps
+ * (256 to-rows of one from-row) that contained a hit; the others touched no memory.
+ * Device memory beyond the operands is 12 bytes per hit of capacity plus the sort's copy.
+ * An empty list on either side, or a threshold no sum reaches: PFZ_OK, *out_total = 0, out_row_ptr all zero.
+ * Limits: fewer than 2^31 rows per list (PFZ_ERR_UNSUPPORTED beyond), and the index's own limits (pfz_index_build).  A NaN
+ * min_similarity or one outside [0, 1], capacity < 0, unequal n_cols: PFZ_ERR_INVALID.  Profiling scopes: `k15_join` (the row
+ * walk), `k15_sort_unpack`.  Blocks. */
+int pfz_cossim_join(pfz_ctx *ctx, const pfz_index *to_index, const pfz_csr *from_matrix, int32_t self_join,
+                    double min_similarity, int64_t capacity, int64_t *out_row_ptr, int32_t *out_idx, float *out_sim,
+                    int64_t *out_total, int64_t *out_counters);
+/* The connected components of "cosine >= min_similarity" over ONE list: the pairs of pfz_cossim_join(ctx, index, matrix, 1,
+ * min_similarity, ...), found by the same walk, but none is stored -- the lane that finds a hit unites the two positions in the
+ * lock-free union-find of csrc/k12_core.h.  `matrix` must be the matrix `index` was built from (PFZ_ERR_INVALID otherwise).
+ * Device memory beyond the operands is O(n) whatever the number of hits; there is no capacity and no repeat.  out_label: host
+ * buffer int32[n], out_label[i] = the SMALLEST position in i's component (so out_label[i] <= i); deterministic, whatever order
+ * the device's atomics took.  *out_pairs == pfz_cossim_join's *out_total; *out_components counts singletons too; out_counters as
+ * above.  No rows: PFZ_OK, *out_pairs = *out_components = 0, nothing else is written (out_label may be NULL).  Limits and errors
+ * as pfz_cossim_join, and a NULL out_pairs / out_components is PFZ_ERR_INVALID.  Profiling scope: `k15_components` (forest, row
+ * walk and labels).  Blocks. */
+int pfz_cossim_components(pfz_ctx *ctx, const pfz_index *index, const pfz_csr *matrix, double min_similarity,
+                          int32_t *out_label, int64_t *out_pairs, int64_t *out_components, int64_t *out_counters);
 
 /* ---- K6: reductions on the hot path's output --------------------------------
  * precision_recall_curve (reference polyfuzz/metrics.py:12-53): for every threshold p_k

@@ -123,6 +123,8 @@ SIGNATURES = {
     "pfz_dense_rescore_topn_mixed": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_f32, c_vp]),
     "pfz_dense_join": (ctypes.c_int, [c_vp, c_vp, c_vp, c_f64, c_i64, c_vp, c_vp, c_vp, P(c_i64), c_vp]),
     "pfz_dense_components": (ctypes.c_int, [c_vp, c_vp, c_f64, c_vp, P(c_i64), P(c_i64), c_vp]),
+    "pfz_cossim_join": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_f64, c_i64, c_vp, c_vp, c_vp, P(c_i64), c_vp]),
+    "pfz_cossim_components": (ctypes.c_int, [c_vp, c_vp, c_vp, c_f64, c_vp, P(c_i64), P(c_i64), c_vp]),
     "pfz_pr_curve_host": (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp]),
     "pfz_linkage_top1": (ctypes.c_int, [c_vp, c_vp, c_f64, c_vp, c_vp, c_vp]),
     "pfz_comm_unique_id": (ctypes.c_int, [c_vp]),
@@ -1235,6 +1237,63 @@ def dense_components(ctx, dev, min_similarity, counters=False):
                                        _ptr(work)))
     out = (label, pairs.value, components.value)
     return out + (dict(zip(DENSE_JOIN_COUNTERS, work.tolist())),) if counters else out
+
+
+# ---- K15: the sparse-cosine threshold join and its components --------------------------------------------------------
+
+SPARSE_JOIN_COUNTERS = ("visits", "skipped", "hit_steps")      # pfz_cossim_join's out_counters, in order
+
+
+def check_min_similarity(min_similarity):
+    """a join's threshold: a real number in [0, 1] (ValueError otherwise; NaN compares false) -> float"""
+    if (isinstance(min_similarity, bool) or not isinstance(min_similarity, (int, float, np.integer, np.floating))
+            or not 0.0 <= float(min_similarity) <= 1.0):
+        raise ValueError(f"min_similarity must be a number in [0, 1], not {min_similarity!r}")
+    return float(min_similarity)
+
+
+def sparse_join(ctx, index, from_dev, min_similarity, self_join=False, capacity=None, counters=False):
+    """K15: every pair (row of the DeviceCSR from_dev, row of the DeviceIndex index) whose sparse cosine -- cossim_topn's float32,
+    bit for bit -- is >= min_similarity (as float64: equal is a hit; a pair without a common column never is), as CSR over the
+    from-rows: (row_ptr int64[n + 1], to-index int32[hits] ascending within a row, similarity float32[hits], counts).
+    self_join: from_dev is the matrix the index was built from, and every unordered pair comes once as (i, j), i < j.  capacity:
+    the hits the first call's buffers have room for (None: a modest guess, four per from-row); when the exact total the call
+    returns exceeds it the call is repeated ONCE with room for that total, never more often.  counts: {"pairs": hits}, with
+    counters=True also SPARSE_JOIN_COUNTERS (the last call's)."""
+    t = check_min_similarity(min_similarity)
+    n = from_dev.n_rows
+    work = np.zeros(3, np.int64) if counters else None
+    total = c_i64(0)
+    cap = max(4096, 4 * int(n)) if capacity is None else int(capacity)
+    for _ in range(2):
+        row_ptr = np.empty(n + 1, np.int64)
+        idx, sim = np.empty(cap, np.int32), np.empty(cap, np.float32)
+        check(ctx.lib.pfz_cossim_join(ctx.h, index.h, from_dev.h, int(bool(self_join)), t, cap, _ptr(row_ptr), _ptr(idx), _ptr(sim),
+                                      ctypes.byref(total), _ptr(work)))
+        if total.value <= cap:
+            break
+        cap = total.value
+    assert total.value <= cap                     # (the second call had room for the exact total)
+    hits = total.value
+    counts = {"pairs": hits}
+    if counters:
+        counts.update(zip(SPARSE_JOIN_COUNTERS, work.tolist()))
+    return row_ptr, idx[:hits].copy(), sim[:hits].copy(), counts
+
+
+def sparse_components(ctx, index, dev, min_similarity, counters=False):
+    """K15: the connected components of "sparse cosine >= min_similarity" over the rows of `dev`, the matrix `index` was built
+    from (the pairs of sparse_join's self-join, united on the device, never stored) -- (label int32[n], pairs, components):
+    label[i] is the smallest position in i's component, pairs the number of hits (sparse_join's total), components the number
+    of components, singletons included.  counters=True appends a dict of SPARSE_JOIN_COUNTERS."""
+    t = check_min_similarity(min_similarity)
+    work = np.zeros(3, np.int64) if counters else None
+    label = np.empty(dev.n_rows, np.int32)
+    pairs, components = c_i64(0), c_i64(0)
+    check(ctx.lib.pfz_cossim_components(ctx.h, index.h, dev.h, t, _ptr(label), ctypes.byref(pairs), ctypes.byref(components),
+                                        _ptr(work)))
+    out = (label, pairs.value, components.value)
+    return out + (dict(zip(SPARSE_JOIN_COUNTERS, work.tolist())),) if counters else out
 
 
 # ---- exact rescoring of a 16-bit / int8 top-n (k5_rescore_topn) ------------------------------------------------------

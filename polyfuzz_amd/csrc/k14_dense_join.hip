@@ -185,6 +185,36 @@ __global__ __launch_bounds__(256) void k14_unpack(const uint64_t *__restrict__ k
         for (int64_t r = row + 1; r <= n_from; ++r) row_ptr[r] = total;
 }
 
+// The tail of a threshold join (K14 here, K15 in k15_sparse_join.hip): the `total` appended hits -- distinct keys row << 32 | col,
+// the float32 scores' bits beside them -- sorted, unpacked into CSR over n_from rows and downloaded into the caller's three host
+// arrays.  total == 0: the row pointers are all zero and nothing else is written.  `scope` times the sort and the unpack.  Blocks.
+int join_sort_unpack(pfz_ctx *ctx, const char *scope, const uint64_t *d_keys, const uint32_t *d_vals, int64_t total, int64_t n_from,
+                     int64_t *out_row_ptr, int32_t *out_idx, float *out_sim)
+{
+    if (total == 0) {
+        for (int64_t r = 0; r <= n_from; ++r) out_row_ptr[r] = 0;
+        return PFZ_OK;
+    }
+    DevBuf d_skeys, d_svals, d_ptr, d_idx;
+    {
+        ProfScope ps(ctx, scope);
+        const size_t cap = (size_t)sort_codes_capacity(total);
+        PFZ_TRY(d_skeys.alloc(ctx, cap * sizeof(uint64_t)));
+        PFZ_TRY(d_svals.alloc(ctx, cap * sizeof(uint32_t)));
+        PFZ_TRY(sort_pairs_u64(ctx, d_keys, d_vals, d_skeys.as<uint64_t>(), d_svals.as<uint32_t>(), total));
+        PFZ_TRY(d_ptr.alloc(ctx, (size_t)(n_from + 1) * sizeof(int64_t)));
+        PFZ_TRY(d_idx.alloc(ctx, (size_t)total * sizeof(int32_t)));
+        hipLaunchKernelGGL(k14_unpack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, d_skeys.as<uint64_t>(), total,
+                           n_from, d_ptr.as<int64_t>(), d_idx.as<int32_t>());
+        PFZ_HIP(hipGetLastError());
+    }
+    PFZ_TRY(copy_d2h(ctx, out_row_ptr, d_ptr.p, (size_t)(n_from + 1) * sizeof(int64_t)));
+    PFZ_TRY(copy_d2h(ctx, out_idx, d_idx.p, (size_t)total * sizeof(int32_t)));
+    PFZ_TRY(copy_d2h(ctx, out_sim, d_svals.p, (size_t)total * sizeof(float)));
+    PFZ_HIP(hipStreamSynchronize(ctx->stream));
+    return PFZ_OK;
+}
+
 // the smallest float32 >= t (t in [0, 1])
 static float threshold32(double t)
 {
@@ -262,7 +292,7 @@ static int dense_join_run(pfz_ctx *ctx, const pfz_dense *F, const pfz_dense *T, 
     int64_t grid;
     PFZ_TRY(dense_join_grid("pfz_dense_join", &P, &grid));
 
-    DevBuf d_keys, d_vals, d_state, d_skeys, d_svals, d_ptr, d_idx;
+    DevBuf d_keys, d_vals, d_state;
     PFZ_TRY(d_keys.alloc(ctx, (size_t)capacity * sizeof(uint64_t)));
     PFZ_TRY(d_vals.alloc(ctx, (size_t)capacity * sizeof(float)));
     PFZ_TRY(d_state.alloc(ctx, 3 * sizeof(unsigned long long)));
@@ -283,27 +313,8 @@ static int dense_join_run(pfz_ctx *ctx, const pfz_dense *F, const pfz_dense *T, 
         out_counters[1] = (int64_t)state[2];
     }
     if (total > capacity) return PFZ_OK;       // the caller's buffers stay as they are: it repeats the call with room for `total`
-    if (total == 0) {
-        for (int64_t r = 0; r <= n_from; ++r) out_row_ptr[r] = 0;
-        return PFZ_OK;
-    }
-    {
-        ProfScope ps(ctx, "k14_sort_unpack");
-        const size_t cap = (size_t)sort_codes_capacity(total);
-        PFZ_TRY(d_skeys.alloc(ctx, cap * sizeof(uint64_t)));
-        PFZ_TRY(d_svals.alloc(ctx, cap * sizeof(uint32_t)));
-        PFZ_TRY(sort_pairs_u64(ctx, d_keys.as<uint64_t>(), d_vals.as<uint32_t>(), d_skeys.as<uint64_t>(), d_svals.as<uint32_t>(), total));
-        PFZ_TRY(d_ptr.alloc(ctx, (size_t)(n_from + 1) * sizeof(int64_t)));
-        PFZ_TRY(d_idx.alloc(ctx, (size_t)total * sizeof(int32_t)));
-        hipLaunchKernelGGL(k14_unpack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, d_skeys.as<uint64_t>(), total,
-                           n_from, d_ptr.as<int64_t>(), d_idx.as<int32_t>());
-        PFZ_HIP(hipGetLastError());
-    }
-    PFZ_TRY(copy_d2h(ctx, out_row_ptr, d_ptr.p, (size_t)(n_from + 1) * sizeof(int64_t)));
-    PFZ_TRY(copy_d2h(ctx, out_idx, d_idx.p, (size_t)total * sizeof(int32_t)));
-    PFZ_TRY(copy_d2h(ctx, out_sim, d_svals.p, (size_t)total * sizeof(float)));
-    PFZ_HIP(hipStreamSynchronize(ctx->stream));
-    return PFZ_OK;
+    return join_sort_unpack(ctx, "k14_sort_unpack", d_keys.as<uint64_t>(), d_vals.as<uint32_t>(), total, n_from, out_row_ptr, out_idx,
+                            out_sim);
 }
 
 static int dense_comp_run(pfz_ctx *ctx, const pfz_dense *V, double t, int32_t *out_label, int64_t *out_pairs, int64_t *out_components,

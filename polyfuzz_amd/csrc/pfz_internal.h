@@ -359,4 +359,10 @@ int sort_pairs_u64(pfz_ctx *ctx, const uint64_t *in, const uint32_t *vin, uint64
 int k12_forest_begin(pfz_ctx *ctx, int32_t n, int32_t *parent);
 int k12_forest_flatten(pfz_ctx *ctx, const int32_t *parent, int32_t n, int32_t *label, unsigned long long *n_roots);
 
+// The tail of the threshold joins that append (key = row << 32 | col, float32 score bits) pairs (K14, K15): `total` of them sorted,
+// unpacked into CSR over n_from rows and downloaded into the caller's host arrays; total == 0 zeroes the row pointers.  `scope` is
+// the profiling scope of the sort and the unpack.  Blocks (k14_dense_join.hip).
+int join_sort_unpack(pfz_ctx *ctx, const char *scope, const uint64_t *d_keys, const uint32_t *d_vals, int64_t total, int64_t n_from,
+                     int64_t *out_row_ptr, int32_t *out_idx, float *out_sim);
+
 }  // namespace pfz

@@ -20,7 +20,7 @@ from scipy.sparse import csr_matrix
 
 from .. import _lib
 from ._base import BaseMatcher
-from ._utils import topn_to_frame, object_column, clip_top_n, FrameBuilder, _METHODS
+from ._utils import topn_to_frame, object_column, gather_column, clip_top_n, FrameBuilder, _METHODS
 
 _SPLIT_MIN_ROWS = 20000      # from-rows from which match() has its result handed on in row ranges, the frame built under the device's work
 _SPLIT_EVENT = 48            # context event slots 48 .. 63: range i final
@@ -265,6 +265,67 @@ class TFIDF(BaseMatcher):
         top_n = clip_top_n(self.top_n, to_list)
         lower = float(self.min_similarity) if self.cosine_method in ("sparse", "hip") else 0.0
         return _lib.cossim_topn(ctx, self._dev_index, from_dev, max(top_n, 1), lower, exclude_diag=to_list is None)
+
+    def join(self,
+             from_list: List[str],
+             to_list: List[str] = None,
+             min_similarity: float = 0.8,
+             re_train: bool = True) -> pd.DataFrame:
+        """ Every pair whose TF-IDF cosine is at least `min_similarity` (K15): the frame From, To, Similarity with one row per
+        pair, ordered by from-index, then to-index.  A from-string without a partner has no row.  Similarity is the float32
+        score `match` computes for the pair, unrounded, as float64, and a pair is kept iff that value is >= min_similarity:
+        equal is kept; a pair without a common n-gram never is, also at 0.  Exact in that sense: every such pair is found,
+        whatever their number -- there is no top_n to guess and no n x top_n table comes back.
+
+        The lists are fitted and vectorised exactly as `match` does, so the scores are `match`'s; re_train=False reuses the
+        fitted to-side.  to_list None: the self-join of from_list -- every unordered pair of positions i < j once, as
+        From = from_list[i], To = from_list[j]; never a string with itself, but equal strings at different positions are a pair.
+
+        `top_n`, `min_similarity` of the constructor and `cosine_method` play no part: always the kernel's cosine.
+        min_similarity: a number in [0, 1] (ValueError otherwise).  The frame has the columns single_linkage reads; for the
+        clusters of the self-join's graph see `components`, which never builds the frame.  Sets last_timings and
+        last_counts = {"pairs": hits}. """
+        t = _lib.check_min_similarity(min_similarity)
+        ctx = _lib.Context.default()
+        t0 = time.perf_counter()
+        self_join = not to_list          # (as _extract_tf_idf: no to-list, the from-side IS the indexed matrix)
+        if len(from_list) == 0:
+            if self_join:                # (what fitting nothing says, in match() too)
+                raise ValueError("empty vocabulary; perhaps the documents only contain stop words")
+            if re_train:                 # fitting on to_list + nothing is fitting on to_list
+                self._extract_tf_idf(to_list, None, True)
+            self._require_fitted()
+            row_ptr, idx, sim, counts = np.zeros(1, np.int64), np.zeros(0, np.int32), np.zeros(0, np.float32), {"pairs": 0}
+        else:
+            from_dev, _ = self._extract_tf_idf(from_list, to_list, re_train)
+            row_ptr, idx, sim, counts = _lib.sparse_join(ctx, self._dev_index, from_dev, t, self_join=self_join)
+        t1 = time.perf_counter()
+        names = from_list if self_join else to_list
+        frm = np.repeat(np.arange(len(row_ptr) - 1, dtype=np.int32), np.diff(row_ptr))
+        matches = pd.DataFrame({"From": gather_column(from_list, frm), "To": gather_column(names, idx),
+                                "Similarity": sim.astype(np.float64)}, copy=False)
+        self.last_timings = {"device": (t1 - t0) * 1e3, "frame": (time.perf_counter() - t1) * 1e3}
+        self.last_counts = counts
+        return matches
+
+    def components(self, from_list: List[str], min_similarity: float = 0.8) -> np.ndarray:
+        """ Near-duplicate clusters of `from_list` (K15): int32 labels, label[i] = the smallest position in i's connected
+        component of the graph whose edges are the pairs `join(from_list, min_similarity=...)` reports -- "A ~ B and B ~ C put
+        A, B and C together".  A string with no partner is its own component (label[i] == i).  Exact and deterministic.  The
+        list is fitted as `match(from_list)` does; the pairs are united on the device where they are found and never stored or
+        downloaded.  polyfuzz_amd.linkage.connected_components turns the labels into the three dicts single_linkage returns.
+        `top_n`, `min_similarity` of the constructor and `cosine_method` play no part.  Sets last_timings and
+        last_counts = {"pairs": hits, "components": components}. """
+        t = _lib.check_min_similarity(min_similarity)
+        ctx = _lib.Context.default()
+        t0 = time.perf_counter()
+        if len(from_list) == 0:
+            raise ValueError("empty vocabulary; perhaps the documents only contain stop words")
+        dev, _ = self._extract_tf_idf(from_list, None, True)
+        label, pairs, components = _lib.sparse_components(ctx, self._dev_index, dev, t)
+        self.last_timings = {"device": (time.perf_counter() - t0) * 1e3, "frame": 0.0}
+        self.last_counts = {"pairs": pairs, "components": components}
+        return label
 
     # ---- internals ---------------------------------------------------------------
     def _params(self):
