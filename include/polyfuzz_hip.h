@@ -80,6 +80,9 @@ int pfz_prof_enable(pfz_ctx *ctx, int32_t on);
 int pfz_prof_reset(pfz_ctx *ctx);
 /* total ms and launch count of kernel `name` since the last reset (blocks).  Every form of K3 is timed as
  * `k3_cossim_topn`; `k3_lockstep` (0 ms, a count only) says how many of those launches the lock-step form served.
+ * K4: `k4_indel` (every launch of a call), `k4_indel_general` (its general-kernel launch, merge included), `k4_general_rows`
+ * (0 ms; the count is the number of from-rows the general kernel took), `k4_quad_launches` (0 ms; the count is the number of
+ * quad / octo launches: several short from-strings per workgroup pass).
  * K8: `k8_jaro` (every launch of a call), `k8_jaro_general` (its general-kernel launches), `k8_pairs_scored` (0 ms; the
  * count is the number of pairs whose float64 score was computed).
  * K9: `k9_lev` (every launch of a call), `k9_lev_general` (its general-kernel launches), `k9_pairs_walked` (0 ms; the count is

@@ -900,6 +900,7 @@ static int indel_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T_c,
                 else if (ns == 8) hipLaunchKernelGGL((k4_indel_quad_kernel<16, 8>), qgrid, dim3(256), lds, st, A);
                 else hipLaunchKernelGGL((k4_indel_quad_kernel<16, 4>), qgrid, dim3(256), lds, st, A);
                 PFZ_HIP(hipGetLastError());
+                prof_count(ctx, "k4_quad_launches");
                 PFZ_TRY(merge(st));
             }
             continue;
@@ -941,6 +942,8 @@ static int indel_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T_c,
         A.rows = (const int32_t *)d_rows[6].p;
         A.n_rows = (int32_t)cls[6].size();
         PFZ_TRY(ensure_partial());
+        ProfScope ps(ctx, "k4_indel_general");
+        prof_count(ctx, "k4_general_rows", (int64_t)cls[6].size());
         if (ntop > 0 && pl->idb == 8)
             hipLaunchKernelGGL((k4_indel_general_topn_kernel<8>), dim3((unsigned)gridg), dim3(256), 0, ctx->stream, A, W,
                                (uint64_t *)d_pm.p, (uint64_t *)d_v.p);

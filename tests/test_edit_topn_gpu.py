@@ -223,7 +223,7 @@ def ratio_lists(oracle_mod):
             "wide": (fl16, tl16, oracle_mod.indel_argmax(fl16, tl16, want_matrix=True)[2])}
 
 
-@pytest.mark.parametrize("which,general", [("narrow", False), ("narrow", True), ("wide", False)])
+@pytest.mark.parametrize("which,general", [("narrow", False), ("narrow", True), ("wide", False), ("wide", True)])
 def test_indel_topn_mixed(ctx, ratio_lists, monkeypatch, which, general):
     """from-lengths on both sides of every word class's border -- with ntop > 1 the short ones run in the one-string kernel -- against
     ~200 to-strings, every one twice; 16-bit symbols; everything through the general kernel.  Column 0 == pfz_indel_argmax, which

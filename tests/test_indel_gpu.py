@@ -102,9 +102,10 @@ def test_self_match_removes_first_equal(ctx, oracle_mod, golden):
 
 
 def test_general_kernel_long_strings_and_forced(ctx, oracle_mod, monkeypatch):
-    """From-strings beyond 1024 characters (and alphabets whose match table does not fit LDS) take the general kernel:
-    any number of 64-bit words, match table and V columns in global scratch.  Bit-exact against the oracle; forcing
-    EVERY row through it (PFZ_K4_FORCE_GENERAL) reproduces the word-class kernels' results."""
+    """From-strings beyond 1024 characters (and alphabets whose match table does not fit LDS: those are built in
+    tests/test_indel_table_borders_gpu.py) take the general kernel: any number of 64-bit words, match table and V columns
+    in global scratch.  Bit-exact against the oracle; forcing EVERY row through it (PFZ_K4_FORCE_GENERAL) reproduces the
+    word-class kernels' results (with more rows than workgroups: tests/test_second_row_gpu.py)."""
     from polyfuzz_amd import _lib
     rng = np.random.default_rng(12)
     alpha = np.array(list("abcdefghijklmnop qrst"), dtype=object)
