@@ -94,7 +94,9 @@ int pfz_prof_reset(pfz_ctx *ctx);
  * K14: `k14_join` (the tile kernel of a call), `k14_sort_unpack` (the hits sorted with their scores and turned into CSR),
  * `k14_components` (forest, tile kernel with its hooks, labels).
  * K15: `k15_join` (the row walk of a call), `k15_sort_unpack` (the hits sorted with their scores and turned into CSR),
- * `k15_components` (forest, row walk with its hooks, labels). */
+ * `k15_components` (forest, row walk with its hooks, labels).
+ * K16: `k16_keys_sort` (keys, sort and row pointers), `k16_pairs_join` (the scoring launches of a call, either sink),
+ * `k16_pairs_join_general` (its general-kernel launch), `k16_compact` (the join's scan and compaction). */
 int pfz_prof_get(pfz_ctx *ctx, const char *name, double *total_ms, int64_t *launches);
 
 /* ---- CSR matrices --------------------------------------------------------
@@ -520,6 +522,55 @@ int pfz_indel_components(pfz_ctx *ctx, const pfz_strings *strings, double min_si
 #define PFZ_PAIR_JARO_WINKLER 4
 int pfz_pairs_rescore_topn(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings,
                            const pfz_topn *candidates, int32_t scorer, int32_t ntop, int32_t *out_idx, double *out_score);
+
+/* ---- K16: the candidate pairs at or above an edit-distance similarity, and their components ----
+ * The threshold form of K10: blocking, then "score >= min_similarity" on the few pairs the blocking left -- the record-linkage
+ * rule ("Jaro-Winkler >= 0.9") at a size where all pairs (K11) are not an option, and the only threshold form Jaro and
+ * Jaro-Winkler have.  `candidates` is K10's input: a result buffer of at least from_strings->n rows whose idx half holds, per
+ * from-row, up to candidates->ntop indices into the to-list, read on the device, never downloaded; its val half is ignored.  An
+ * index outside [0, n_to), the -1 of an empty slot among them, is skipped wherever it stands, and -- unlike K10 -- an index that
+ * occurs twice in a row counts once.
+ * Two lists: the candidate pairs are {(i, j) : j in row i}.
+ * to_strings == NULL, or the from-list's own handle: the self-join.  The candidate pairs are the SYMMETRISED table: the unordered
+ * {i, j}, i != j, with j in row i or i in row j.  Each is scored once and reported once as row min(i, j), to-index max(i, j),
+ * with score(strings[min], strings[max]): the lower position is the from-string.  A row's own index in its row is skipped;
+ * equal strings at different positions are a pair.
+ * scorer: PFZ_PAIR_LEVENSHTEIN, _OSA, _JARO, _JARO_WINKLER (1 .. 4).  PFZ_PAIR_RATIO (0) is refused with PFZ_ERR_INVALID: it
+ * lives on 0 .. 100, where a min_similarity in [0, 1] is ambiguous.  A pair's score is the float64 value, bit for bit, that
+ * pfz_pairs_rescore_topn computes for it.  A pair is a hit iff score >= min_similarity, float64 against float64: equal is kept.
+ * Exact among the candidate pairs: every one is scored to its end (no window, no abandon rule, no bound -- the table is short);
+ * a pair the table does not hold is never scored.
+ * Output of pfz_pairs_join, host buffers: CSR over the from-rows.  out_row_ptr int64[n_from + 1]; hit p of row i,
+ * out_row_ptr[i] <= p < out_row_ptr[i + 1]: out_idx[p] the to-index (ascending within a row), out_sim[p] its score.
+ * Deterministic: equal inputs give equal bytes, whatever order the columns of the table's rows stand in.
+ * capacity: the hits out_idx / out_sim have room for (they may be NULL when it is 0).  *out_total is always the exact number of
+ * hits.  When it exceeds `capacity` the call still returns PFZ_OK, has written NONE of the three output arrays (the device never
+ * writes a hit past the capacity either) and is to be repeated with capacity >= *out_total.
+ * out_counters: NULL, or int64[3] -- [0] the table cells that are a candidate pair (inside [0, n_to), not the row's own index
+ * in a self-join; a repeated cell counts every time), [1] the distinct pairs scored, [2] the hits (== *out_total).
+ * from_strings->n == 0, an empty to-list or candidates->ntop == 0: PFZ_OK, zero row pointers, *out_total = 0, no launch.
+ * pfz_pairs_components: out_label int32[n], out_label[i] = the SMALLEST position in i's connected component of the graph whose
+ * edges are the hits of pfz_pairs_join(ctx, strings, NULL, candidates, ...).  The hits are united where they are found, in the
+ * lock-free forest of pfz_lev_components (csrc/k12_core.h), and never stored: no capacity, no repeat; deterministic.
+ * *out_pairs == that join's *out_total, *out_components counts singletons too, out_counters as above.  strings->n == 0: PFZ_OK,
+ * *out_pairs = *out_components = 0, nothing else is written (out_label may be NULL); candidates->ntop == 0: every string its
+ * own label, no launch.
+ * Any length and any alphabet: from-strings of up to 64 characters run in registers (Jaro: against partners of up to 256
+ * characters), everything else, and alphabets whose match table exceeds 60 KiB, in a general -- slow -- kernel.  The to-side
+ * preparation is pfz_indel_*'s, cached on the to-list's handle.  One wave serves a from-string's partners 64 at a time, however
+ * many the symmetrised table gives it.
+ * Call-scoped device memory: 8 B per table cell for the keys and 8 B per cell, the cells rounded up to a power of two, for
+ * their sorted copy; pfz_pairs_join adds 8 B per cell for the scores and 4 B for the hit flags the scan runs over.
+ * PFZ_ERR_INVALID: a NULL argument, scorer 0 or outside 1 .. 4, a NaN min_similarity or one outside [0, 1], capacity < 0, NULL
+ * outputs with capacity > 0, fewer candidate rows than from-strings.  PFZ_ERR_UNSUPPORTED, with the limit in the message:
+ * more than 1024 candidates per row (K10's limit), a list of 2^31 strings or more, n_from * candidates->ntop of 2^31 table cells
+ * or more (the scan over them is 32-bit), a string of 2^30 - 1 characters or more.  Blocks. */
+int pfz_pairs_join(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings, const pfz_topn *candidates,
+                   int32_t scorer, double min_similarity, int64_t capacity, int64_t *out_row_ptr, int32_t *out_idx,
+                   double *out_sim, int64_t *out_total, int64_t *out_counters);
+int pfz_pairs_components(pfz_ctx *ctx, const pfz_strings *strings, const pfz_topn *candidates, int32_t scorer,
+                         double min_similarity, int32_t *out_label, int64_t *out_pairs, int64_t *out_components,
+                         int64_t *out_counters);
 
 /* ---- K5: dense cosine top-n -----------------------------------------------
  * Replaces cosine_similarity on dense embedding matrices

@@ -104,6 +104,8 @@ SIGNATURES = {
     "pfz_indel_join": (ctypes.c_int, [c_vp, c_vp, c_vp, c_f64, c_i64, c_vp, c_vp, c_vp, c_vp, P(c_i64), c_vp]),
     "pfz_indel_components": (ctypes.c_int, [c_vp, c_vp, c_f64, c_vp, P(c_i64), P(c_i64), c_vp]),
     "pfz_pairs_rescore_topn": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "pfz_pairs_join": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_f64, c_i64, c_vp, c_vp, c_vp, P(c_i64), c_vp]),
+    "pfz_pairs_components": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_f64, c_vp, P(c_i64), P(c_i64), c_vp]),
     "pfz_fuzz_extract_one": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "pfz_fuzz_extract_one_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "pfz_fuzz_plan_info": (ctypes.c_int, [c_vp, c_vp, P(c_i64), P(c_i64), P(c_i64), P(c_i64)]),
@@ -955,6 +957,55 @@ def pairs_rescore_topn(ctx, from_dev, to_dev, candidates, scorer, ntop):
     sid = PAIR_SCORERS[scorer] if isinstance(scorer, str) else int(scorer)
     check(ctx.lib.pfz_pairs_rescore_topn(ctx.h, from_dev.h, to_dev.h, candidates.h, sid, int(ntop), _ptr(idx), _ptr(score)))
     return idx, score
+
+
+# K16: the scorers of K10 that live on 0..1 (ratio, on 0..100, has no threshold form), and pfz_pairs_join's out_counters, in order
+PAIR_JOIN_SCORERS = {"levenshtein": 1, "osa": 2, "jaro": 3, "jaro_winkler": 4}
+PAIR_JOIN_COUNTERS = ("candidates", "scored", "pairs")
+
+
+def pairs_join(ctx, from_dev, to_dev, candidates, scorer, min_similarity, capacity=None, counters=False):
+    """K16: the candidate pairs of the DeviceTopN `candidates` (K10's input: row i holds indices into to_dev, anything outside
+    [0, n_to) skipped, an index listed twice counted once) whose score under `scorer` (a PAIR_JOIN_SCORERS name, or a PFZ_PAIR_*
+    id) is >= min_similarity (float64 against float64, equal is a hit), as CSR over the from-rows -- (row_ptr int64[n + 1],
+    to-index int32[hits] ascending within a row, similarity float64[hits]).  to_dev None (or from_dev itself): the self-join over
+    the symmetrised table, every unordered pair {i, j} with j in row i or i in row j once, as (min, max), scored with the lower
+    position as the from-string; a row's own index is skipped.  capacity and the ONE repeat as in lev_join.  counters=True appends
+    a dict of PAIR_JOIN_COUNTERS (the last call's): table cells that are a candidate pair, distinct pairs scored, hits."""
+    t = check_min_similarity(min_similarity)
+    sid = PAIR_JOIN_SCORERS[scorer] if isinstance(scorer, str) else int(scorer)
+    work = np.zeros(3, np.int64) if counters else None
+    total = c_i64(0)
+    to_h = None if to_dev is None else to_dev.h
+    cap = max(4096, 4 * int(from_dev.n)) if capacity is None else int(capacity)
+    for _ in range(2):
+        row_ptr = np.empty(from_dev.n + 1, np.int64)
+        idx, sim = np.empty(cap, np.int32), np.empty(cap, np.float64)
+        check(ctx.lib.pfz_pairs_join(ctx.h, from_dev.h, to_h, candidates.h, sid, t, cap, _ptr(row_ptr), _ptr(idx), _ptr(sim),
+                                     ctypes.byref(total), _ptr(work)))
+        if total.value <= cap:
+            break
+        cap = total.value
+    assert total.value <= cap                     # (the second call had room for the exact total)
+    n = total.value
+    out = (row_ptr, idx[:n].copy(), sim[:n].copy())
+    return out + (dict(zip(PAIR_JOIN_COUNTERS, work.tolist())),) if counters else out
+
+
+def pairs_components(ctx, dev, candidates, scorer, min_similarity, counters=False):
+    """K16: the connected components of the graph whose edges are the hits of pairs_join's self-join over `dev` and `candidates`,
+    united on the device, never stored -- (label int32[n], pairs, components): label[i] is the smallest position in i's component,
+    pairs the number of hits (pairs_join's total), components the number of components, singletons included.  counters=True
+    appends a dict of PAIR_JOIN_COUNTERS."""
+    t = check_min_similarity(min_similarity)
+    sid = PAIR_JOIN_SCORERS[scorer] if isinstance(scorer, str) else int(scorer)
+    work = np.zeros(3, np.int64) if counters else None
+    label = np.empty(dev.n, np.int32)
+    pairs, components = c_i64(0), c_i64(0)
+    check(ctx.lib.pfz_pairs_components(ctx.h, dev.h, candidates.h, sid, t, _ptr(label), ctypes.byref(pairs), ctypes.byref(components),
+                                       _ptr(work)))
+    out = (label, pairs.value, components.value)
+    return out + (dict(zip(PAIR_JOIN_COUNTERS, work.tolist())),) if counters else out
 
 
 # compute_dtype of the dense path -> PFZ_DENSE_* (include/polyfuzz_hip.h)

@@ -27,9 +27,9 @@
 // table in global memory, any length, any alphabet, slow.
 // Bound: integer VALU + LDS look-ups behind a dependent chain of gathered loads (code unit -> lut -> PM) per to-character
 // (measured beside the all-pairs kernels).
-#include "edit_walk.h"
-#include "k10_core.h"
-#include "k8_core.h"
+// The score of one pair -- pair_score_reg, pair_score_general, the PAIR_* and MODE_* constants, the view of the two lists -- is
+// pair_score.h's, which K16 (k16_pairs_join.hip) includes too.
+#include "pair_score.h"
 #include "topn_wave.h"
 
 #include <algorithm>
@@ -37,23 +37,12 @@
 
 namespace pfz {
 
-constexpr int kPairsMaxCandidates = 1024;      // per row, as pfz_dense_rescore_topn
-constexpr int kPairsJaroRegLen = 256;          // to-positions whose flags the Jaro register kernel keeps
-
-enum { PAIR_RATIO = 0, PAIR_LEVENSHTEIN = 1, PAIR_OSA = 2, PAIR_JARO = 3, PAIR_JARO_WINKLER = 4 };
-enum { MODE_REG32 = 0, MODE_REG64 = 1, MODE_GENERAL = 2 };
-
-struct PairArgs : FromView {   // (the plan's packed groups are not read here)
-    const void *b_chars;       // to-strings, the raw list
-    int32_t b_width;
-    const int64_t *b_off;      // [n_to + 1]
-    int64_t n_to;
+struct PairArgs : PairView {
     const int32_t *cand;       // [>= n_from][m] candidate to-indices; anything outside [0, n_to) is skipped
     int32_t m;
     const int32_t *rows;       // the from-rows of this launch (register kernels)
     int32_t n_rows;
     uint8_t *mode;             // [n_from] MODE_*: the general kernel serves the rows marked MODE_GENERAL
-    int32_t scorer;            // PAIR_*
     int32_t ntop;
     int32_t *out_idx;          // [n_from][ntop]
     double *out_score;
@@ -73,51 +62,6 @@ __device__ inline void pair_store_row(const PairArgs &A, int64_t row, const Topn
     if (lane < A.ntop) {
         A.out_idx[row * A.ntop + lane] = l.idx == INT_MAX ? -1 : l.idx;
         A.out_score[row * A.ntop + lane] = l.idx == INT_MAX ? 0.0 : l.score;
-    }
-}
-
-// one pair in registers: the from-string is in the wave's match table `pm`, the lane walks its to-string [b0, b0 + lb)
-template <typename WORD, int FAMILY>      // FAMILY: PAIR_RATIO, PAIR_LEVENSHTEIN, PAIR_OSA, PAIR_JARO (Winkler: A.scorer)
-__device__ __forceinline__ double pair_score_reg(const PairArgs &A, const WORD *pm, int la, int64_t b0, int lb)
-{
-    if constexpr (FAMILY == PAIR_RATIO) {
-        WORD v = (WORD)~(WORD)0;
-        for (int t = 0; t < lb; ++t) lcs_step_reg<WORD>(v, pm[edit_symbol(A, A.b_chars, A.b_width, b0 + t)]);
-        const int lcs = __popcll((uint64_t)(WORD)~v);
-        return la + lb == 0 ? 100.0 : ratio_of(lcs, (int64_t)la + lb);
-    }
-    else if constexpr (FAMILY == PAIR_LEVENSHTEIN || FAMILY == PAIR_OSA) {
-        LevState<WORD> s;
-        lev_begin(s, la);
-        for (int t = 0; t < lb; ++t) lev_step<WORD, FAMILY == PAIR_OSA>(s, pm[edit_symbol(A, A.b_chars, A.b_width, b0 + t)], true);
-        return lev_similarity(lev_distance(s.dist, la, lb), la, lb);
-    }
-    else {
-        constexpr int WB = (int)sizeof(WORD) * 8;
-        constexpr int NB = kPairsJaroRegLen / WB;      // lb <= 256: the caller's promise
-        JaroFlags<WORD> s;
-        WORD fb[NB];
-        jaro_begin(s, jaro_range(la, lb));
-#pragma unroll
-        for (int k = 0; k < NB; ++k) {
-            s.fb = 0;
-            const int hi = min(lb, (k + 1) * WB);
-            for (int j = k * WB; j < hi; ++j) jaro_match<WORD>(s, pm[edit_symbol(A, A.b_chars, A.b_width, b0 + j)], j, j - k * WB);
-            fb[k] = s.fb;
-        }
-        const int m = __popcll((uint64_t)s.fa);
-        const int prefix = jaro_prefix(s.pre);
-        int half_t = 0;
-        if (m >= 2) {          // (one flagged pair cannot be out of order)
-#pragma unroll
-            for (int k = 0; k < NB; ++k) {
-                s.fb = fb[k];
-                const int hi = min(lb, (k + 1) * WB);
-                for (int j = k * WB; j < hi; ++j)
-                    half_t += jaro_transpose<WORD>(s, pm[edit_symbol(A, A.b_chars, A.b_width, b0 + j)], j - k * WB);
-            }
-        }
-        return jaro_score(m, half_t, la, lb, prefix, A.scorer == PAIR_JARO_WINKLER);
     }
 }
 
@@ -161,78 +105,6 @@ __global__ __launch_bounds__(64) void k10_pairs_kernel(PairArgs A)
         pair_store_row(A, row, list);
         pm_reg_clear(pm, my_sym);
     }
-}
-
-// one pair of the general kernel: the from-string's match table `pm` (WA words per symbol, W of them in use) and this lane's words
-// s0 / s1 / s2[w * 64] are in global memory
-__device__ __forceinline__ double pair_score_general(const PairArgs &A, const uint64_t *pm, uint64_t *s0, uint64_t *s1, uint64_t *s2,
-                                                     int WA, int W, int la, int64_t b0, int lb)
-{
-    if (A.scorer == PAIR_RATIO) {
-        for (int w = 0; w < W; ++w) s0[(int64_t)w * 64] = ~0ull;
-        for (int t = 0; t < lb; ++t) {
-            const uint64_t *pmc = pm + (int64_t)edit_symbol(A, A.b_chars, A.b_width, b0 + t) * WA;
-            uint64_t carry = 0;
-            for (int w = 0; w < W; ++w) {
-                uint64_t v = s0[(int64_t)w * 64];
-                lcs_step_word(v, pmc[w], carry);
-                s0[(int64_t)w * 64] = v;
-            }
-        }
-        int lcs = 0;
-        for (int w = 0; w < W; ++w) lcs += __popcll(~s0[(int64_t)w * 64]);
-        return la + lb == 0 ? 100.0 : ratio_of(lcs, (int64_t)la + lb);
-    }
-    if (A.scorer == PAIR_LEVENSHTEIN || A.scorer == PAIR_OSA) {
-        // s0 / s1 / s2: VP / VN / the previous step's D0
-        const bool osa = A.scorer == PAIR_OSA;
-        lev_column_begin(s0, s1, s2, W, la, 64);
-        const uint64_t last = la > 0 ? 1ull << ((la - 1) % 64) : 0ull;
-        int dist = la;
-        int c_prev = 0;                                         // (symbol 0: an empty table entry)
-        for (int t = 0; t < lb; ++t) {
-            const int c = edit_symbol(A, A.b_chars, A.b_width, b0 + t);
-            const uint64_t *eq = pm + (int64_t)c * WA, *eq_prev = pm + (int64_t)c_prev * WA;
-            dist += osa ? lev_column_step<true>(s0, s1, s2, eq, eq_prev, W, last, 64) : lev_column_step<false>(s0, s1, s2, eq, eq_prev, W, last, 64);
-            c_prev = c;
-        }
-        return lev_similarity(lev_distance(dist, la, lb), la, lb);
-    }
-    // Jaro.  s0: the flagged from-positions (W words), s1: the flagged to-positions ((lb + 63) / 64 words <= WS)
-    const int WBl = lb > 0 ? (lb + 63) / 64 : 1;
-    const int range = jaro_range(la, lb);
-    for (int w = 0; w < W; ++w) s0[(int64_t)w * 64] = 0ull;
-    for (int w = 0; w < WBl; ++w) s1[(int64_t)w * 64] = 0ull;
-    int m = 0;
-    uint32_t pre = 0;
-    for (int t = 0; t < lb; ++t) {
-        const uint64_t *pmc = pm + (int64_t)edit_symbol(A, A.b_chars, A.b_width, b0 + t) * WA;
-        if (t < 4) pre |= (uint32_t)((pmc[0] >> t) & 1) << t;
-        const int lo = max(t - range, 0), hi = min(t + range, la - 1);
-        for (int w = lo >> 6; w <= hi >> 6 && lo <= hi; ++w) {
-            const uint64_t f = s0[(int64_t)w * 64];
-            const uint64_t x = pmc[w] & bit_span<uint64_t>(max(lo - 64 * w, 0), min(hi - 64 * w, 63)) & ~f;
-            if (x) {
-                s0[(int64_t)w * 64] = f | (x & (0 - x));
-                s1[(int64_t)(t >> 6) * 64] |= 1ull << (t & 63);
-                ++m;
-                break;
-            }
-        }
-    }
-    int half_t = 0;
-    if (m >= 2) {
-        int wa = 0;
-        uint64_t cur = s0[0];
-        for (int t = 0; t < lb; ++t) {
-            if (!((s1[(int64_t)(t >> 6) * 64] >> (t & 63)) & 1)) continue;
-            while (cur == 0 && wa + 1 < W) cur = s0[(int64_t)(++wa) * 64];      // (as many flags on either side)
-            const uint64_t low = cur & (0 - cur);
-            cur ^= low;
-            half_t += !(pm[(int64_t)edit_symbol(A, A.b_chars, A.b_width, b0 + t) * WA + wa] & low);
-        }
-    }
-    return jaro_score(m, half_t, la, lb, jaro_prefix(pre), A.scorer == PAIR_JARO_WINKLER);
 }
 
 // The general case: any lengths, any alphabet.  One wave per workgroup and from-string; the match table of the from-string (WA

@@ -143,7 +143,9 @@ def connected_components(strings: List[str], model,
     `components` finds the pairs and unites them on the device (K12; "indel": K13), and only one label per string comes back.
     Or an Embeddings model (K14, the cosine of the vectors); `embeddings`, when given, are the strings' ready-made row vectors
     and are handed to its `components` -- equal strings must then have equal vectors.  Or a TFIDF model (K15, the sparse cosine
-    `match` scores with; the list is fitted as `match(strings)` does)."""
+    `match` scores with; the list is fitted as `match(strings)` does).  Or a BlockedEditDistance with scorer "levenshtein", "osa",
+    "jaro" or "jaro_winkler" (K16): the components of the pairs among its symmetrised TF-IDF candidates that reach min_similarity --
+    equal strings share one whenever the blocking stage lists one for the other."""
     strings = list(strings)
     extra = {} if embeddings is None else {"embeddings": embeddings}
     return dicts_from_labels(strings, model.components(strings, min_similarity, **extra))

@@ -4,7 +4,8 @@ The reference's edit-distance loop scores every from-string against every to-str
 quadratic.  Record linkage at scale is done in two stages: a cheap, high-recall candidate search ("blocking") -- here the
 character n-gram TF-IDF matcher's top `candidates` per from-string (polyfuzz/models/_utils.py:82-91), left in HBM by
 TFIDF.match_device -- and an exact string scorer on those few pairs only: K10 (csrc/k10_pairs.hip), which scores the candidate
-table under ratio / Levenshtein / OSA / Jaro / Jaro-Winkler and re-ranks every row.
+table under ratio / Levenshtein / OSA / Jaro / Jaro-Winkler and re-ranks every row.  K16 (csrc/k16_pairs_join.hip) holds the same
+table against a threshold instead: the candidate pairs at or above a similarity, or their connected components.
 """
 import time
 from typing import Callable, List, Tuple, Union
@@ -55,9 +56,17 @@ class BlockedEditDistance(BaseMatcher):
       * in a self-match (to_list=None) a row's own index is never a candidate and equal strings elsewhere in the list are: TF-IDF's
         self-match rule, not EditDistance's (which leaves out the first equal element of the list).
 
+    join(from_list, to_list, min_similarity) and components(from_list, min_similarity) are the threshold forms (K16): every
+    candidate pair whose score is >= min_similarity, as a frame of pairs or as one component label per string.  They are exact
+    among the SYMMETRISED candidates -- in a self-join the unordered pairs {i, j} with j among i's candidates or i among j's, each
+    scored once with the lower position as the from-string --; a row's own index is never a candidate; `top_n` and `normalize`
+    play no part; "ratio" (0..100) is refused: the scorers are "levenshtein", "osa", "jaro" and "jaro_winkler".
+
     match(..., re_train=False) reuses the fitted TF-IDF side, and the resident raw to-list when the list it is handed equals the
     one uploaded last (EditDistance's rule).  There is no CPU fallback.  Pickling leaves the device handles behind.
     """
+    last_counts = None      # {"candidates", "scored", "pairs"[, "components"]} of the last `join` / `components` call
+
     def __init__(self,
                  scorer: Union[Callable, str, None] = "ratio",
                  candidates: int = 32,
@@ -121,7 +130,6 @@ class BlockedEditDistance(BaseMatcher):
 
     def _rescore(self, from_list, to_list, re_train):
         """(index int32[n, ntop], score float64[n, ntop], the choices' list, (start, candidates final, rescored) times)"""
-        self_match = to_list is None
         m = clip_top_n(self.candidates, to_list)                  # what TFIDF.match_device leaves per row (_utils.py:54-56)
         ntop = max(1, clip_top_n(self.top_n, to_list))
         if ntop > max(m, 1):
@@ -130,6 +138,14 @@ class BlockedEditDistance(BaseMatcher):
             raise _lib.PfzUnsupported(-4, f"BlockedEditDistance.top_n = {ntop} exceeds the limit of {_lib.PAIR_MAX_TOP_N} best choices per from-string")
         if m > _lib.PAIR_MAX_CANDIDATES:
             raise _lib.PfzUnsupported(-4, f"BlockedEditDistance.candidates = {m} exceeds the limit of {_lib.PAIR_MAX_CANDIDATES} per from-string")
+        ctx, f_dev, t_dev, cand, names, t0, t1 = self._block(from_list, to_list, re_train)
+        idx, score = _lib.pairs_rescore_topn(ctx, f_dev, t_dev, cand, self._scorer_name, ntop)
+        return idx, score, names, (t0, t1, time.perf_counter())
+
+    def _block(self, from_list, to_list, re_train):
+        """The blocking stage and the two raw lists on the device: (context, from-list, to-list -- the from-list's own handle in a
+        self-match --, the candidate table in HBM, the choices' list, start time, time when the table was final)"""
+        self_match = to_list is None
         ctx = _lib.Context.default()
         from ._rapidfuzz import upload_for
         t0 = time.perf_counter()
@@ -147,10 +163,75 @@ class BlockedEditDistance(BaseMatcher):
         else:
             t_dev = held if reuse_to else upload_for(ctx, self._scorer_name, names)
             self._to_dev, self._to_names = t_dev, snap
-        ctx.sync()          # (for last_timings' split alone: K10's entry blocks behind the same stream anyway)
-        t1 = time.perf_counter()
-        idx, score = _lib.pairs_rescore_topn(ctx, f_dev, t_dev, cand, self._scorer_name, ntop)
-        return idx, score, names, (t0, t1, time.perf_counter())
+        ctx.sync()          # (for last_timings' split alone: K10's and K16's entries block behind the same stream anyway)
+        return ctx, f_dev, t_dev, cand, names, t0, time.perf_counter()
+
+    def _check_join(self, what, min_similarity, to_list):
+        """the refusals of join / components, before any device call: the scorer, then the threshold -> float"""
+        if self._scorer_name not in _lib.PAIR_JOIN_SCORERS:
+            raise NotImplementedError(
+                f"BlockedEditDistance.{what} runs on the GPU for the scorers {tuple(_lib.PAIR_JOIN_SCORERS)}; scorer "
+                f"{self._scorer_name!r} lives on 0..100, where a min_similarity in [0, 1] is ambiguous, and has no threshold kernel")
+        t = _lib.check_min_similarity(min_similarity)
+        m = clip_top_n(self.candidates, to_list)                  # as _rescore clips it
+        if m > _lib.PAIR_MAX_CANDIDATES:
+            raise _lib.PfzUnsupported(-4, f"BlockedEditDistance.candidates = {m} exceeds the limit of {_lib.PAIR_MAX_CANDIDATES} per from-string")
+        return t
+
+    def join(self,
+             from_list: List[str],
+             to_list: List[str] = None,
+             min_similarity: float = 0.8,
+             re_train: bool = True) -> pd.DataFrame:
+        """ Every CANDIDATE pair at least `min_similarity` similar under the scorer (K16): the frame From, To, Similarity with one
+        row per pair, ordered by from-index, then to-index.  A from-string without such a partner has no row.  Similarity is the
+        scorer's own float64, unrounded -- the value `match` computes for the pair -- and a pair is kept iff that float64 is >=
+        min_similarity (equal is kept).
+
+        The candidates are `match`'s: every from-string's `candidates` nearest TF-IDF neighbours (clipped to the number of distinct
+        to-strings), found by the same blocking stage and left in HBM.  Exact among them: every candidate pair is scored to its
+        end; a pair the blocking stage did not propose is never scored, however similar.
+
+        to_list None: the self-join of from_list over the SYMMETRISED candidate table -- every unordered pair of positions {i, j},
+        i != j, with j among i's candidates or i among j's, once, as From = from_list[min], To = from_list[max], scored with the
+        lower position as the from-string.  A row's own index is never a candidate; equal strings at different positions are a pair.
+
+        `normalize` is NOT applied: a rescaled score no longer means the threshold.  `top_n` plays no part.
+        re_train=False reuses the fitted TF-IDF side and the resident raw to-list by `match`'s rule.
+
+        Scorers "levenshtein", "osa", "jaro" and "jaro_winkler" (NotImplementedError otherwise: "ratio" lives on 0..100);
+        min_similarity: a number in [0, 1] (ValueError otherwise).  Sets last_timings = {"tfidf", "k16", "frame"} and last_counts =
+        {"candidates": table cells that are a candidate pair, "scored": distinct pairs scored, "pairs": hits}. """
+        t = self._check_join("join", min_similarity, to_list)
+        ctx, f_dev, t_dev, cand, names, t0, t1 = self._block(from_list, to_list, re_train)
+        row_ptr, idx, sim, counts = _lib.pairs_join(ctx, f_dev, None if to_list is None else t_dev, cand, self._scorer_name, t,
+                                                    counters=True)
+        t2 = time.perf_counter()
+        frm = np.repeat(np.arange(len(from_list), dtype=np.int32), np.diff(row_ptr))
+        matches = pd.DataFrame({"From": gather_column(from_list, frm), "To": gather_column(names, idx), "Similarity": sim}, copy=False)
+        self.last_timings = {"tfidf": (t1 - t0) * 1e3, "k16": (t2 - t1) * 1e3, "frame": (time.perf_counter() - t2) * 1e3}
+        self.last_counts = counts
+        return matches
+
+    def components(self,
+                   from_list: List[str],
+                   min_similarity: float = 0.8) -> np.ndarray:
+        """ Clusters of from_list (K16 into K12's forest): int32 labels, label[i] = the smallest position in i's connected component
+        of the graph whose edges are the pairs `join(from_list, min_similarity=...)` reports -- "A ~ B and B ~ C put A, B and C
+        together".  A string with no partner is its own (label[i] == i).  Deterministic.  The pairs are united on the device where
+        they are found and never stored or downloaded.  Blocked: two strings share a component only through chains of CANDIDATE
+        pairs, so equal strings do whenever the blocking stage lists one for the other -- not when there are more copies than
+        `candidates`, or when the string has no n-gram.  polyfuzz_amd.linkage.connected_components turns the labels into the three
+        dicts single_linkage returns.
+
+        `normalize` is NOT applied.  Scorers and min_similarity as for `join`.  Sets last_timings = {"tfidf", "k16", "frame"} and
+        last_counts = {"candidates", "scored", "pairs", "components"}. """
+        t = self._check_join("components", min_similarity, None)
+        ctx, f_dev, _, cand, _, t0, t1 = self._block(from_list, None, True)
+        label, pairs, components, counts = _lib.pairs_components(ctx, f_dev, cand, self._scorer_name, t, counters=True)
+        self.last_timings = {"tfidf": (t1 - t0) * 1e3, "k16": (time.perf_counter() - t1) * 1e3, "frame": 0.0}
+        self.last_counts = dict(counts, components=components)
+        return label
 
     # a matcher is pickled by joblib (reference polyfuzz.py:429-457): device handles stay behind (the TFIDF keeps a host copy of its fit)
     def __getstate__(self):
