@@ -46,6 +46,7 @@ typedef struct pfz_topn pfz_topn;     /* device-resident (idx int32, score fp32)
 typedef struct pfz_strings pfz_strings; /* device-resident packed string list */
 typedef struct pfz_tfidf pfz_tfidf;   /* fitted vectoriser: vocabulary + idf */
 typedef struct pfz_comm pfz_comm;     /* RCCL communicator bound to a context (one process per GPU) */
+typedef struct pfz_pairs pfz_pairs;   /* device-resident pair list of a threshold join: sorted keys row << 32 | col + fp32 scores */
 
 /* ---- library / context -------------------------------------------------- */
 int pfz_version(void);
@@ -96,7 +97,9 @@ int pfz_prof_reset(pfz_ctx *ctx);
  * K15: `k15_join` (the row walk of a call), `k15_sort_unpack` (the hits sorted with their scores and turned into CSR),
  * `k15_components` (forest, row walk with its hooks, labels).
  * K16: `k16_keys_sort` (keys, sort and row pointers), `k16_pairs_join` (the scoring launches of a call, either sink),
- * `k16_pairs_join_general` (its general-kernel launch), `k16_compact` (the join's scan and compaction). */
+ * `k16_pairs_join_general` (its general-kernel launch), `k16_compact` (the join's scan and compaction).
+ * K17 (the key entries): K16's scopes -- `k16_keys_sort` then holds the row pointers alone --, `k17_items` (the work items: count,
+ * scan, fill); pfz_cossim_join_dev: `k15_join` once per launch, `k15_sort`. */
 int pfz_prof_get(pfz_ctx *ctx, const char *name, double *total_ms, int64_t *launches);
 
 /* ---- CSR matrices --------------------------------------------------------
@@ -571,6 +574,53 @@ int pfz_pairs_join(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_stri
 int pfz_pairs_components(pfz_ctx *ctx, const pfz_strings *strings, const pfz_topn *candidates, int32_t scorer,
                          double min_similarity, int32_t *out_label, int64_t *out_pairs, int64_t *out_components,
                          int64_t *out_counters);
+
+/* ---- K17: a threshold join as the blocking key of K16 ----
+ * A candidate table holds a fixed number of neighbours per row; a list whose clusters have thousands of members wants a
+ * similarity instead.  pfz_pairs is a threshold join's result left on the device: n_from, n_to, a self flag, `count` distinct keys
+ * row << 32 | col in ascending order and the float32 score beside each.  It belongs to the context that made it.
+ * pfz_cossim_join_dev: pfz_cossim_join (K15) without the way back -- the same walk, then the sort; nothing is unpacked, nothing
+ * but the call's state words is downloaded.  Operands, hit rule, limits and errors are pfz_cossim_join's; out_counters is its
+ * int64[3], of the last launch.  The capacity is handled inside: the first launch has room for capacity_hint hits (0: max(4096,
+ * 4 per from-row)); when the exact total exceeds that room there is exactly ONE repeat, with room for the exact total.
+ * capacity_hint < 0: PFZ_ERR_INVALID.  An empty list on either side, or a threshold no sum reaches: a valid handle with count 0.
+ * 2^31 pairs or more: PFZ_ERR_UNSUPPORTED (the scan of the kernels that walk the keys is 32-bit).  Device memory of the handle: 12
+ * bytes per pair, the pairs rounded up to a power of two.  Profiling scopes: `k15_join` (once per launch), `k15_sort`.  Blocks
+ * until the walk's total is known; the sort is enqueued.
+ * pfz_pairs_free: NULL is allowed.  pfz_pairs_count: the number of pairs; pfz_pairs_shape: the sizes of the two lists the handle
+ * was made for and whether it is a self-join's (any of the three outputs may be NULL).  pfz_pairs_download: the CSR pfz_cossim_join would
+ * have returned for the same call, byte for byte -- out_row_ptr int64[n_from + 1], out_idx int32[count], out_sim float[count]
+ * (the last two may be NULL when count is 0); for tests and for callers that want the pairs themselves.  Blocks.
+ * pfz_pairs_join_keys / pfz_pairs_components_keys: pfz_pairs_join / pfz_pairs_components with the handle in place of the table.
+ * The candidate pairs are exactly the handle's keys: (row, col) of a two-list handle; of a self handle the unordered pairs, each
+ * once with row < col, scored with the lower position as the from-string.  Score, hit rule (score >= min_similarity, equal is
+ * kept), output, order, capacity rule (NONE of the arrays written when *out_total exceeds the capacity), determinism and the
+ * scorers (1 .. 4; PFZ_PAIR_RATIO is refused with the same message) are K16's; so are the components' labels, *out_pairs and
+ * *out_components.  A handle with count 0, or an empty list: zero row pointers (every string its own label), no launch.
+ * The keys are walked as they lie: no key kernel, no sort.  Where K16 gives a wave a from-row with all its partners, these entries
+ * deal WORK ITEMS, (row, slice) with at most 64 partners (csrc/k17_core.h): behind a threshold a row's partners have no bound,
+ * and a row of thousands would keep one wave busy long after the others are done.  Items are built on the device from the row
+ * pointers (count, scan, fill); each sets up and clears its row's match table itself.  Jaro's hand-over of a partner beyond 256
+ * characters to the general kernel is decided per item, so every pair is scored exactly once.
+ * out_counters: NULL, or int64[4] -- [0] the keys, [1] the distinct pairs scored (== [0]), [2] the hits, [3] the work items.
+ * Call-scoped device memory: 4 B per from-row for the row pointers, 8 B per from-row and 13 B per item for the items;
+ * pfz_pairs_join_keys adds 12 B per key for the scores and the hit flags.
+ * PFZ_ERR_INVALID: a NULL argument, scorer 0 or outside 1 .. 4, a NaN min_similarity or one outside [0, 1], capacity < 0, NULL
+ * outputs with capacity > 0, a handle of another context, lists whose sizes differ from the handle's n_from / n_to, a self handle
+ * with a to-list that is not the from-list's own handle, a two-list handle without a to-list, pfz_pairs_components_keys with a
+ * two-list handle.  PFZ_ERR_UNSUPPORTED: K16's limits on the lists and their strings.  Blocks. */
+int pfz_cossim_join_dev(pfz_ctx *ctx, const pfz_index *to_index, const pfz_csr *from_matrix, int32_t self_join,
+                        double min_similarity, int64_t capacity_hint, pfz_pairs **out, int64_t *out_counters);
+void pfz_pairs_free(pfz_pairs *pairs);
+int pfz_pairs_count(const pfz_pairs *pairs, int64_t *out_count);
+int pfz_pairs_shape(const pfz_pairs *pairs, int64_t *out_n_from, int64_t *out_n_to, int32_t *out_self_join);
+int pfz_pairs_download(pfz_ctx *ctx, const pfz_pairs *pairs, int64_t *out_row_ptr, int32_t *out_idx, float *out_sim);
+int pfz_pairs_join_keys(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings, const pfz_pairs *pairs,
+                        int32_t scorer, double min_similarity, int64_t capacity, int64_t *out_row_ptr, int32_t *out_idx,
+                        double *out_sim, int64_t *out_total, int64_t *out_counters);
+int pfz_pairs_components_keys(pfz_ctx *ctx, const pfz_strings *strings, const pfz_pairs *pairs, int32_t scorer,
+                              double min_similarity, int32_t *out_label, int64_t *out_pairs, int64_t *out_components,
+                              int64_t *out_counters);
 
 /* ---- K5: dense cosine top-n -----------------------------------------------
  * Replaces cosine_similarity on dense embedding matrices

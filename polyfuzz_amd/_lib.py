@@ -106,6 +106,13 @@ SIGNATURES = {
     "pfz_pairs_rescore_topn": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
     "pfz_pairs_join": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_f64, c_i64, c_vp, c_vp, c_vp, P(c_i64), c_vp]),
     "pfz_pairs_components": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_f64, c_vp, P(c_i64), P(c_i64), c_vp]),
+    "pfz_cossim_join_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_f64, c_i64, P(c_vp), c_vp]),
+    "pfz_pairs_free": (None, [c_vp]),
+    "pfz_pairs_count": (ctypes.c_int, [c_vp, P(c_i64)]),
+    "pfz_pairs_shape": (ctypes.c_int, [c_vp, P(c_i64), P(c_i64), P(c_i32)]),
+    "pfz_pairs_download": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "pfz_pairs_join_keys": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_f64, c_i64, c_vp, c_vp, c_vp, P(c_i64), c_vp]),
+    "pfz_pairs_components_keys": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_f64, c_vp, P(c_i64), P(c_i64), c_vp]),
     "pfz_fuzz_extract_one": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "pfz_fuzz_extract_one_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "pfz_fuzz_plan_info": (ctypes.c_int, [c_vp, c_vp, P(c_i64), P(c_i64), P(c_i64), P(c_i64)]),
@@ -1345,6 +1352,86 @@ def sparse_components(ctx, index, dev, min_similarity, counters=False):
                                         _ptr(work)))
     out = (label, pairs.value, components.value)
     return out + (dict(zip(SPARSE_JOIN_COUNTERS, work.tolist())),) if counters else out
+
+
+# ---- K17: a sparse-cosine threshold join left on the device, and K16 over its keys -----------------------------------
+
+PAIR_SLICE = 64                        # kPairSlice of csrc/k17_core.h: partners per work item of the key entries
+PAIR_KEYS_COUNTERS = ("candidates", "scored", "pairs", "items")      # pfz_pairs_join_keys' out_counters, in order
+
+
+class DevicePairs(_Handle):
+    """A threshold join's pairs in HBM (pfz_pairs): n sorted keys row << 32 | col with their float32 scores, over n_from x n_to
+    positions; self_join: one list, every unordered pair once with row < col."""
+    _free = "pfz_pairs_free"
+
+    def __init__(self, ctx, h):
+        super().__init__(ctx, h)
+        n, n_from, n_to, self_join = c_i64(0), c_i64(0), c_i64(0), c_i32(0)
+        check(ctx.lib.pfz_pairs_count(h, ctypes.byref(n)))
+        check(ctx.lib.pfz_pairs_shape(h, ctypes.byref(n_from), ctypes.byref(n_to), ctypes.byref(self_join)))
+        self.n, self.n_from, self.n_to, self.self_join = n.value, n_from.value, n_to.value, bool(self_join.value)
+
+    def download(self):
+        """(row_ptr int64[n_from + 1], to-index int32[n], similarity float32[n]): sparse_join's first three, byte for byte"""
+        row_ptr = np.empty(self.n_from + 1, np.int64)
+        idx, sim = np.empty(self.n, np.int32), np.empty(self.n, np.float32)
+        check(self.ctx.lib.pfz_pairs_download(self.ctx.h, self.h, _ptr(row_ptr), _ptr(idx), _ptr(sim)))
+        return row_ptr, idx, sim
+
+
+def sparse_join_dev(ctx, index, from_dev, min_similarity, self_join=False, capacity_hint=None, counters=False):
+    """K15 with its result left on the device: the pairs sparse_join(ctx, index, from_dev, min_similarity, self_join) reports, as
+    a DevicePairs.  capacity_hint: the hits the first launch has room for (None: the library's default, max(4096, 4 per
+    from-row)); a larger total costs exactly one repeat inside the call.  counters=True: (pairs, dict of SPARSE_JOIN_COUNTERS)."""
+    t = check_min_similarity(min_similarity)
+    hint = 0 if capacity_hint is None else int(capacity_hint)
+    if hint < 0:
+        raise ValueError(f"capacity_hint must be >= 0, not {capacity_hint!r}")
+    work = np.zeros(3, np.int64) if counters else None
+    h = c_vp()
+    check(ctx.lib.pfz_cossim_join_dev(ctx.h, index.h, from_dev.h, int(bool(self_join)), t, hint, ctypes.byref(h), _ptr(work)))
+    pairs = DevicePairs(ctx, h)
+    return (pairs, dict(zip(SPARSE_JOIN_COUNTERS, work.tolist()))) if counters else pairs
+
+
+def pairs_join_keys(ctx, from_dev, to_dev, pairs, scorer, min_similarity, capacity=None, counters=False):
+    """K17: pairs_join with the DevicePairs `pairs` in place of the table -- the candidate pairs are exactly its keys (a self-join's:
+    to_dev None or from_dev itself, every pair once with row < col, the lower position the from-string).  Score, hit rule, CSR,
+    capacity and the ONE repeat as pairs_join.  counters=True appends a dict of PAIR_KEYS_COUNTERS: the keys, the distinct pairs
+    scored (== the keys), the hits, the (row, slice) work items of at most PAIR_SLICE partners the kernels were dealt."""
+    t = check_min_similarity(min_similarity)
+    sid = PAIR_JOIN_SCORERS[scorer] if isinstance(scorer, str) else int(scorer)
+    work = np.zeros(4, np.int64) if counters else None
+    total = c_i64(0)
+    to_h = None if to_dev is None else to_dev.h
+    cap = max(4096, 4 * int(from_dev.n)) if capacity is None else int(capacity)
+    for _ in range(2):
+        row_ptr = np.empty(from_dev.n + 1, np.int64)
+        idx, sim = np.empty(cap, np.int32), np.empty(cap, np.float64)
+        check(ctx.lib.pfz_pairs_join_keys(ctx.h, from_dev.h, to_h, pairs.h, sid, t, cap, _ptr(row_ptr), _ptr(idx), _ptr(sim),
+                                          ctypes.byref(total), _ptr(work)))
+        if total.value <= cap:
+            break
+        cap = total.value
+    assert total.value <= cap                     # (the second call had room for the exact total)
+    n = total.value
+    out = (row_ptr, idx[:n].copy(), sim[:n].copy())
+    return out + (dict(zip(PAIR_KEYS_COUNTERS, work.tolist())),) if counters else out
+
+
+def pairs_components_keys(ctx, dev, pairs, scorer, min_similarity, counters=False):
+    """K17: pairs_components with the self-join DevicePairs `pairs` in place of the table -- (label int32[n], pairs, components).
+    counters=True appends a dict of PAIR_KEYS_COUNTERS."""
+    t = check_min_similarity(min_similarity)
+    sid = PAIR_JOIN_SCORERS[scorer] if isinstance(scorer, str) else int(scorer)
+    work = np.zeros(4, np.int64) if counters else None
+    label = np.empty(dev.n, np.int32)
+    n_pairs, components = c_i64(0), c_i64(0)
+    check(ctx.lib.pfz_pairs_components_keys(ctx.h, dev.h, pairs.h, sid, t, _ptr(label), ctypes.byref(n_pairs), ctypes.byref(components),
+                                            _ptr(work)))
+    out = (label, n_pairs.value, components.value)
+    return out + (dict(zip(PAIR_KEYS_COUNTERS, work.tolist())),) if counters else out
 
 
 # ---- exact rescoring of a 16-bit / int8 top-n (k5_rescore_topn) ------------------------------------------------------

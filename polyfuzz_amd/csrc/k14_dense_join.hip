@@ -202,15 +202,27 @@ int join_sort_unpack(pfz_ctx *ctx, const char *scope, const uint64_t *d_keys, co
         PFZ_TRY(d_skeys.alloc(ctx, cap * sizeof(uint64_t)));
         PFZ_TRY(d_svals.alloc(ctx, cap * sizeof(uint32_t)));
         PFZ_TRY(sort_pairs_u64(ctx, d_keys, d_vals, d_skeys.as<uint64_t>(), d_svals.as<uint32_t>(), total));
-        PFZ_TRY(d_ptr.alloc(ctx, (size_t)(n_from + 1) * sizeof(int64_t)));
-        PFZ_TRY(d_idx.alloc(ctx, (size_t)total * sizeof(int32_t)));
-        hipLaunchKernelGGL(k14_unpack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, d_skeys.as<uint64_t>(), total,
-                           n_from, d_ptr.as<int64_t>(), d_idx.as<int32_t>());
-        PFZ_HIP(hipGetLastError());
+        PFZ_TRY(join_unpack(ctx, d_skeys.as<uint64_t>(), total, n_from, &d_ptr, &d_idx));
     }
+    return join_download(ctx, d_ptr, d_idx, d_svals.as<uint32_t>(), total, n_from, out_row_ptr, out_idx, out_sim);
+}
+
+int join_unpack(pfz_ctx *ctx, const uint64_t *d_skeys, int64_t total, int64_t n_from, DevBuf *d_ptr, DevBuf *d_idx)
+{
+    PFZ_TRY(d_ptr->alloc(ctx, (size_t)(n_from + 1) * sizeof(int64_t)));
+    PFZ_TRY(d_idx->alloc(ctx, (size_t)total * sizeof(int32_t)));
+    hipLaunchKernelGGL(k14_unpack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, d_skeys, total, n_from,
+                       d_ptr->as<int64_t>(), d_idx->as<int32_t>());
+    PFZ_HIP(hipGetLastError());
+    return PFZ_OK;
+}
+
+int join_download(pfz_ctx *ctx, const DevBuf &d_ptr, const DevBuf &d_idx, const uint32_t *d_svals, int64_t total, int64_t n_from,
+                  int64_t *out_row_ptr, int32_t *out_idx, float *out_sim)
+{
     PFZ_TRY(copy_d2h(ctx, out_row_ptr, d_ptr.p, (size_t)(n_from + 1) * sizeof(int64_t)));
     PFZ_TRY(copy_d2h(ctx, out_idx, d_idx.p, (size_t)total * sizeof(int32_t)));
-    PFZ_TRY(copy_d2h(ctx, out_sim, d_svals.p, (size_t)total * sizeof(float)));
+    PFZ_TRY(copy_d2h(ctx, out_sim, d_svals, (size_t)total * sizeof(float)));
     PFZ_HIP(hipStreamSynchronize(ctx->stream));
     return PFZ_OK;
 }

@@ -25,12 +25,16 @@
 //   * counters, kept in wave-uniform registers and added once per from-row: (row, block) visits that had postings, those of
 //     them the bound skipped, sweep steps that contained a hit.  The adds of the rows go round 256 lines of counters that the
 //     host sums: every row adding to the same word cost more than the counters are worth.
+//   * pfz_cossim_join_dev leaves the join on the device: the same launch (k15_launch<false>, called) and sort_pairs_u64, the sorted
+//     keys and scores owned by a pfz_pairs handle that K16's key entries walk (k16_pairs_join.hip, K17); the capacity is handled
+//     inside -- a first launch with room for the caller's hint, one repeat with the exact total when that was too little.
 // LDS: 4 C + 256 bytes (the accumulators and the scatter's 64 markers), below the 4 C + 768 of k3_cossim_topn_kernel<C, 96>, so
 // the 18 workgroups per CU at C = 2048 are kept.  Large to-sides run this form too: there is no lock-step variant.
 #include "k3_core.h"
 #include "k12_core.h"
 #include "k15_core.h"
 
+#include <algorithm>
 #include <cmath>
 
 namespace pfz {
@@ -307,6 +311,76 @@ static int sparse_join_run(pfz_ctx *ctx, const pfz_index *ix, const pfz_csr *A, 
                             out_sim);
 }
 
+// The hits a first launch of pfz_cossim_join_dev has room for when its caller gives no hint: pfz_cossim_join's callers' guess
+constexpr int64_t kJoinDevDefaultRoom = 4096, kJoinDevDefaultPerRow = 4;
+
+static void pairs_handle_free(pfz_pairs *h)
+{
+    if (!h) return;
+    if (h->keys) pool_free(h->keys);
+    if (h->vals) pool_free(h->vals);
+    delete h;
+}
+
+// The join with its result left in HBM: the walk (at most twice: the capacity is handled here) and the sort; nothing is unpacked,
+// nothing but the state words comes to the host.
+static int sparse_join_dev_run(pfz_ctx *ctx, const pfz_index *ix, const pfz_csr *A, bool self, double t, int64_t hint, pfz_pairs **out,
+                               int64_t *out_counters)
+{
+    PFZ_HIP(hipSetDevice(ctx->device));
+    if (out_counters) out_counters[0] = out_counters[1] = out_counters[2] = 0;
+    Owner<pfz_pairs, pairs_handle_free> h(new pfz_pairs);
+    h->ctx = ctx;
+    h->n_from = A->n_rows;
+    h->n_to = ix->n_rows;
+    h->self = self;
+    SparseJoinArgs P;
+    if (h->n_from == 0 || h->n_to == 0 || !k15_args(ix, A, self, t, &P)) {
+        *out = h.release();
+        return PFZ_OK;
+    }
+    DevBuf d_keys, d_vals, d_state;
+    PFZ_TRY(d_state.alloc(ctx, kStateWords * sizeof(unsigned long long)));
+    P.state = d_state.as<unsigned long long>();
+    std::vector<unsigned long long> state(kStateWords);
+    int64_t room = hint > 0 ? hint : std::max(kJoinDevDefaultRoom, kJoinDevDefaultPerRow * h->n_from), total = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        PFZ_TRY(d_keys.alloc(ctx, (size_t)room * sizeof(uint64_t)));
+        PFZ_TRY(d_vals.alloc(ctx, (size_t)room * sizeof(float)));
+        PFZ_HIP(hipMemsetAsync(d_state.p, 0, kStateWords * sizeof(unsigned long long), ctx->stream));
+        P.keys = d_keys.as<uint64_t>();
+        P.vals = d_vals.as<float>();
+        P.capacity = (unsigned long long)room;
+        {
+            ProfScope ps(ctx, "k15_join");
+            PFZ_TRY(k15_launch<false>(ctx, ix, P));
+            PFZ_TRY(copy_d2h(ctx, state.data(), d_state.p, kStateWords * sizeof(unsigned long long)));      // (waits for the kernel)
+        }
+        total = (int64_t)state[0];
+        if (total >= ((int64_t)1 << 31)) {
+            set_error("pfz_cossim_join_dev: %lld pairs are more than the limit of 2^31 - 1 (the scan of the kernels that walk them is 32-bit)",
+                      (long long)total);
+            return PFZ_ERR_UNSUPPORTED;
+        }
+        if (total <= room) break;
+        room = total;      // the ONE repeat, with the exact total
+    }
+    k15_counters(state, out_counters);
+    if (total > 0) {
+        ProfScope ps(ctx, "k15_sort");
+        DevBuf d_skeys, d_svals;
+        const size_t cap = (size_t)sort_codes_capacity(total);
+        PFZ_TRY(d_skeys.alloc(ctx, cap * sizeof(uint64_t)));
+        PFZ_TRY(d_svals.alloc(ctx, cap * sizeof(uint32_t)));
+        PFZ_TRY(sort_pairs_u64(ctx, d_keys.as<uint64_t>(), d_vals.as<uint32_t>(), d_skeys.as<uint64_t>(), d_svals.as<uint32_t>(), total));
+        h->keys = (uint64_t *)d_skeys.release();
+        h->vals = (uint32_t *)d_svals.release();
+        h->count = total;
+    }
+    *out = h.release();
+    return PFZ_OK;
+}
+
 static int sparse_comp_run(pfz_ctx *ctx, const pfz_index *ix, const pfz_csr *A, double t, int32_t *out_label, int64_t *out_pairs,
                            int64_t *out_components, int64_t *out_counters)
 {
@@ -370,6 +444,48 @@ int pfz_cossim_join(pfz_ctx *ctx, const pfz_index *to_index, const pfz_csr *from
     PFZ_TRY(sparse_join_operands("pfz_cossim_join", to_index, from_matrix, min_similarity, self_join != 0));
     return sparse_join_run(ctx, to_index, from_matrix, self_join != 0, min_similarity, capacity, out_row_ptr, out_idx, out_sim, out_total,
                            out_counters);
+}
+
+int pfz_cossim_join_dev(pfz_ctx *ctx, const pfz_index *to_index, const pfz_csr *from_matrix, int32_t self_join, double min_similarity,
+                        int64_t capacity_hint, pfz_pairs **out, int64_t *out_counters)
+{
+    PFZ_REQUIRE(ctx && to_index && from_matrix && out, "pfz_cossim_join_dev: NULL argument");
+    PFZ_REQUIRE(capacity_hint >= 0, "pfz_cossim_join_dev: capacity_hint %lld < 0", (long long)capacity_hint);
+    PFZ_TRY(sparse_join_operands("pfz_cossim_join_dev", to_index, from_matrix, min_similarity, self_join != 0));
+    return sparse_join_dev_run(ctx, to_index, from_matrix, self_join != 0, min_similarity, capacity_hint, out, out_counters);
+}
+
+void pfz_pairs_free(pfz_pairs *pairs) { pairs_handle_free(pairs); }
+
+int pfz_pairs_count(const pfz_pairs *pairs, int64_t *out_count)
+{
+    PFZ_REQUIRE(pairs && out_count, "pfz_pairs_count: NULL argument");
+    *out_count = pairs->count;
+    return PFZ_OK;
+}
+
+int pfz_pairs_shape(const pfz_pairs *pairs, int64_t *out_n_from, int64_t *out_n_to, int32_t *out_self_join)
+{
+    PFZ_REQUIRE(pairs, "pfz_pairs_shape: NULL argument");
+    if (out_n_from) *out_n_from = pairs->n_from;
+    if (out_n_to) *out_n_to = pairs->n_to;
+    if (out_self_join) *out_self_join = pairs->self ? 1 : 0;
+    return PFZ_OK;
+}
+
+int pfz_pairs_download(pfz_ctx *ctx, const pfz_pairs *pairs, int64_t *out_row_ptr, int32_t *out_idx, float *out_sim)
+{
+    PFZ_REQUIRE(ctx && pairs && out_row_ptr, "pfz_pairs_download: NULL argument");
+    PFZ_REQUIRE(pairs->ctx == ctx, "pfz_pairs_download: the pair list belongs to another context");
+    PFZ_REQUIRE(pairs->count == 0 || (out_idx && out_sim), "pfz_pairs_download: NULL output for %lld pairs", (long long)pairs->count);
+    if (pairs->count == 0) {
+        for (int64_t r = 0; r <= pairs->n_from; ++r) out_row_ptr[r] = 0;
+        return PFZ_OK;
+    }
+    PFZ_HIP(hipSetDevice(ctx->device));
+    DevBuf d_ptr, d_idx;
+    PFZ_TRY(join_unpack(ctx, pairs->keys, pairs->count, pairs->n_from, &d_ptr, &d_idx));
+    return join_download(ctx, d_ptr, d_idx, pairs->vals, pairs->count, pairs->n_from, out_row_ptr, out_idx, out_sim);
 }
 
 int pfz_cossim_components(pfz_ctx *ctx, const pfz_index *index, const pfz_csr *matrix, double min_similarity, int32_t *out_label,

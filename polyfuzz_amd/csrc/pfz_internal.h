@@ -166,6 +166,16 @@ struct pfz_topn {
     float *val = nullptr;
 };
 
+// A threshold join's result left on the device (K15: pfz_cossim_join_dev): `count` distinct keys row << 32 | col, ascending, and the
+// float32 score beside each.  Both blocks hold sort_codes_capacity(count) entries (the sort's padding), NULL while count == 0.
+struct pfz_pairs {
+    pfz_ctx *ctx = nullptr;
+    int64_t n_from = 0, n_to = 0, count = 0;
+    bool self = false;           // one list: every unordered pair once, row < col
+    uint64_t *keys = nullptr;
+    uint32_t *vals = nullptr;    // float32 bits
+};
+
 struct pfz_strings {
     pfz_ctx *ctx = nullptr;
     int64_t n = 0, n_units = 0;
@@ -364,5 +374,10 @@ int k12_forest_flatten(pfz_ctx *ctx, const int32_t *parent, int32_t n, int32_t *
 // the profiling scope of the sort and the unpack.  Blocks (k14_dense_join.hip).
 int join_sort_unpack(pfz_ctx *ctx, const char *scope, const uint64_t *d_keys, const uint32_t *d_vals, int64_t total, int64_t n_from,
                      int64_t *out_row_ptr, int32_t *out_idx, float *out_sim);
+// its two halves behind the sort, for keys that are sorted already (a pfz_pairs handle, k15_sparse_join.hip): `total` >= 1 keys
+// unpacked into row pointers and to-indices in two fresh blocks (enqueued), and the three arrays downloaded (blocks)
+int join_unpack(pfz_ctx *ctx, const uint64_t *d_skeys, int64_t total, int64_t n_from, DevBuf *d_ptr, DevBuf *d_idx);
+int join_download(pfz_ctx *ctx, const DevBuf &d_ptr, const DevBuf &d_idx, const uint32_t *d_svals, int64_t total, int64_t n_from,
+                  int64_t *out_row_ptr, int32_t *out_idx, float *out_sim);
 
 }  // namespace pfz

@@ -145,7 +145,9 @@ def connected_components(strings: List[str], model,
     and are handed to its `components` -- equal strings must then have equal vectors.  Or a TFIDF model (K15, the sparse cosine
     `match` scores with; the list is fitted as `match(strings)` does).  Or a BlockedEditDistance with scorer "levenshtein", "osa",
     "jaro" or "jaro_winkler" (K16): the components of the pairs among its symmetrised TF-IDF candidates that reach min_similarity --
-    equal strings share one whenever the blocking stage lists one for the other."""
+    equal strings share one whenever the blocking stage lists one for the other.  A BlockedEditDistance with blocking_similarity
+    set (K17) takes the pairs of the TF-IDF threshold join at that cosine for its candidates instead: equal strings that have an
+    n-gram then share a component however many copies the list holds."""
     strings = list(strings)
     extra = {} if embeddings is None else {"embeddings": embeddings}
     return dicts_from_labels(strings, model.components(strings, min_similarity, **extra))

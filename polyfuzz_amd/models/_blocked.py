@@ -5,7 +5,9 @@ quadratic.  Record linkage at scale is done in two stages: a cheap, high-recall 
 character n-gram TF-IDF matcher's top `candidates` per from-string (polyfuzz/models/_utils.py:82-91), left in HBM by
 TFIDF.match_device -- and an exact string scorer on those few pairs only: K10 (csrc/k10_pairs.hip), which scores the candidate
 table under ratio / Levenshtein / OSA / Jaro / Jaro-Winkler and re-ranks every row.  K16 (csrc/k16_pairs_join.hip) holds the same
-table against a threshold instead: the candidate pairs at or above a similarity, or their connected components.
+table against a threshold instead: the candidate pairs at or above a similarity, or their connected components.  With
+`blocking_similarity` the threshold forms block by a TF-IDF THRESHOLD join instead of the table (K17): the pairs TFIDF.join reports,
+left in HBM by TFIDF.join_device and walked there.
 """
 import time
 from typing import Callable, List, Tuple, Union
@@ -43,6 +45,12 @@ class BlockedEditDistance(BaseMatcher):
         normalize: min-max normalise the similarity scores (reference _distance.py:83-86): ONE minimum and maximum over the
                 cells that hold a choice; empty cells stay 0.0
         model_id: The name of the particular instance, used when comparing models
+        blocking_similarity: None (the default): `join` and `components` score the top-`candidates` table.  A number b in [0, 1]:
+                they score exactly the pairs TFIDF(n_gram_range, clean_string, remove_space_ngrams).join(from_list, to_list, b)
+                reports (K15's rule: the float32 cosine as float64 >= b, never a pair without a common n-gram, a self-join's
+                unordered pairs once) -- a row has as many candidates as it has such partners, thousands if need be.
+                `candidates`, `top_n`, the constructor's min_similarity and `normalize` then play no part in these two calls, and
+                the limit of 1024 candidates does not apply; `match` is unchanged: it ranks, and needs the table
 
     The frame has EditDistance.top_n's layout: From, To, Similarity[, To_2, Similarity_2, ...], the scorer's own float64 value,
     unrounded (ratio on 0..100, the others on 0..1), in the order (score descending, to-list index ascending); a cell without a
@@ -62,10 +70,14 @@ class BlockedEditDistance(BaseMatcher):
     scored once with the lower position as the from-string --; a row's own index is never a candidate; `top_n` and `normalize`
     play no part; "ratio" (0..100) is refused: the scorers are "levenshtein", "osa", "jaro" and "jaro_winkler".
 
+    With blocking_similarity = b (K17) the two calls are exact among the pairs of the TF-IDF threshold join at b instead: every
+    such pair is scored once, in a self-join with the lower position as the from-string; frame, order and labels are the same.
+
     match(..., re_train=False) reuses the fitted TF-IDF side, and the resident raw to-list when the list it is handed equals the
     one uploaded last (EditDistance's rule).  There is no CPU fallback.  Pickling leaves the device handles behind.
     """
-    last_counts = None      # {"candidates", "scored", "pairs"[, "components"]} of the last `join` / `components` call
+    last_counts = None      # {"candidates", "scored", "pairs"[, "items"][, "components"]} of the last `join` / `components` call
+    blocking_similarity = None      # (a matcher pickled before the attribute existed reads as None)
 
     def __init__(self,
                  scorer: Union[Callable, str, None] = "ratio",
@@ -76,7 +88,8 @@ class BlockedEditDistance(BaseMatcher):
                  clean_string: bool = True,
                  remove_space_ngrams: bool = True,
                  normalize: bool = True,
-                 model_id: str = None):
+                 model_id: str = None,
+                 blocking_similarity: float = None):
         super().__init__(model_id)
         self.type = "BlockedEditDistance"
         self._scorer_name = _device_scorer(scorer)
@@ -102,6 +115,12 @@ class BlockedEditDistance(BaseMatcher):
         self.clean_string = bool(clean_string)
         self.remove_space_ngrams = bool(remove_space_ngrams)
         self.normalize = normalize
+        if blocking_similarity is not None:
+            try:
+                blocking_similarity = _lib.check_min_similarity(blocking_similarity)
+            except ValueError:
+                raise ValueError(f"blocking_similarity must be None or a number in [0, 1], not {blocking_similarity!r}") from None
+        self.blocking_similarity = blocking_similarity
         self._tfidf = TFIDF(n_gram_range=self.n_gram_range, clean_string=self.clean_string, min_similarity=self.min_similarity,
                             top_n=self.candidates, remove_space_ngrams=self.remove_space_ngrams)
         self._to_dev = self._to_names = None     # device copy of the last raw to-list (+ the cached K4 plan K10 reads its alphabet from)
@@ -142,9 +161,10 @@ class BlockedEditDistance(BaseMatcher):
         idx, score = _lib.pairs_rescore_topn(ctx, f_dev, t_dev, cand, self._scorer_name, ntop)
         return idx, score, names, (t0, t1, time.perf_counter())
 
-    def _block(self, from_list, to_list, re_train):
+    def _block(self, from_list, to_list, re_train, threshold=None):
         """The blocking stage and the two raw lists on the device: (context, from-list, to-list -- the from-list's own handle in a
-        self-match --, the candidate table in HBM, the choices' list, start time, time when the table was final)"""
+        self-match --, the candidate table in HBM, the choices' list, start time, time when the table was final).  threshold: the
+        candidates are the pairs of the TF-IDF threshold join at that cosine (a _lib.DevicePairs) instead of the table"""
         self_match = to_list is None
         ctx = _lib.Context.default()
         from ._rapidfuzz import upload_for
@@ -156,7 +176,10 @@ class BlockedEditDistance(BaseMatcher):
         held = self._to_dev
         self._to_dev = self._to_names = None      # set again below, once this call's to-list is resident
         self._tfidf.top_n = self.candidates
-        cand = self._tfidf.match_device(from_list, to_list, re_train=re_train)      # enqueued: the table stays in HBM
+        if threshold is None:
+            cand = self._tfidf.match_device(from_list, to_list, re_train=re_train)      # enqueued: the table stays in HBM
+        else:
+            cand = self._tfidf.join_device(from_list, to_list, threshold, re_train=re_train)      # the sorted keys stay in HBM
         f_dev = upload_for(ctx, self._scorer_name, from_list)                      # (host work while the device blocks)
         if self_match:
             t_dev = f_dev
@@ -174,7 +197,7 @@ class BlockedEditDistance(BaseMatcher):
                 f"{self._scorer_name!r} lives on 0..100, where a min_similarity in [0, 1] is ambiguous, and has no threshold kernel")
         t = _lib.check_min_similarity(min_similarity)
         m = clip_top_n(self.candidates, to_list)                  # as _rescore clips it
-        if m > _lib.PAIR_MAX_CANDIDATES:
+        if self.blocking_similarity is None and m > _lib.PAIR_MAX_CANDIDATES:
             raise _lib.PfzUnsupported(-4, f"BlockedEditDistance.candidates = {m} exceeds the limit of {_lib.PAIR_MAX_CANDIDATES} per from-string")
         return t
 
@@ -201,11 +224,16 @@ class BlockedEditDistance(BaseMatcher):
 
         Scorers "levenshtein", "osa", "jaro" and "jaro_winkler" (NotImplementedError otherwise: "ratio" lives on 0..100);
         min_similarity: a number in [0, 1] (ValueError otherwise).  Sets last_timings = {"tfidf", "k16", "frame"} and last_counts =
-        {"candidates": table cells that are a candidate pair, "scored": distinct pairs scored, "pairs": hits}. """
+        {"candidates": table cells that are a candidate pair, "scored": distinct pairs scored, "pairs": hits}.
+
+        With blocking_similarity = b (K17) the candidates are the pairs of the TF-IDF threshold join at b (class docstring), walked
+        in HBM as (row, slice) work items; last_counts = {"candidates": the join's pairs, "scored" (== candidates), "pairs",
+        "items": work items}; last_timings["tfidf"] is K15 with its sort. """
         t = self._check_join("join", min_similarity, to_list)
-        ctx, f_dev, t_dev, cand, names, t0, t1 = self._block(from_list, to_list, re_train)
-        row_ptr, idx, sim, counts = _lib.pairs_join(ctx, f_dev, None if to_list is None else t_dev, cand, self._scorer_name, t,
-                                                    counters=True)
+        b = self.blocking_similarity
+        ctx, f_dev, t_dev, cand, names, t0, t1 = self._block(from_list, to_list, re_train, b)
+        join = _lib.pairs_join if b is None else _lib.pairs_join_keys
+        row_ptr, idx, sim, counts = join(ctx, f_dev, None if to_list is None else t_dev, cand, self._scorer_name, t, counters=True)
         t2 = time.perf_counter()
         frm = np.repeat(np.arange(len(from_list), dtype=np.int32), np.diff(row_ptr))
         matches = pd.DataFrame({"From": gather_column(from_list, frm), "To": gather_column(names, idx), "Similarity": sim}, copy=False)
@@ -225,10 +253,15 @@ class BlockedEditDistance(BaseMatcher):
         dicts single_linkage returns.
 
         `normalize` is NOT applied.  Scorers and min_similarity as for `join`.  Sets last_timings = {"tfidf", "k16", "frame"} and
-        last_counts = {"candidates", "scored", "pairs", "components"}. """
+        last_counts = {"candidates", "scored", "pairs", "components"}.
+
+        With blocking_similarity = b (K17) the edges are the hits among the pairs of the TF-IDF threshold join at b: equal strings
+        share a component however many copies there are, as long as they have an n-gram; last_counts gains "items". """
         t = self._check_join("components", min_similarity, None)
-        ctx, f_dev, _, cand, _, t0, t1 = self._block(from_list, None, True)
-        label, pairs, components, counts = _lib.pairs_components(ctx, f_dev, cand, self._scorer_name, t, counters=True)
+        b = self.blocking_similarity
+        ctx, f_dev, _, cand, _, t0, t1 = self._block(from_list, None, True, b)
+        comp = _lib.pairs_components if b is None else _lib.pairs_components_keys
+        label, pairs, components, counts = comp(ctx, f_dev, cand, self._scorer_name, t, counters=True)
         self.last_timings = {"tfidf": (t1 - t0) * 1e3, "k16": (time.perf_counter() - t1) * 1e3, "frame": 0.0}
         self.last_counts = dict(counts, components=components)
         return label

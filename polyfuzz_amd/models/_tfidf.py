@@ -308,6 +308,26 @@ class TFIDF(BaseMatcher):
         self.last_counts = counts
         return matches
 
+    def join_device(self, from_list: List[str], to_list: List[str] = None, min_similarity: float = 0.8, re_train: bool = True):
+        """The pairs of `join()` left on the device: a _lib.DevicePairs -- the sorted keys from-index << 32 | to-index with their
+        fp32 cosines -- for consumers that walk them there (BlockedEditDistance with blocking_similarity: K17).  The threshold
+        sibling of match_device.  Fitting, re_train and the empty-list behaviour are `join`'s; an empty from-list gives a list of
+        no pairs.  `.download()` gives the CSR of `join`."""
+        t = _lib.check_min_similarity(min_similarity)
+        ctx = _lib.Context.default()
+        self_join = not to_list
+        if len(from_list) == 0:
+            if self_join:
+                raise ValueError("empty vocabulary; perhaps the documents only contain stop words")
+            if re_train:
+                self._extract_tf_idf(to_list, None, True)
+            self._require_fitted()
+            from_dev = _lib.DeviceCSR.upload(ctx, np.zeros(1, np.int64), np.zeros(0, np.int32), np.zeros(0, np.float32),
+                                             self._dev_to.shape[1])
+        else:
+            from_dev, _ = self._extract_tf_idf(from_list, to_list, re_train)
+        return _lib.sparse_join_dev(ctx, self._dev_index, from_dev, t, self_join=self_join)
+
     def components(self, from_list: List[str], min_similarity: float = 0.8) -> np.ndarray:
         """ Near-duplicate clusters of `from_list` (K15): int32 labels, label[i] = the smallest position in i's connected
         component of the graph whose edges are the pairs `join(from_list, min_similarity=...)` reports -- "A ~ B and B ~ C put
