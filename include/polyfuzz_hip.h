@@ -60,6 +60,22 @@ int pfz_ctx_sync(pfz_ctx *ctx);
 int pfz_ctx_info(pfz_ctx *ctx, char *name256, int32_t *n_cu, int64_t *hbm_bytes);
 /* the context's caching allocator: bytes in blocks that handles and running calls hold, bytes it keeps for re-use */
 int pfz_pool_stats(pfz_ctx *ctx, int64_t *live_bytes, int64_t *cached_bytes);
+/* Diagnostic, in the spirit of pfz_prof_enable: what the allocator's blocks hold when they are handed out.  The contents of a block
+ * are UNSPECIFIED -- a fresh block is whatever the runtime gives (very often zero), a cached one holds what its last user left -- and
+ * every entry point must compute the same result whatever they are.  Mode 0 (the default) leaves the allocator as it is: it does
+ * not clear, and the only cost is one branch per allocation.  Modes 1 to 3 fill every block handed out from then on, fresh or
+ * cached, over its whole size class with one 64-bit little-endian word, and wait for the context's stream before returning (so work
+ * on the side streams sees the fill as well; slow, for tests):
+ *   1  ZERO   0x0000000000000000
+ *   2  ONE64  0x0000000000000001  every 8-, 16-, 32- or 64-bit integer view reads 0 or 1: an index, length, count or offset that
+ *                                 nobody wrote stays in range everywhere
+ *   3  ONE32  0x0000000100000001  every 32-bit word reads 1 (ONE64 leaves the odd ones at 0); a 64-bit view reads 2^32 + 1, so run
+ *                                 it only where ONE64 has shown no dependence
+ * A result that differs between two modes depends on memory nobody wrote.  BLIND SPOT: as floats all three patterns are zero or
+ * denormals of about 0 (1.4e-45, 4.9e-324), so a float accumulator that is not cleared is NOT detected; NaN and large patterns are
+ * left out on purpose -- a missed initialisation must show as a wrong answer, never as a wild address.  The context's scratch buffer
+ * and the pinned staging buffers are no pool blocks and are not filled.  Any other mode: PFZ_ERR_INVALID. */
+int pfz_pool_fill(pfz_ctx *ctx, int32_t mode);
 
 /* HIP-event timers on the context's stream (used by bench.py for the live
  * per-kernel timing the roofline is computed from).  slot in [0, 64). */

@@ -44,6 +44,7 @@ SIGNATURES = {
     "pfz_ctx_sync": (ctypes.c_int, [c_vp]),
     "pfz_ctx_info": (ctypes.c_int, [c_vp, ctypes.c_char_p, P(c_i32), P(c_i64)]),
     "pfz_pool_stats": (ctypes.c_int, [c_vp, P(c_i64), P(c_i64)]),
+    "pfz_pool_fill": (ctypes.c_int, [c_vp, c_i32]),
     "pfz_event_record": (ctypes.c_int, [c_vp, c_i32]),
     "pfz_event_elapsed_ms": (ctypes.c_int, [c_vp, c_i32, c_i32, P(c_f32)]),
     "pfz_prof_enable": (ctypes.c_int, [c_vp, c_i32]),
@@ -244,6 +245,16 @@ class Context:
         live, cached = c_i64(), c_i64()
         check(self.lib.pfz_pool_stats(self.h, ctypes.byref(live), ctypes.byref(cached)))
         return live.value, cached.value
+
+    # pfz_pool_fill's modes and the 64-bit little-endian word each writes over every block the allocator hands out
+    POOL_FILL_OFF, POOL_FILL_ZERO, POOL_FILL_ONE64, POOL_FILL_ONE32 = 0, 1, 2, 3
+    POOL_FILL_WORDS = {POOL_FILL_ZERO: 0x0000000000000000, POOL_FILL_ONE64: 0x0000000000000001,
+                       POOL_FILL_ONE32: 0x0000000100000001}
+
+    def pool_fill(self, mode):
+        """diagnostic: fill every device block handed out from now on with the mode's word (0: off, the allocator does not clear).
+        A result that differs between two modes read memory nobody wrote (pfz_pool_fill; float accumulators are its blind spot)"""
+        check(self.lib.pfz_pool_fill(self.h, int(mode)))
 
     # timers ---------------------------------------------------------------
     def event_record(self, slot):

@@ -1,6 +1,7 @@
 // Context, error reporting, timers, CSR / top-n containers and the shared
 // device scan of libpolyfuzz_hip.so.
 #include "pfz_internal.h"
+#include "pool_class.h"
 #include "topn_wave.h"
 
 #include <stdarg.h>
@@ -264,21 +265,26 @@ int copy_d2h(pfz_ctx *ctx, void *dst_host, const void *src_dev, size_t bytes)
 static std::mutex g_pool_mu;
 static std::unordered_map<void *, std::pair<pfz_ctx *, size_t>> g_pool_owner;  // live block -> (ctx, class size)
 
-static size_t size_class(size_t bytes)
+// the fill of pfz_pool_fill: 64-bit words over a whole size class (a multiple of 8 bytes, pool_class.h), ordinary vector stores
+static __global__ __launch_bounds__(256) void k_pool_fill(uint64_t *__restrict__ p, size_t n_words, uint64_t word)
 {
-    if (bytes < 512) return 512;
-    size_t p2 = 512;
-    while (p2 * 2 <= bytes) p2 *= 2;       // p2 <= bytes < 2*p2
-    for (int j = 0; j <= 4; ++j) {
-        const size_t c = p2 + (p2 / 4) * j;  // p2, 1.25, 1.5, 1.75, 2 x p2
-        if (c >= bytes) return c;
-    }
-    return p2 * 2;
+    const size_t step = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_words; i += step) p[i] = word;
 }
 
-int pool_alloc_raw(pfz_ctx *ctx, void **p, size_t bytes)
+static int pool_fill_block(pfz_ctx *ctx, void *p, size_t cls, int32_t mode)
 {
-    const size_t cls = size_class(bytes);
+    const size_t n_words = cls / 8;
+    const size_t want = (n_words + 255) / 256;
+    const unsigned grid = (unsigned)(want < 4096 ? want : 4096);
+    hipLaunchKernelGGL(k_pool_fill, dim3(grid), dim3(256), 0, ctx->stream, (uint64_t *)p, n_words, pool_fill_word(mode));
+    PFZ_HIP(hipGetLastError());
+    PFZ_HIP(hipStreamSynchronize(ctx->stream));   // a consumer on a side stream sees the fill too
+    return PFZ_OK;
+}
+
+static int pool_take(pfz_ctx *ctx, void **p, size_t cls)
+{
     std::lock_guard<std::mutex> lk(g_pool_mu);
     auto it = ctx->pool_free_lists.find(cls);
     if (it != ctx->pool_free_lists.end() && !it->second.empty()) {
@@ -304,6 +310,20 @@ int pool_alloc_raw(pfz_ctx *ctx, void **p, size_t bytes)
     g_pool_owner[*p] = {ctx, cls};
     ctx->pool_live_bytes += cls;
     return PFZ_OK;
+}
+
+// Contents of a block are unspecified: a cached block holds what its last user left, and mode 0 does not clear.
+int pool_alloc_raw(pfz_ctx *ctx, void **p, size_t bytes)
+{
+    const size_t cls = size_class(bytes);
+    PFZ_TRY(pool_take(ctx, p, cls));
+    if (ctx->pool_fill_mode == kPoolFillOff) return PFZ_OK;
+    const int rc = pool_fill_block(ctx, *p, cls, ctx->pool_fill_mode);   // (the pool lock is released: the fill waits for the stream)
+    if (rc != PFZ_OK) {
+        pool_free(*p);
+        *p = nullptr;
+    }
+    return rc;
 }
 
 void pool_free(void *p)
@@ -737,6 +757,14 @@ int pfz_pool_stats(pfz_ctx *ctx, int64_t *live_bytes, int64_t *cached_bytes)
     std::lock_guard<std::mutex> lk(g_pool_mu);
     if (live_bytes) *live_bytes = (int64_t)ctx->pool_live_bytes;
     if (cached_bytes) *cached_bytes = (int64_t)ctx->pool_cached_bytes;
+    return PFZ_OK;
+}
+
+int pfz_pool_fill(pfz_ctx *ctx, int32_t mode)
+{
+    PFZ_REQUIRE(ctx, "pfz_pool_fill: ctx is NULL");
+    PFZ_REQUIRE(pool_fill_mode_ok(mode), "pfz_pool_fill: mode %d is none of 0 (off), 1 (ZERO), 2 (ONE64), 3 (ONE32)", mode);
+    ctx->pool_fill_mode = mode;
     return PFZ_OK;
 }
 

@@ -120,6 +120,7 @@ struct pfz_ctx {
     // caching allocator state: size class -> free blocks
     std::map<size_t, std::vector<void *>> pool_free_lists;
     size_t pool_cached_bytes = 0, pool_live_bytes = 0;
+    int32_t pool_fill_mode = 0;           // pfz_pool_fill: 0 off, 1..3 every block handed out is filled (pool_class.h)
 };
 
 struct pfz_csr {
