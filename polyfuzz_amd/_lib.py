@@ -857,6 +857,37 @@ def lev_matrix(ctx, from_dev, to_dev, scorer, begin=0, end=None):
 LEV_JOIN_COUNTERS = ("pairs_in_window", "pairs_finished", "steps")
 
 
+def _join_call(n_from, capacity, dtypes, counter_names, counters, call):
+    """The capacity protocol of every threshold join: buffers for `capacity` hits (None: a modest guess, four per from-row),
+    call(cap, row_ptr, per-hit arrays, total, work) -> the ctypes call's status, ONE repeat with room for the exact total when it
+    exceeds cap.  Returns (row_ptr, copies of the per-hit arrays cut to the total, total, dict of the counters or None)."""
+    work = np.zeros(len(counter_names), np.int64) if counters else None
+    total = c_i64(0)
+    cap = max(4096, 4 * int(n_from)) if capacity is None else int(capacity)
+    for repeat in (False, True):
+        row_ptr = np.empty(n_from + 1, np.int64)
+        hits = [np.empty(cap, dt) for dt in dtypes]
+        check(call(cap, _ptr(row_ptr), [_ptr(a) for a in hits], ctypes.byref(total), _ptr(work)))
+        if total.value <= cap:
+            break
+        if repeat:                                # (the second call had room for the exact total)
+            raise AssertionError(f"the repeated call reports {total.value} hits, the first reported {cap}")
+        cap = total.value
+    n = total.value
+    return row_ptr, tuple(a[:n].copy() for a in hits), n, dict(zip(counter_names, work.tolist())) if counters else None
+
+
+def _components_call(n, counter_names, counters, call):
+    """A components entry: call(label, pairs, components, work) -> the ctypes call's status; (label int32[n], pairs, components),
+    and with counters the dict of them appended"""
+    work = np.zeros(len(counter_names), np.int64) if counters else None
+    label = np.empty(n, np.int32)
+    pairs, components = c_i64(0), c_i64(0)
+    check(call(_ptr(label), ctypes.byref(pairs), ctypes.byref(components), _ptr(work)))
+    out = (label, pairs.value, components.value)
+    return out + (dict(zip(counter_names, work.tolist())),) if counters else out
+
+
 def lev_join(ctx, from_dev, to_dev, scorer, min_similarity, capacity=None, counters=False):
     """K11: every pair with similarity >= min_similarity (float64 against float64, equal is a hit) as CSR over the from-rows --
     (row_ptr int64[n + 1], to-index int32[hits] ascending within a row, distance int32[hits], similarity float64[hits]).
@@ -864,22 +895,12 @@ def lev_join(ctx, from_dev, to_dev, scorer, min_similarity, capacity=None, count
     buffers have room for (None: a modest guess, four per from-string); when the exact total the call returns exceeds it the
     call is repeated ONCE with room for that total, never more often.  counters=True appends a dict of LEV_JOIN_COUNTERS (the
     last call's)."""
-    work = np.zeros(3, np.int64) if counters else None
-    total = c_i64(0)
     to_h = None if to_dev is None else to_dev.h
-    cap = max(4096, 4 * int(from_dev.n)) if capacity is None else int(capacity)
-    for _ in range(2):
-        row_ptr = np.empty(from_dev.n + 1, np.int64)
-        idx, dist, sim = np.empty(cap, np.int32), np.empty(cap, np.int32), np.empty(cap, np.float64)
-        check(ctx.lib.pfz_lev_join(ctx.h, from_dev.h, to_h, LEV_SCORERS[scorer], float(min_similarity), cap, _ptr(row_ptr), _ptr(idx),
-                                   _ptr(dist), _ptr(sim), ctypes.byref(total), _ptr(work)))
-        if total.value <= cap:
-            break
-        cap = total.value
-    assert total.value <= cap                     # (the second call had room for the exact total)
-    n = total.value
-    out = (row_ptr, idx[:n].copy(), dist[:n].copy(), sim[:n].copy())
-    return out + (dict(zip(LEV_JOIN_COUNTERS, work.tolist())),) if counters else out
+    row_ptr, hits, _, work = _join_call(
+        from_dev.n, capacity, (np.int32, np.int32, np.float64), LEV_JOIN_COUNTERS, counters,
+        lambda cap, ptr, hit, total, wk: ctx.lib.pfz_lev_join(ctx.h, from_dev.h, to_h, LEV_SCORERS[scorer], float(min_similarity), cap,
+                                                              ptr, *hit, total, wk))
+    return (row_ptr,) + hits + ((work,) if counters else ())
 
 
 def lev_components(ctx, dev, scorer, min_similarity, counters=False):
@@ -887,13 +908,8 @@ def lev_components(ctx, dev, scorer, min_similarity, counters=False):
     united on the device, never stored) -- (label int32[n], pairs, components): label[i] is the smallest position in i's
     component, pairs the number of hits (lev_join's total), components the number of components, singletons included.
     counters=True appends a dict of LEV_JOIN_COUNTERS (the walk is lev_join's: so are the values)."""
-    work = np.zeros(3, np.int64) if counters else None
-    label = np.empty(dev.n, np.int32)
-    pairs, components = c_i64(0), c_i64(0)
-    check(ctx.lib.pfz_lev_components(ctx.h, dev.h, LEV_SCORERS[scorer], float(min_similarity), _ptr(label), ctypes.byref(pairs),
-                                     ctypes.byref(components), _ptr(work)))
-    out = (label, pairs.value, components.value)
-    return out + (dict(zip(LEV_JOIN_COUNTERS, work.tolist())),) if counters else out
+    return _components_call(dev.n, LEV_JOIN_COUNTERS, counters, lambda label, pairs, components, wk: ctx.lib.pfz_lev_components(
+        ctx.h, dev.h, LEV_SCORERS[scorer], float(min_similarity), label, pairs, components, wk))
 
 
 # K13: rapidfuzz.distance.Indel.normalized_similarity (K4's metric on the 0..1 scale), the definition of include/polyfuzz_hip.h
@@ -928,34 +944,18 @@ def indel_join(ctx, from_dev, to_dev, min_similarity, capacity=None, counters=Fa
     similarity >= min_similarity as CSR over the from-rows -- (row_ptr int64[n + 1], to-index int32[hits] ascending within a
     row, Indel distance |a| + |b| - 2 lcs int32[hits], similarity float64[hits]).  to_dev None (or from_dev itself): the
     self-join, i < j.  capacity and the ONE repeat as in lev_join; counters=True appends a dict of LEV_JOIN_COUNTERS."""
-    work = np.zeros(3, np.int64) if counters else None
-    total = c_i64(0)
     to_h = None if to_dev is None else to_dev.h
-    cap = max(4096, 4 * int(from_dev.n)) if capacity is None else int(capacity)
-    for _ in range(2):
-        row_ptr = np.empty(from_dev.n + 1, np.int64)
-        idx, dist, sim = np.empty(cap, np.int32), np.empty(cap, np.int32), np.empty(cap, np.float64)
-        check(ctx.lib.pfz_indel_join(ctx.h, from_dev.h, to_h, float(min_similarity), cap, _ptr(row_ptr), _ptr(idx), _ptr(dist),
-                                     _ptr(sim), ctypes.byref(total), _ptr(work)))
-        if total.value <= cap:
-            break
-        cap = total.value
-    assert total.value <= cap                     # (the second call had room for the exact total)
-    n = total.value
-    out = (row_ptr, idx[:n].copy(), dist[:n].copy(), sim[:n].copy())
-    return out + (dict(zip(LEV_JOIN_COUNTERS, work.tolist())),) if counters else out
+    row_ptr, hits, _, work = _join_call(
+        from_dev.n, capacity, (np.int32, np.int32, np.float64), LEV_JOIN_COUNTERS, counters,
+        lambda cap, ptr, hit, total, wk: ctx.lib.pfz_indel_join(ctx.h, from_dev.h, to_h, float(min_similarity), cap, ptr, *hit, total, wk))
+    return (row_ptr,) + hits + ((work,) if counters else ())
 
 
 def indel_components(ctx, dev, min_similarity, counters=False):
     """K13: lev_components's twin under the Indel similarity -- (label int32[n], pairs, components), the pairs of indel_join's
     self-join united on the device, never stored.  counters=True appends a dict of LEV_JOIN_COUNTERS."""
-    work = np.zeros(3, np.int64) if counters else None
-    label = np.empty(dev.n, np.int32)
-    pairs, components = c_i64(0), c_i64(0)
-    check(ctx.lib.pfz_indel_components(ctx.h, dev.h, float(min_similarity), _ptr(label), ctypes.byref(pairs), ctypes.byref(components),
-                                       _ptr(work)))
-    out = (label, pairs.value, components.value)
-    return out + (dict(zip(LEV_JOIN_COUNTERS, work.tolist())),) if counters else out
+    return _components_call(dev.n, LEV_JOIN_COUNTERS, counters, lambda label, pairs, components, wk: ctx.lib.pfz_indel_components(
+        ctx.h, dev.h, float(min_similarity), label, pairs, components, wk))
 
 
 # scorer of K10 -> PFZ_PAIR_* (include/polyfuzz_hip.h)
@@ -992,22 +992,11 @@ def pairs_join(ctx, from_dev, to_dev, candidates, scorer, min_similarity, capaci
     a dict of PAIR_JOIN_COUNTERS (the last call's): table cells that are a candidate pair, distinct pairs scored, hits."""
     t = check_min_similarity(min_similarity)
     sid = PAIR_JOIN_SCORERS[scorer] if isinstance(scorer, str) else int(scorer)
-    work = np.zeros(3, np.int64) if counters else None
-    total = c_i64(0)
     to_h = None if to_dev is None else to_dev.h
-    cap = max(4096, 4 * int(from_dev.n)) if capacity is None else int(capacity)
-    for _ in range(2):
-        row_ptr = np.empty(from_dev.n + 1, np.int64)
-        idx, sim = np.empty(cap, np.int32), np.empty(cap, np.float64)
-        check(ctx.lib.pfz_pairs_join(ctx.h, from_dev.h, to_h, candidates.h, sid, t, cap, _ptr(row_ptr), _ptr(idx), _ptr(sim),
-                                     ctypes.byref(total), _ptr(work)))
-        if total.value <= cap:
-            break
-        cap = total.value
-    assert total.value <= cap                     # (the second call had room for the exact total)
-    n = total.value
-    out = (row_ptr, idx[:n].copy(), sim[:n].copy())
-    return out + (dict(zip(PAIR_JOIN_COUNTERS, work.tolist())),) if counters else out
+    row_ptr, hits, _, work = _join_call(
+        from_dev.n, capacity, (np.int32, np.float64), PAIR_JOIN_COUNTERS, counters,
+        lambda cap, ptr, hit, total, wk: ctx.lib.pfz_pairs_join(ctx.h, from_dev.h, to_h, candidates.h, sid, t, cap, ptr, *hit, total, wk))
+    return (row_ptr,) + hits + ((work,) if counters else ())
 
 
 def pairs_components(ctx, dev, candidates, scorer, min_similarity, counters=False):
@@ -1017,13 +1006,8 @@ def pairs_components(ctx, dev, candidates, scorer, min_similarity, counters=Fals
     appends a dict of PAIR_JOIN_COUNTERS."""
     t = check_min_similarity(min_similarity)
     sid = PAIR_JOIN_SCORERS[scorer] if isinstance(scorer, str) else int(scorer)
-    work = np.zeros(3, np.int64) if counters else None
-    label = np.empty(dev.n, np.int32)
-    pairs, components = c_i64(0), c_i64(0)
-    check(ctx.lib.pfz_pairs_components(ctx.h, dev.h, candidates.h, sid, t, _ptr(label), ctypes.byref(pairs), ctypes.byref(components),
-                                       _ptr(work)))
-    out = (label, pairs.value, components.value)
-    return out + (dict(zip(PAIR_JOIN_COUNTERS, work.tolist())),) if counters else out
+    return _components_call(dev.n, PAIR_JOIN_COUNTERS, counters, lambda label, pairs, components, wk: ctx.lib.pfz_pairs_components(
+        ctx.h, dev.h, candidates.h, sid, t, label, pairs, components, wk))
 
 
 # compute_dtype of the dense path -> PFZ_DENSE_* (include/polyfuzz_hip.h)
@@ -1273,24 +1257,11 @@ def dense_join(ctx, from_dev, to_dev, min_similarity, capacity=None, counters=Fa
     _dense_join_operand(from_dev, "the from-vectors")
     if to_dev is not None:
         _dense_join_operand(to_dev, "the to-vectors")
-    work = np.zeros(2, np.int64) if counters else None
-    total = c_i64(0)
     to_h = None if to_dev is None else to_dev.h
-    cap = max(4096, 4 * int(from_dev.n)) if capacity is None else int(capacity)
-    for _ in range(2):
-        row_ptr = np.empty(from_dev.n + 1, np.int64)
-        idx, sim = np.empty(cap, np.int32), np.empty(cap, np.float32)
-        check(ctx.lib.pfz_dense_join(ctx.h, from_dev.h, to_h, float(min_similarity), cap, _ptr(row_ptr), _ptr(idx), _ptr(sim),
-                                     ctypes.byref(total), _ptr(work)))
-        if total.value <= cap:
-            break
-        cap = total.value
-    assert total.value <= cap                     # (the second call had room for the exact total)
-    n = total.value
-    counts = {"pairs": n}
-    if counters:
-        counts.update(zip(DENSE_JOIN_COUNTERS, work.tolist()))
-    return row_ptr, idx[:n].copy(), sim[:n].copy(), counts
+    row_ptr, hits, n, work = _join_call(
+        from_dev.n, capacity, (np.int32, np.float32), DENSE_JOIN_COUNTERS, counters,
+        lambda cap, ptr, hit, total, wk: ctx.lib.pfz_dense_join(ctx.h, from_dev.h, to_h, float(min_similarity), cap, ptr, *hit, total, wk))
+    return (row_ptr,) + hits + ({"pairs": n, **(work or {})},)
 
 
 def dense_components(ctx, dev, min_similarity, counters=False):
@@ -1299,13 +1270,8 @@ def dense_components(ctx, dev, min_similarity, counters=False):
     component, pairs the number of hits (dense_join's total), components the number of components, singletons included.
     counters=True appends a dict of DENSE_JOIN_COUNTERS."""
     _dense_join_operand(dev, "the vectors")
-    work = np.zeros(2, np.int64) if counters else None
-    label = np.empty(dev.n, np.int32)
-    pairs, components = c_i64(0), c_i64(0)
-    check(ctx.lib.pfz_dense_components(ctx.h, dev.h, float(min_similarity), _ptr(label), ctypes.byref(pairs), ctypes.byref(components),
-                                       _ptr(work)))
-    out = (label, pairs.value, components.value)
-    return out + (dict(zip(DENSE_JOIN_COUNTERS, work.tolist())),) if counters else out
+    return _components_call(dev.n, DENSE_JOIN_COUNTERS, counters, lambda label, pairs, components, wk: ctx.lib.pfz_dense_components(
+        ctx.h, dev.h, float(min_similarity), label, pairs, components, wk))
 
 
 # ---- K15: the sparse-cosine threshold join and its components --------------------------------------------------------
@@ -1330,24 +1296,11 @@ def sparse_join(ctx, index, from_dev, min_similarity, self_join=False, capacity=
     returns exceeds it the call is repeated ONCE with room for that total, never more often.  counts: {"pairs": hits}, with
     counters=True also SPARSE_JOIN_COUNTERS (the last call's)."""
     t = check_min_similarity(min_similarity)
-    n = from_dev.n_rows
-    work = np.zeros(3, np.int64) if counters else None
-    total = c_i64(0)
-    cap = max(4096, 4 * int(n)) if capacity is None else int(capacity)
-    for _ in range(2):
-        row_ptr = np.empty(n + 1, np.int64)
-        idx, sim = np.empty(cap, np.int32), np.empty(cap, np.float32)
-        check(ctx.lib.pfz_cossim_join(ctx.h, index.h, from_dev.h, int(bool(self_join)), t, cap, _ptr(row_ptr), _ptr(idx), _ptr(sim),
-                                      ctypes.byref(total), _ptr(work)))
-        if total.value <= cap:
-            break
-        cap = total.value
-    assert total.value <= cap                     # (the second call had room for the exact total)
-    hits = total.value
-    counts = {"pairs": hits}
-    if counters:
-        counts.update(zip(SPARSE_JOIN_COUNTERS, work.tolist()))
-    return row_ptr, idx[:hits].copy(), sim[:hits].copy(), counts
+    row_ptr, hits, n, work = _join_call(
+        from_dev.n_rows, capacity, (np.int32, np.float32), SPARSE_JOIN_COUNTERS, counters,
+        lambda cap, ptr, hit, total, wk: ctx.lib.pfz_cossim_join(ctx.h, index.h, from_dev.h, int(bool(self_join)), t, cap, ptr, *hit, total,
+                                                                 wk))
+    return (row_ptr,) + hits + ({"pairs": n, **(work or {})},)
 
 
 def sparse_components(ctx, index, dev, min_similarity, counters=False):
@@ -1356,13 +1309,8 @@ def sparse_components(ctx, index, dev, min_similarity, counters=False):
     label[i] is the smallest position in i's component, pairs the number of hits (sparse_join's total), components the number
     of components, singletons included.  counters=True appends a dict of SPARSE_JOIN_COUNTERS."""
     t = check_min_similarity(min_similarity)
-    work = np.zeros(3, np.int64) if counters else None
-    label = np.empty(dev.n_rows, np.int32)
-    pairs, components = c_i64(0), c_i64(0)
-    check(ctx.lib.pfz_cossim_components(ctx.h, index.h, dev.h, t, _ptr(label), ctypes.byref(pairs), ctypes.byref(components),
-                                        _ptr(work)))
-    out = (label, pairs.value, components.value)
-    return out + (dict(zip(SPARSE_JOIN_COUNTERS, work.tolist())),) if counters else out
+    return _components_call(dev.n_rows, SPARSE_JOIN_COUNTERS, counters, lambda label, pairs, components, wk: ctx.lib.pfz_cossim_components(
+        ctx.h, index.h, dev.h, t, label, pairs, components, wk))
 
 
 # ---- K17: a sparse-cosine threshold join left on the device, and K16 over its keys -----------------------------------
@@ -1413,22 +1361,11 @@ def pairs_join_keys(ctx, from_dev, to_dev, pairs, scorer, min_similarity, capaci
     scored (== the keys), the hits, the (row, slice) work items of at most PAIR_SLICE partners the kernels were dealt."""
     t = check_min_similarity(min_similarity)
     sid = PAIR_JOIN_SCORERS[scorer] if isinstance(scorer, str) else int(scorer)
-    work = np.zeros(4, np.int64) if counters else None
-    total = c_i64(0)
     to_h = None if to_dev is None else to_dev.h
-    cap = max(4096, 4 * int(from_dev.n)) if capacity is None else int(capacity)
-    for _ in range(2):
-        row_ptr = np.empty(from_dev.n + 1, np.int64)
-        idx, sim = np.empty(cap, np.int32), np.empty(cap, np.float64)
-        check(ctx.lib.pfz_pairs_join_keys(ctx.h, from_dev.h, to_h, pairs.h, sid, t, cap, _ptr(row_ptr), _ptr(idx), _ptr(sim),
-                                          ctypes.byref(total), _ptr(work)))
-        if total.value <= cap:
-            break
-        cap = total.value
-    assert total.value <= cap                     # (the second call had room for the exact total)
-    n = total.value
-    out = (row_ptr, idx[:n].copy(), sim[:n].copy())
-    return out + (dict(zip(PAIR_KEYS_COUNTERS, work.tolist())),) if counters else out
+    row_ptr, hits, _, work = _join_call(
+        from_dev.n, capacity, (np.int32, np.float64), PAIR_KEYS_COUNTERS, counters,
+        lambda cap, ptr, hit, total, wk: ctx.lib.pfz_pairs_join_keys(ctx.h, from_dev.h, to_h, pairs.h, sid, t, cap, ptr, *hit, total, wk))
+    return (row_ptr,) + hits + ((work,) if counters else ())
 
 
 def pairs_components_keys(ctx, dev, pairs, scorer, min_similarity, counters=False):
@@ -1436,13 +1373,8 @@ def pairs_components_keys(ctx, dev, pairs, scorer, min_similarity, counters=Fals
     counters=True appends a dict of PAIR_KEYS_COUNTERS."""
     t = check_min_similarity(min_similarity)
     sid = PAIR_JOIN_SCORERS[scorer] if isinstance(scorer, str) else int(scorer)
-    work = np.zeros(4, np.int64) if counters else None
-    label = np.empty(dev.n, np.int32)
-    n_pairs, components = c_i64(0), c_i64(0)
-    check(ctx.lib.pfz_pairs_components_keys(ctx.h, dev.h, pairs.h, sid, t, _ptr(label), ctypes.byref(n_pairs), ctypes.byref(components),
-                                            _ptr(work)))
-    out = (label, n_pairs.value, components.value)
-    return out + (dict(zip(PAIR_KEYS_COUNTERS, work.tolist())),) if counters else out
+    return _components_call(dev.n, PAIR_KEYS_COUNTERS, counters, lambda label, pairs_out, components, wk: ctx.lib.pfz_pairs_components_keys(
+        ctx.h, dev.h, pairs.h, sid, t, label, pairs_out, components, wk))
 
 
 # ---- exact rescoring of a 16-bit / int8 top-n (k5_rescore_topn) ------------------------------------------------------

@@ -49,4 +49,16 @@ K9_HD int join_key_row(uint64_t key) { return (int)(key >> 40); }
 K9_HD int join_key_to(uint64_t key) { return (int)((key >> 16) & 0xffffffu); }
 K9_HD int join_key_dist(uint64_t key) { return (int)(key & 0xffffu); }
 
+// The row pointers over `total` (>= 1) hits sorted by row, position p's share: hit p belongs to `row`, hit p - 1 to `prev` (-1 for
+// p = 0), and every row that begins between the two begins at p -- row_ptr[r] = p for prev < r <= row; the last position also closes
+// the rows behind its own, up to row_ptr[n_rows] = total.  Over p = 0 .. total - 1 every row_ptr[0 .. n_rows] is written exactly
+// once.  PTR: int64_t (K11, K13, K14 / K15's unpack) or int32_t (K16's segments); `row` may be n_rows itself (K16's keys that are
+// no pair).
+template <typename PTR> K9_HD void rows_fill(int64_t prev, int64_t row, int64_t p, int64_t total, int64_t n_rows, PTR *row_ptr)
+{
+    for (int64_t r = prev + 1; r <= row; ++r) row_ptr[r] = (PTR)p;
+    if (p == total - 1)
+        for (int64_t r = row + 1; r <= n_rows; ++r) row_ptr[r] = (PTR)total;
+}
+
 }  // namespace pfz

@@ -16,9 +16,11 @@
 // loads: label[i] = root of i, and the roots counted.  The root of a component is its smallest position (k12_core.h), so the
 // labels do not depend on the order in which the hooks happened.
 // Hits are counted as K11 counts them (one ballot and one atomic add per wave and group), which holds `pairs` to K11's total.
-// The walk is the one K11 runs: argument block, window, ownership rule, counters and the general body are edit_walk.h's, with "no
-// second list" as a compile-time constant and CompHook as the hit sink; the register walk is k11_join_kernel's, written out here
-// with the same two choices (edit_walk.h says why it is not one body).
+// The walk is the one K11 runs: argument block, window, ownership rule, counters, the general body, the set-up kernel and the
+// launches over the row classes are edit_walk.h's, with "no second list" as a compile-time constant and ForestHook as the hit
+// sink; the register walk is k11_join_kernel's, written out here with the same two choices (edit_walk.h says why it is not one
+// body).  The forest of a components run -- this one's, K13's, K14's, K15's, K16's -- is pfz_internal.h's ForestRun, whose two
+// kernels are launched from here.
 #include "edit_walk.h"
 #include "k12_core.h"
 
@@ -27,22 +29,6 @@
 #include <limits.h>
 
 namespace pfz {
-
-struct CompArgs : WalkArgs {   // (n_to: the list's own length)
-    int32_t *parent;           // [n] the forest (k12_core.h)
-};
-
-// the walk's hit sink: the hits of one wave and group counted with one atomic, and each hit lane hooks its pair into the forest
-struct CompHook {
-    const CompArgs &A;
-    __device__ void operator()(bool hit, int row, int orig, int) const
-    {
-        const unsigned long long m = __ballot(hit);
-        if (m == 0) return;
-        if ((threadIdx.x & 63) == 0) atomicAdd(A.total, (unsigned long long)__popcll(m));
-        if (hit) uf_unite<UfDeviceOps>(A.parent, row, orig);
-    }
-};
 
 // WORD: uint32_t (from-strings of <= 32 characters) or uint64_t (<= 64), against to-strings of any length
 template <typename WORD, int IDB, bool OSA>
@@ -68,7 +54,7 @@ __global__ __launch_bounds__(256) void k12_walk_kernel(CompArgs A)
             const int slot = g * 64 + lane;
             const int orig = A.b_orig[slot];
             const int lb = A.b_len[slot];
-            const int km = A.kmax[max(la, lb)];
+            const int km = A.cut[max(la, lb)];
             bool alive = join_owned(true, row, la, orig, lb) && join_in_window(km, la, lb);
             if (!__any(alive)) continue;
             n_win += alive;
@@ -91,7 +77,7 @@ __global__ __launch_bounds__(256) void k12_walk_kernel(CompArgs A)
             n_fin += alive;
             n_steps += alive ? lb : 0;
             const int d = lev_distance(s.dist, la, lb);
-            CompHook{A}(alive && d <= km, row, orig, d);
+            A.sink(alive && d <= km, row, orig, d);
         }
         __syncthreads();                                  // every wave is done with the match table
         pm_reg_clear(pm, my_sym);
@@ -105,16 +91,7 @@ __global__ __launch_bounds__(256) void k12_walk_general_kernel(CompArgs A, int32
                                                                 uint64_t *__restrict__ vp_all, uint64_t *__restrict__ vn_all,
                                                                 uint64_t *__restrict__ d0_all)
 {
-    walk_general_body<IDB, OSA, false>(A, true, CompHook{A}, WA, pm_all, vp_all, vn_all, d0_all);
-}
-
-// before the walk: the cutoff of every M (K11's table: K9's formula evaluated around a guess, k11_core.h) and every position its
-// own root
-__global__ __launch_bounds__(256) void k12_begin(double t, int32_t n_kmax, int32_t *__restrict__ kmax, int32_t n, int32_t *__restrict__ parent)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n_kmax) kmax[i] = join_kmax(t, (int)i, (int)i);
-    if (i < n) parent[i] = (int32_t)i;
+    walk_general_body<IDB, OSA, false>(A, true, A.sink, WA, pm_all, vp_all, vn_all, d0_all);
 }
 
 // after the walk, behind the kernel boundary: label[i] = the root of i's tree, and the roots counted (one atomic per wave)
@@ -131,14 +108,14 @@ __global__ __launch_bounds__(256) void k12_flatten(const int32_t *__restrict__ p
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(n_roots, (unsigned long long)__popcll(m));
 }
 
-// the two ends of a forest for the other kernels that hook into one (K14, pfz_internal.h): every position its own root, on the
-// context's stream ...
-int k12_forest_begin(pfz_ctx *ctx, int32_t n, int32_t *parent)
+// K11's and K12's set-up launch (edit_walk.h): the cutoff table and, for n > 0, every position its own root
+int lev_walk_begin(pfz_ctx *ctx, double t, int32_t n_kmax, int32_t *kmax, int32_t n, int32_t *parent)
 {
-    hipLaunchKernelGGL(k12_begin, dim3((unsigned)(((int64_t)n + 255) / 256)), dim3(256), 0, ctx->stream, 0.0, 0, (int32_t *)nullptr, n, parent);
-    PFZ_HIP(hipGetLastError());
-    return PFZ_OK;
+    return walk_begin<KmaxByM>(ctx, t, n_kmax, kmax, n, parent);
 }
+
+// the two ends of a forest (pfz_internal.h ForestRun): every position its own root, on the context's stream ...
+int k12_forest_begin(pfz_ctx *ctx, int32_t n, int32_t *parent) { return lev_walk_begin(ctx, 0.0, 0, nullptr, n, parent); }
 
 // ... and, behind the kernels that hooked, the labels and the number of roots added to *n_roots
 int k12_forest_flatten(pfz_ctx *ctx, const int32_t *parent, int32_t n, int32_t *label, unsigned long long *n_roots)
@@ -151,91 +128,24 @@ int k12_forest_flatten(pfz_ctx *ctx, const int32_t *parent, int32_t n, int32_t *
 static int comp_run(pfz_ctx *ctx, const pfz_strings *F, int32_t scorer, double t, int32_t *out_label, int64_t *out_pairs,
                     int64_t *out_components, int64_t *out_counters)
 {
-    PFZ_HIP(hipSetDevice(ctx->device));
-    *out_pairs = *out_components = 0;
-    if (out_counters) out_counters[0] = out_counters[1] = out_counters[2] = 0;
-    const int64_t n = F->n;
-    if (n == 0) return PFZ_OK;
-    if (n > (int64_t)INT_MAX - 64 || F->max_len >= (int64_t)INT_MAX) {
-        set_error("pfz_lev_components: %lld strings, the longest of %lld characters: positions (padded to groups of 64) and lengths "
-                  "are 32-bit", (long long)n, (long long)F->max_len);
-        return PFZ_ERR_UNSUPPORTED;
-    }
-    const pfz_indel_plan *pl;
-    PFZ_TRY(indel_plan_get(ctx, F, &pl));
-
-    // K11's three classes: <= 32 characters in 32-bit words, 33 .. 64 in 64-bit words while the match table fits 60 KiB of LDS
-    // (K4's limit); everything else is the general kernel's
-    const RowClasses rc = classify_rows(F, 0, n, lds_table_fits(pl));
-    const std::vector<int32_t> (&rows_cls)[3] = rc.rows;
-
-    DevBuf d_rows[3], d_kmax, d_parent, d_label, d_state;
-    for (int c = 0; c < 3; ++c)
-        if (!rows_cls[c].empty()) PFZ_TRY(d_rows[c].upload(ctx, rows_cls[c]));
-    const int32_t n_kmax = (int32_t)F->max_len + 1;
-    PFZ_TRY(d_kmax.alloc(ctx, (size_t)n_kmax * sizeof(int32_t)));
-    PFZ_TRY(d_parent.alloc(ctx, (size_t)n * sizeof(int32_t)));
-    PFZ_TRY(d_label.alloc(ctx, (size_t)n * sizeof(int32_t)));
-    PFZ_TRY(d_state.alloc(ctx, 5 * sizeof(unsigned long long)));      // the hits, the three counters, the roots
-    PFZ_HIP(hipMemsetAsync(d_state.p, 0, 5 * sizeof(unsigned long long), ctx->stream));
-    const int64_t n_begin = std::max<int64_t>(n, n_kmax);
-    hipLaunchKernelGGL(k12_begin, dim3((unsigned)((n_begin + 255) / 256)), dim3(256), 0, ctx->stream, t, n_kmax, d_kmax.as<int32_t>(),
-                       (int32_t)n, d_parent.as<int32_t>());
-    PFZ_HIP(hipGetLastError());
-
-    CompArgs A;
-    static_cast<EditView &>(A) = edit_view(F, pl);
-    A.n_to = (int32_t)n;
-    A.kmax = d_kmax.as<int32_t>();
-    A.parent = d_parent.as<int32_t>();
-    A.total = d_state.as<unsigned long long>();
-    A.counters = out_counters ? d_state.as<unsigned long long>() + 1 : nullptr;
-
-    const int64_t max_grid = (int64_t)ctx->prop.multiProcessorCount * 8;
-    {
-        ProfScope ps_all(ctx, "k12_walk");
-        for (int c = 0; c < 2; ++c) {
-            if (rows_cls[c].empty()) continue;
-            A.rows = d_rows[c].as<int32_t>();
-            A.n_rows = (int32_t)rows_cls[c].size();
-            const dim3 grid((unsigned)std::min<int64_t>(A.n_rows, max_grid));
-            const size_t lds = (size_t)A.n_sym1 * (c == 1 ? sizeof(uint64_t) : sizeof(uint32_t));
-            dispatch_idb_osa(pl->idb, scorer != 0, [&](auto IDB, auto OSA) {
-                if (c == 0) hipLaunchKernelGGL((k12_walk_kernel<uint32_t, decltype(IDB)::value, decltype(OSA)::value>), grid, dim3(256), lds, ctx->stream, A);
-                else hipLaunchKernelGGL((k12_walk_kernel<uint64_t, decltype(IDB)::value, decltype(OSA)::value>), grid, dim3(256), lds, ctx->stream, A);
+    auto launch = [&](const pfz_indel_plan *pl, const RowClasses &rc, DevBuf (&d_rows)[3], CompArgs &A) {
+        return walk_launch(
+            ctx, rc, d_rows, A, {1, 1, 1}, "pfz_lev_components", "a string", "k12_walk_general",
+            [&](auto word, dim3 grid, size_t lds) {
+                dispatch_idb_osa(pl->idb, scorer != 0, [&](auto IDB, auto OSA) {
+                    hipLaunchKernelGGL((k12_walk_kernel<decltype(word), decltype(IDB)::value, decltype(OSA)::value>), grid, dim3(256), lds,
+                                       ctx->stream, A);
+                });
+            },
+            [&](dim3 grid, int32_t WA, GeneralBufs &gb) {
+                dispatch_idb_osa(pl->idb, scorer != 0, [&](auto IDB, auto OSA) {
+                    hipLaunchKernelGGL((k12_walk_general_kernel<decltype(IDB)::value, decltype(OSA)::value>), grid, dim3(256), 0, ctx->stream, A,
+                                       WA, gb.pm.as<uint64_t>(), gb.col[0].as<uint64_t>(), gb.col[1].as<uint64_t>(), gb.col[2].as<uint64_t>());
+                });
             });
-            PFZ_HIP(hipGetLastError());
-        }
-        if (!rows_cls[2].empty()) {
-            A.rows = d_rows[2].as<int32_t>();
-            A.n_rows = (int32_t)rows_cls[2].size();
-            const int32_t WA = (int32_t)((rc.longest + 63) / 64);
-            int64_t grid = std::min<int64_t>(A.n_rows, max_grid);
-            PFZ_TRY(general_grid(&grid, A.n_sym1, WA, "pfz_lev_components", "a string", rc.longest));
-            ProfScope ps(ctx, "k12_walk_general");
-            GeneralBufs gb;
-            PFZ_TRY(general_bufs_alloc(ctx, &gb, grid, A.n_sym1, WA, {WA, WA, WA}, 256));
-            dispatch_idb_osa(pl->idb, scorer != 0, [&](auto IDB, auto OSA) {
-                hipLaunchKernelGGL((k12_walk_general_kernel<decltype(IDB)::value, decltype(OSA)::value>), dim3((unsigned)grid), dim3(256), 0,
-                                   ctx->stream, A, WA, gb.pm.as<uint64_t>(), gb.col[0].as<uint64_t>(), gb.col[1].as<uint64_t>(),
-                                   gb.col[2].as<uint64_t>());
-            });
-            PFZ_HIP(hipGetLastError());
-        }
-    }
-    {
-        ProfScope ps(ctx, "k12_flatten");
-        PFZ_TRY(k12_forest_flatten(ctx, d_parent.as<int32_t>(), (int32_t)n, d_label.as<int32_t>(), d_state.as<unsigned long long>() + 4));
-    }
-    unsigned long long state[5];
-    PFZ_TRY(copy_d2h(ctx, state, d_state.p, sizeof(state)));
-    PFZ_TRY(copy_d2h(ctx, out_label, d_label.p, (size_t)n * sizeof(int32_t)));
-    PFZ_HIP(hipStreamSynchronize(ctx->stream));
-    *out_pairs = (int64_t)state[0];
-    *out_components = (int64_t)state[4];
-    if (out_counters)
-        for (int k = 0; k < 3; ++k) out_counters[k] = (int64_t)state[k + 1];
-    return PFZ_OK;
+    };
+    return edit_comp_run(ctx, {"pfz_lev_components", "lengths", "k12_walk", "k12_flatten"}, F, t, F->max_len + 1, lev_walk_begin, launch,
+                         out_label, out_pairs, out_components, out_counters);
 }
 
 }  // namespace pfz

@@ -28,6 +28,7 @@
 // g = bj (bj + 1) / 2 + bi and decoded in the kernel; of a diagonal block's 64 workgroups the 28 below the diagonal leave at once,
 // as do those of tiles beyond the edge.  A deal of 2^24 workgroups or more goes out as several launches (k14_launch).
 #include "k5_core.h"
+#include "k11_core.h"
 #include "k12_core.h"
 
 #include <algorithm>
@@ -116,7 +117,7 @@ __device__ __forceinline__ void k14_body(const DenseJoinArgs &P)
         sb[j] = col_ok[j] ? P.inv_b[cbase + 32 * j] : 0.f;
     }
     // The corner in two halves of 32 rows (the accumulator pairs i = 0, 1): the half's 32 scores of the lane, its hits as a mask
-    // (bit 16 j + r), and -- only where some lane of the wave has one -- ONE atomic for all of them (K11's JoinAppend, with a
+    // (bit 16 j + r), and -- only where some lane of the wave has one -- ONE atomic for all of them (K11's KeyAppend, with a
     // prefix sum in place of the ballot's popcount: a lane may hold several).
     bool corner_hit = false;
 #pragma unroll
@@ -170,19 +171,15 @@ __global__ __launch_bounds__(256, 2) void k14_join_kernel(DenseJoinArgs P) { k14
 // (a self-join always: the components of ONE list)
 __global__ __launch_bounds__(256, 2) void k14_comp_kernel(DenseJoinArgs P) { k14_body<true>(P); }
 
-// the sorted keys -> CSR: hit p of the row-major order, and the row pointers of every row that begins between hit p - 1 and hit p
-// (K11's unpack; the scores are already in place beside the keys)
+// the sorted keys -> CSR: hit p of the row-major order and its share of the row pointers (k11_core.h rows_fill; the scores are
+// already in place beside the keys)
 __global__ __launch_bounds__(256) void k14_unpack(const uint64_t *__restrict__ keys, int64_t total, int64_t n_from,
                                                    int64_t *__restrict__ row_ptr, int32_t *__restrict__ out_idx)
 {
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= total) return;
-    const int64_t row = (int64_t)(keys[p] >> 32);
     out_idx[p] = (int32_t)(uint32_t)keys[p];
-    const int64_t prev = p > 0 ? (int64_t)(keys[p - 1] >> 32) : -1;
-    for (int64_t r = prev + 1; r <= row; ++r) row_ptr[r] = p;
-    if (p == total - 1)
-        for (int64_t r = row + 1; r <= n_from; ++r) row_ptr[r] = total;
+    rows_fill(p > 0 ? (int64_t)(keys[p - 1] >> 32) : -1, (int64_t)(keys[p] >> 32), p, total, n_from, row_ptr);
 }
 
 // The tail of a threshold join (K14 here, K15 in k15_sparse_join.hip): the `total` appended hits -- distinct keys row << 32 | col,
@@ -347,23 +344,22 @@ static int dense_comp_run(pfz_ctx *ctx, const pfz_dense *V, double t, int32_t *o
     int64_t grid;
     PFZ_TRY(dense_join_grid("pfz_dense_components", &P, &grid));
 
-    DevBuf d_parent, d_label, d_state;
-    PFZ_TRY(d_parent.alloc(ctx, (size_t)n * sizeof(int32_t)));
-    PFZ_TRY(d_label.alloc(ctx, (size_t)n * sizeof(int32_t)));
+    ForestRun forest;
+    DevBuf d_state;
+    PFZ_TRY(forest.alloc(ctx, n));
     PFZ_TRY(d_state.alloc(ctx, 4 * sizeof(unsigned long long)));      // the hits, the two counters, the roots
     PFZ_HIP(hipMemsetAsync(d_state.p, 0, 4 * sizeof(unsigned long long), ctx->stream));
-    P.parent = d_parent.as<int32_t>();
+    P.parent = forest.parent.as<int32_t>();
     P.state = d_state.as<unsigned long long>();
     {
         ProfScope ps(ctx, "k14_components");
-        PFZ_TRY(k12_forest_begin(ctx, (int32_t)n, P.parent));
+        PFZ_TRY(forest.begin(ctx));
         PFZ_TRY(k14_launch(ctx, k14_comp_kernel, P, grid));
-        PFZ_TRY(k12_forest_flatten(ctx, P.parent, (int32_t)n, d_label.as<int32_t>(), P.state + 3));
+        PFZ_TRY(forest.flatten(ctx, P.state + 3));
     }
     unsigned long long state[4];
     PFZ_TRY(copy_d2h(ctx, state, d_state.p, sizeof(state)));
-    PFZ_TRY(copy_d2h(ctx, out_label, d_label.p, (size_t)n * sizeof(int32_t)));
-    PFZ_HIP(hipStreamSynchronize(ctx->stream));
+    PFZ_TRY(forest.download(ctx, out_label));
     *out_pairs = (int64_t)state[0];
     *out_components = (int64_t)state[3];
     if (out_counters) {

@@ -391,23 +391,22 @@ static int sparse_comp_run(pfz_ctx *ctx, const pfz_index *ix, const pfz_csr *A, 
     if (n == 0) return PFZ_OK;
     SparseJoinArgs P;
     const bool any = k15_args(ix, A, true, t, &P);
-    DevBuf d_parent, d_label, d_state;
-    PFZ_TRY(d_parent.alloc(ctx, (size_t)n * sizeof(int32_t)));
-    PFZ_TRY(d_label.alloc(ctx, (size_t)n * sizeof(int32_t)));
+    ForestRun forest;
+    DevBuf d_state;
+    PFZ_TRY(forest.alloc(ctx, n));
     PFZ_TRY(d_state.alloc(ctx, kStateWords * sizeof(unsigned long long)));
     PFZ_HIP(hipMemsetAsync(d_state.p, 0, kStateWords * sizeof(unsigned long long), ctx->stream));
-    P.parent = d_parent.as<int32_t>();
+    P.parent = forest.parent.as<int32_t>();
     P.state = d_state.as<unsigned long long>();
     {
         ProfScope ps(ctx, "k15_components");
-        PFZ_TRY(k12_forest_begin(ctx, (int32_t)n, P.parent));
+        PFZ_TRY(forest.begin(ctx));
         if (any) PFZ_TRY(k15_launch<true>(ctx, ix, P));
-        PFZ_TRY(k12_forest_flatten(ctx, P.parent, (int32_t)n, d_label.as<int32_t>(), P.state + 1));
+        PFZ_TRY(forest.flatten(ctx, P.state + 1));
     }
     std::vector<unsigned long long> state(kStateWords);
     PFZ_TRY(copy_d2h(ctx, state.data(), d_state.p, kStateWords * sizeof(unsigned long long)));
-    PFZ_TRY(copy_d2h(ctx, out_label, d_label.p, (size_t)n * sizeof(int32_t)));
-    PFZ_HIP(hipStreamSynchronize(ctx->stream));
+    PFZ_TRY(forest.download(ctx, out_label));
     *out_pairs = (int64_t)state[0];
     *out_components = (int64_t)state[1];
     k15_counters(state, out_counters);

@@ -11,6 +11,8 @@
 // key differs from its predecessor" picks each distinct pair once, in (row, to-index) order: CSR order.
 #pragma once
 
+#include "k11_core.h"
+
 #include <stdint.h>
 
 #if defined(__HIPCC__)
@@ -38,16 +40,11 @@ K16_HD int64_t pair_key_row(uint64_t key, int64_t n_rows) { return key == kPairK
 // is sorted key p the first of its pair?  (the first key of a row has a predecessor of another row, or none)
 K16_HD bool pair_key_first(const uint64_t *keys, int64_t p) { return p == 0 || keys[p - 1] != keys[p]; }
 
-// Position p's share of the row pointers over n sorted keys (k11_unpack's scheme): seg[r] = the first position whose row is >= r,
-// for every row that begins between key p - 1 and key p; the last position also closes the rows behind its own.  Every seg[0 ..
-// n_rows] is written exactly once over p = 0 .. n - 1 (n >= 1); seg[n_rows] = the number of keys that are a pair.
+// Position p's share of the row pointers over n sorted keys (k11_core.h rows_fill): seg[r] = the first position whose row is >= r.
+// Every seg[0 .. n_rows] is written exactly once over p = 0 .. n - 1 (n >= 1); seg[n_rows] = the number of keys that are a pair.
 K16_HD void pair_rows_fill(const uint64_t *keys, int64_t p, int64_t n, int64_t n_rows, int32_t *seg)
 {
-    const int64_t row = pair_key_row(keys[p], n_rows);
-    const int64_t prev = p > 0 ? pair_key_row(keys[p - 1], n_rows) : -1;
-    for (int64_t r = prev + 1; r <= row; ++r) seg[r] = (int32_t)p;
-    if (p == n - 1)
-        for (int64_t r = row + 1; r <= n_rows; ++r) seg[r] = (int32_t)n;
+    rows_fill(p > 0 ? pair_key_row(keys[p - 1], n_rows) : -1, pair_key_row(keys[p], n_rows), p, n, n_rows, seg);
 }
 
 }  // namespace pfz

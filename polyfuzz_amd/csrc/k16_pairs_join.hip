@@ -10,7 +10,7 @@
 //           (outside [0, n_to), a row's own index) gets all ones.  A thread per cell, no atomics;
 //   sort    sort_codes_u64 (sort_u64.hip).  Equal keys -- a cell listed twice, the two directions of a self-join pair -- are now
 //           adjacent, the keys that are no pair stand at the end, and the rest is in (row, to-index) order; row pointers over the
-//           sorted keys by k11_unpack's scheme (k16_core.h pair_rows_fill);
+//           sorted keys by the joins' shared scheme (k16_core.h pair_rows_fill);
 //   score   K10's mapping: workgroup = ONE wave = one from-string at a time, its match table PM[symbol] in LDS, a lane per partner
 //           in chunks of 64 -- over the row's POINTER RANGE, not over the table's width: after the symmetrisation a string that many
 //           others list (a hub) has far more partners than the table has columns.  A lane whose key equals its predecessor's does
@@ -627,17 +627,15 @@ static int pairs_comp_run(pfz_ctx *ctx, const char *entry, const pfz_strings *F,
         return PFZ_OK;
     }
     PFZ_HIP(hipSetDevice(ctx->device));
-    DevBuf d_parent, d_label;
-    PFZ_TRY(d_parent.alloc(ctx, (size_t)n * sizeof(int32_t)));
-    PFZ_TRY(d_label.alloc(ctx, (size_t)n * sizeof(int32_t)));
-    PFZ_TRY(k12_forest_begin(ctx, (int32_t)n, d_parent.as<int32_t>()));
+    ForestRun forest;
+    PFZ_TRY(forest.alloc(ctx, n));
+    PFZ_TRY(forest.begin(ctx));
     PairWalk w;
-    PFZ_TRY(src.walk(ctx, entry, F, F, true, scorer, t, d_parent.as<int32_t>(), w));
-    PFZ_TRY(k12_forest_flatten(ctx, d_parent.as<int32_t>(), (int32_t)n, d_label.as<int32_t>(), w.state.as<unsigned long long>() + 2));
+    PFZ_TRY(src.walk(ctx, entry, F, F, true, scorer, t, forest.parent.as<int32_t>(), w));
+    PFZ_TRY(forest.flatten(ctx, w.state.as<unsigned long long>() + 2));
     unsigned long long state[3];
     PFZ_TRY(pairs_counters(ctx, w, n, state, out_counters));
-    PFZ_TRY(copy_d2h(ctx, out_label, d_label.p, (size_t)n * sizeof(int32_t)));
-    PFZ_HIP(hipStreamSynchronize(ctx->stream));
+    PFZ_TRY(forest.download(ctx, out_label));
     *out_pairs = (int64_t)state[1];
     *out_components = (int64_t)state[2];
     return PFZ_OK;

@@ -366,9 +366,32 @@ int sort_pairs_u64(pfz_ctx *ctx, const uint64_t *in, const uint32_t *vin, uint64
 
 // K12's forest for other kernels that hook pairs into one with uf_unite<UfDeviceOps> (k12_core.h): parent[i] = i for i < n, and,
 // behind the hooking kernels, label[i] = the smallest position of i's tree with the number of trees added to *n_roots (device).
-// Both enqueue on ctx->stream (k12_components.hip: k12_begin, k12_flatten).
+// Both enqueue on ctx->stream (k12_components.hip: edit_walk.h's set-up kernel, k12_flatten).
 int k12_forest_begin(pfz_ctx *ctx, int32_t n, int32_t *parent);
 int k12_forest_flatten(pfz_ctx *ctx, const int32_t *parent, int32_t n, int32_t *label, unsigned long long *n_roots);
+
+// The forest of one components run (K12 .. K16), between those two ends: it owns parent and label.  In the order of a run:
+// alloc; begin (K12 and K13 leave it out: their set-up launch, edit_walk.h walk_begin, roots the positions beside its cutoff
+// table); the caller's hooking kernels on parent; flatten, which adds the number of roots to the run's device word *n_roots; the
+// caller's own read-backs; download, which brings the labels and waits for the stream.
+struct ForestRun {
+    DevBuf parent, label;
+    int32_t n = 0;
+    int alloc(pfz_ctx *ctx, int64_t n_items)
+    {
+        n = (int32_t)n_items;
+        PFZ_TRY(parent.alloc(ctx, (size_t)n * sizeof(int32_t)));
+        return label.alloc(ctx, (size_t)n * sizeof(int32_t));
+    }
+    int begin(pfz_ctx *ctx) { return k12_forest_begin(ctx, n, parent.as<int32_t>()); }
+    int flatten(pfz_ctx *ctx, unsigned long long *n_roots) { return k12_forest_flatten(ctx, parent.as<int32_t>(), n, label.as<int32_t>(), n_roots); }
+    int download(pfz_ctx *ctx, int32_t *out_label)
+    {
+        PFZ_TRY(copy_d2h(ctx, out_label, label.p, (size_t)n * sizeof(int32_t)));
+        PFZ_HIP(hipStreamSynchronize(ctx->stream));
+        return PFZ_OK;
+    }
+};
 
 // The tail of the threshold joins that append (key = row << 32 | col, float32 score bits) pairs (K14, K15): `total` of them sorted,
 // unpacked into CSR over n_from rows and downloaded into the caller's host arrays; total == 0 zeroes the row pointers.  `scope` is

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../polyfuzz_amd/csrc/k11_core.h"
+#include "rows_fill_host.h"
 
 using namespace pfz;
 
@@ -183,6 +184,15 @@ extern "C" void k11_host_unpack(int32_t row, int32_t to, int32_t d, int32_t *out
     out[2] = join_key_dist(key);
 }
 
+// the row pointers of the unpacking (rows_fill_host.h), in both pointer widths; *cases: the sequences tried
+extern "C" int k11_host_rows_fill(int64_t *cases)
+{
+    long long n = 0;
+    const int bad = rows_fill_check<int64_t>(&n) + rows_fill_check<int32_t>(&n);
+    *cases = n;
+    return bad;
+}
+
 #ifdef K11_HOST_MAIN
 #include <cmath>
 #include <stdio.h>
@@ -204,6 +214,9 @@ int main()
                    (long long)rep[6]);
             bad |= rep[1] || rep[2] || rep[3] || rep[4] || rep[6] || rep[5] == 0;
         }
+    int64_t cases = 0;
+    bad |= k11_host_rows_fill(&cases) != 0;
+    printf("rows_fill: %lld sequences\n", (long long)cases);
     return bad;
 }
 #endif

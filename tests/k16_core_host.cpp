@@ -1,8 +1,10 @@
 // Host build of polyfuzz_amd/csrc/k16_core.h, run stand-alone by tests/test_pairs_join_cpu.py: K16's keys, the sentinel's place in
 // the sorted order, the rule that picks every distinct pair once and the row pointers, held to a model made of std::set on seeded
 // random tables -- two lists and self-join, with junk cells, own indices, duplicates, empty rows in front, in the middle and at the
-// end, and tables without a single pair.  Prints "k16_core_host ok <tables> <pairs>" and returns 0, or says what differs.
+// end, and tables without a single pair; then the row-pointer fill they share with the other joins, exhaustively on small inputs
+// (rows_fill_host.h).  Prints "k16_core_host ok <tables> <pairs> <row sequences>" and returns 0, or says what differs.
 #include "../polyfuzz_amd/csrc/k16_core.h"
+#include "rows_fill_host.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -102,6 +104,9 @@ int main()
         if (one_table(seed, n, m, n_to, self, fill, &pairs)) return 1;
         ++tables;
     }
-    std::printf("k16_core_host ok %d %lld\n", tables, pairs);
+    long long sequences = 0;
+    if (const int bad = rows_fill_check<int32_t>(&sequences) + rows_fill_check<int64_t>(&sequences))
+        return fail("row pointers of the small sequences against the counting loop", -1, bad, 0);
+    std::printf("k16_core_host ok %d %lld %lld\n", tables, pairs, sequences);
     return 0;
 }

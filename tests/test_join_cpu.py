@@ -6,6 +6,7 @@ EditDistance.join, the entry point in header / library / ctypes table, the kerne
 fixture (tests/golden/c3_lev_join_oracle.npz) against the oracle it was made from."""
 import ctypes
 import importlib.util
+import math
 import os
 import subprocess
 import sys
@@ -28,7 +29,8 @@ MAX_LEN = 6
 def host():
     so = os.path.join(REPO, "oracle", "_build", "k11_core_host.so")
     csrc = os.path.join(REPO, "polyfuzz_amd", "csrc")
-    src = [os.path.join(HERE, "k11_core_host.cpp"), os.path.join(csrc, "k11_core.h"), os.path.join(csrc, "k9_core.h")]
+    src = [os.path.join(HERE, "k11_core_host.cpp"), os.path.join(HERE, "rows_fill_host.h"), os.path.join(csrc, "k11_core.h"),
+           os.path.join(csrc, "k9_core.h")]
     os.makedirs(os.path.dirname(so), exist_ok=True)
     if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in src):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", src[0], "-o", so])
@@ -85,6 +87,15 @@ def test_kmax_is_the_formula_not_the_floor(host):
     assert host.k11_host_kmax(0.8, 5, 5) == 1 and int(np.floor((1.0 - 0.8) * 5)) == 0 and differs > 20
     assert host.k11_host_kmax(1.0, 0, 0) == 0 and host.k11_host_kmax(np.nextafter(1.0, 0.0), 7, 3) == 0
     assert host.k11_host_kmax(0.0, 9, 4) == 9
+
+
+def test_row_pointer_fill_exhaustively(host):
+    """rows_fill (k11_core.h), which every join's unpack and K16's segments share: for every ascending sequence of 1 .. 5 hit rows
+    over 0 .. 4 rows -- rows without a hit in front, in the middle and at the end, and K16's row behind the last -- and both
+    pointer widths, every row pointer is written exactly once and equals the hits counted in the rows before it"""
+    cases = ctypes.c_int64(0)
+    assert host.k11_host_rows_fill(ctypes.byref(cases)) == 0
+    assert cases.value == 2 * sum(math.comb(n_rows + total, total) for n_rows in range(5) for total in range(1, 6))
 
 
 def test_packed_hit_round_trip(host):
@@ -163,7 +174,7 @@ def test_kernel_budget():
     """the eight register-kernel instances (32- / 64-bit words x 8- / 16-bit symbols x Levenshtein / OSA) are held to K9's own
     limits: no scratch, static LDS no larger than K8's (the match table is dynamic), at most 64 registers -- eight waves per SIMD
     (measured: 39 .. 43 in 32-bit words, 45 .. 50 in 64-bit words; the threshold reaches them as a table of integer cutoffs, no
-    lane divides); the general kernel, the cutoff table and the unpacking are held to no scratch.  No kernel of K11 carries one
+    lane divides); the general kernel, the cutoff table and the unpacking (edit_walk.h's, K11's instances) are held to no scratch.  No kernel of K11 carries one
     of the names tests/test_levenshtein_cpu.py counts K9's kernels by."""
     sys.path.insert(0, os.path.join(REPO, "tools"))
     import kernel_budget
@@ -180,9 +191,10 @@ def test_kernel_budget():
     for name, k in hits.items():
         assert k["scratch"] == 0 and k["lds"] <= k8_lds and k["lds"] % 16 == 0, (name, k)
         assert k["vgpr"] <= (56 if "unsigned int" in name else 64), (name, k)
-    k11 = {pretty[k]: v for k, v in md.items() if "k11_" in pretty[k]}
+    k11 = {pretty[k]: v for k, v in md.items() if "k11_" in pretty[k] or "walk_begin_kernel<pfz::KmaxByM>" in pretty[k]
+           or "edit_unpack_kernel<pfz::LevScore>" in pretty[k]}
     assert len(k11) == 8 + 4 + 2 and sum("k11_join_general_kernel" in n for n in k11) == 4, sorted(k11)
-    assert any("k11_kmax_table" in n for n in k11) and any("k11_unpack" in n for n in k11)
+    assert any("walk_begin_kernel<pfz::KmaxByM>" in n for n in k11) and any("edit_unpack_kernel<pfz::LevScore>" in n for n in k11)
     for name, k in k11.items():
         assert k["scratch"] == 0, (name, k)
         assert "k9_lev_kernel" not in name and "k9_lev_general_kernel" not in name

@@ -5,6 +5,7 @@ packing, the sentinel's order, the unique rule, the row pointers -- compiled for
 (tests/k16_core_host.cpp) and run, once plain and once under the host's address and undefined-behaviour sanitizers."""
 import ctypes
 import inspect
+import math
 import os
 import subprocess
 
@@ -209,7 +210,9 @@ def test_the_definitions_are_symmetric_on_the_test_lists():
 
 def _host_program(tag, flags):
     exe = os.path.join(REPO, "oracle", "_build", f"k16_core_host_{tag}")
-    src = [os.path.join(HERE, "k16_core_host.cpp"), os.path.join(REPO, "polyfuzz_amd", "csrc", "k16_core.h")]
+    csrc = os.path.join(REPO, "polyfuzz_amd", "csrc")
+    src = [os.path.join(HERE, "k16_core_host.cpp"), os.path.join(HERE, "rows_fill_host.h")] + [os.path.join(csrc, h) for h in (
+        "k16_core.h", "k11_core.h", "k9_core.h")]
     os.makedirs(os.path.dirname(exe), exist_ok=True)
     if not os.path.exists(exe) or any(os.path.getmtime(s) > os.path.getmtime(exe) for s in src):
         subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror"] + flags + [src[0], "-o", exe])
@@ -221,6 +224,8 @@ def _run_host_program(exe):
     assert out.returncode == 0, out.stdout + out.stderr
     words = out.stdout.split()
     assert words[:2] == ["k16_core_host", "ok"] and int(words[2]) == 240 and int(words[3]) > 1000, out.stdout
+    # the shared row-pointer fill: every ascending sequence of 1 .. 5 rows over 0 .. 4 rows (and the row behind the last), both widths
+    assert int(words[4]) == 2 * sum(math.comb(n_rows + total, total) for n_rows in range(5) for total in range(1, 6)), out.stdout
 
 
 def test_keys_sentinel_unique_rule_and_row_pointers_on_the_host():
