@@ -357,6 +357,42 @@ int pfz_fuzz_extract_one_dev(pfz_ctx *ctx, const pfz_strings *from_strings, cons
 int pfz_fuzz_plan_info(pfz_ctx *ctx, const pfz_strings *to_strings, int64_t *n_symbols, int64_t *n_groups, int64_t *n_tokens,
                        int64_t *n_general_strings);
 
+/* ---- K18: all pairs at or above a score of the per-pair rapidfuzz scorers, and their components ----
+ * The threshold form of K7: where the reference's RapidFuzz matcher keeps process.extractOne's single best choice
+ * (_rapidfuzz.py:99-113), this is rapidfuzz.process.cdist(from, to, scorer=..., score_cutoff=c) /
+ * process.extract(..., limit=None, score_cutoff=c) -- every pair that reaches the cutoff.
+ * score(i, j) is exactly the float64 pfz_fuzz_extract_one computes for the pair (rapidfuzz's 0..100 scale), `scorer` as there
+ * (0 WRatio .. 6 partial_token_ratio).  A pair is a hit iff score >= score_cutoff, float64 against float64 (equal is a hit).
+ * pfz_fuzz_join: two lists -- every pair (from i, to j).  to_strings == NULL or the from-list's own handle is the self-join: every
+ * pair i < j once, as row i, to-index j, scored as scorer(strings[i], strings[j]); never (i, i); equal strings at other positions
+ * are pairs like any other (a string without a token scores 0 with its copy under WRatio and the token-set scorers, and is then
+ * no pair above a cutoff of 0).  Row i of a self-join scores the choices behind it: K7's "up to" skip code -2 - i
+ * (pfz_fuzz_extract_one), which the entry generates itself.
+ * The output is CSR over the from-rows in host buffers -- out_row_ptr int64[n_from + 1], and per hit out_idx (the to-index,
+ * ascending within a row) and out_score (the 0..100 float64); the same call gives the same bytes every time.  capacity: the
+ * hits the two arrays have room for (they may be NULL when it is 0); *out_total is always the exact number of hits; when it
+ * exceeds `capacity` the call returns PFZ_OK, has written NONE of the three output arrays (the device never writes a hit past the
+ * capacity either) and is to be repeated with capacity >= *out_total.  out_counters: NULL, or int64[3] -- [0] pairs whose upper
+ * bound was computed, [1] pairs scored exactly, [2] 64-bit word-steps of the scored pairs (K7's estimate from their lengths).
+ * Exact: a pair is left unscored only where K7's upper bound of its score, plus K7's slack, is below the cutoff
+ * (csrc/k18_core.h); the score of a pair that reaches the cutoff is exact (csrc/k7_core.h: fz_score with a fixed floor).
+ * From-strings beyond 256 characters or 32 distinct tokens (and to-strings beyond 32 distinct tokens) take a general -- slow --
+ * kernel.  The preparation is pfz_fuzz_extract_one's, cached on the handles.
+ * scorer outside 0..6, a NaN score_cutoff or one outside [0, 100], capacity < 0: PFZ_ERR_INVALID.  K7's list limits (2^31 - 65
+ * strings), and a capacity beyond 2^32 - 1: PFZ_ERR_UNSUPPORTED.  Blocks. */
+int pfz_fuzz_join(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings, int32_t scorer, double score_cutoff,
+                  int64_t capacity, int64_t *out_row_ptr, int32_t *out_idx, double *out_score, int64_t *out_total,
+                  int64_t *out_counters);
+/* The connected components of "score >= score_cutoff" over ONE list (reference _rapidfuzz.py:99-113 asks for the one best choice
+ * only; polyfuzz/linkage.py groups greedily over such a frame).  The pairs are those of pfz_fuzz_join(ctx, strings, NULL, scorer,
+ * score_cutoff, ...), found by the same kernels and united where they are found in the lock-free union-find of csrc/k12_core.h:
+ * O(n) device memory, no pair is stored.  out_label: host buffer int32[n], out_label[i] = the SMALLEST position in i's component;
+ * deterministic.  *out_pairs == pfz_fuzz_join's *out_total; *out_components counts singletons too; out_counters as above.
+ * strings->n == 0: PFZ_OK, *out_pairs = *out_components = 0, nothing else is written (out_label may be NULL).
+ * Errors as pfz_fuzz_join (there is no capacity).  Blocks. */
+int pfz_fuzz_components(pfz_ctx *ctx, const pfz_strings *strings, int32_t scorer, double score_cutoff, int32_t *out_label,
+                        int64_t *out_pairs, int64_t *out_components, int64_t *out_counters);
+
 /* ---- K8: all-pairs Jaro / Jaro-Winkler similarity + row arg-max --------------
  * Replaces the hot loop of EditDistance._calculate_edit_distance (reference
  * polyfuzz/models/_distance.py:89-102) with the `scorer` argument (_distance.py:32) set to

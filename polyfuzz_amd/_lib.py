@@ -117,6 +117,8 @@ SIGNATURES = {
     "pfz_fuzz_extract_one": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "pfz_fuzz_extract_one_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "pfz_fuzz_plan_info": (ctypes.c_int, [c_vp, c_vp, P(c_i64), P(c_i64), P(c_i64), P(c_i64)]),
+    "pfz_fuzz_join": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_f64, c_i64, c_vp, c_vp, c_vp, P(c_i64), c_vp]),
+    "pfz_fuzz_components": (ctypes.c_int, [c_vp, c_vp, c_i32, c_f64, c_vp, P(c_i64), P(c_i64), c_vp]),
     "pfz_dense_cossim_topn_host": (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_f32, c_i32,
                                                   c_vp, c_vp]),
     "pfz_dense_dot_topn_host": (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_f32, c_i32,
@@ -1272,6 +1274,35 @@ def dense_components(ctx, dev, min_similarity, counters=False):
     _dense_join_operand(dev, "the vectors")
     return _components_call(dev.n, DENSE_JOIN_COUNTERS, counters, lambda label, pairs, components, wk: ctx.lib.pfz_dense_components(
         ctx.h, dev.h, float(min_similarity), label, pairs, components, wk))
+
+
+# ---- K18: the threshold join of K7's scorers and its components ---------------------------------------------------------
+
+FUZZ_JOIN_COUNTERS = ("bounded", "scored", "steps")      # pfz_fuzz_join's out_counters, in order
+
+
+def fuzz_join(ctx, from_dev, to_dev, scorer, score_cutoff, capacity=None, counters=False):
+    """K18: every pair whose `scorer` score -- fuzz_extract_one's float64 on rapidfuzz's 0..100 scale, bit for bit -- is
+    >= score_cutoff (float64 against float64: equal is a hit), as CSR over the from-rows: (row_ptr int64[n + 1], to-index
+    int32[hits] ascending within a row, score float64[hits]).  scorer: a name of FUZZ_SCORERS.  to_dev None (or from_dev itself):
+    the self-join, every pair i < j once as row i, to-index j.  capacity: the hits the first call's buffers have room for (None:
+    a modest guess, four per from-string); when the exact total the call returns exceeds it the call is repeated ONCE with room
+    for that total, never more often.  counters=True appends a dict of FUZZ_JOIN_COUNTERS (the last call's)."""
+    to_h = None if to_dev is None else to_dev.h
+    row_ptr, hits, _, work = _join_call(
+        from_dev.n, capacity, (np.int32, np.float64), FUZZ_JOIN_COUNTERS, counters,
+        lambda cap, ptr, hit, total, wk: ctx.lib.pfz_fuzz_join(ctx.h, from_dev.h, to_h, FUZZ_SCORERS[scorer], float(score_cutoff), cap, ptr,
+                                                               *hit, total, wk))
+    return (row_ptr,) + hits + ((work,) if counters else ())
+
+
+def fuzz_components(ctx, dev, scorer, score_cutoff, counters=False):
+    """K18: the connected components of "score >= score_cutoff" over the list `dev` (the pairs of fuzz_join's self-join, united
+    on the device, never stored) -- (label int32[n], pairs, components): label[i] is the smallest position in i's component,
+    pairs the number of hits (fuzz_join's total), components the number of components, singletons included.  counters=True
+    appends a dict of FUZZ_JOIN_COUNTERS."""
+    return _components_call(dev.n, FUZZ_JOIN_COUNTERS, counters, lambda label, pairs, components, wk: ctx.lib.pfz_fuzz_components(
+        ctx.h, dev.h, FUZZ_SCORERS[scorer], float(score_cutoff), label, pairs, components, wk))
 
 
 # ---- K15: the sparse-cosine threshold join and its components --------------------------------------------------------

@@ -39,40 +39,13 @@
 // from-string) take k7_general_kernel: the same scorers with any number of words and tokens, all state in global
 // scratch -- slow, but the reference accepts such inputs.   PARITY UNPINNED (rapidfuzz is not installable): the oracle
 // is oracle/fuzz_scorers.{py,c}, anchored on rapidfuzz's published values.
-#include "pfz_internal.h"
+#include "k7_device.h"
 
 #include <algorithm>
 #include <climits>
 
-#undef PFZ_HD
-#define PFZ_HD __device__ inline
-#define PFZ_LDS_U16 __attribute__((address_space(3))) uint16_t
-#define PFZ_LDS_U8 __attribute__((address_space(3))) uint8_t
-#ifdef PFZ_K7_PROFILE
-#define FZ_TICK(T, k)                                                 \
-    do {                                                              \
-        const long long now_ = clock64();                             \
-        (T).tk[k] += (unsigned int)(now_ - (T).t0);                   \
-        (T).t0 = now_;                                                \
-    } while (0)
-#endif
-// (the builtin takes the condition as it is: __ballot() compares an integer copy of it with 0 -- a select and a compare more)
-#define FZ_BALLOT(x) __builtin_amdgcn_ballot_w64(x)
-#define FZ_ANY(x) (FZ_BALLOT(x) != 0ull)
-#include "k7_core.h"
-#include "k7_args.h"
-#include "k7_plan.h"
-
 namespace pfz {
 
-// One from-string per WAVE (a one-wave workgroup): what a from-string costs on top of its pairs -- the bounding sweeps, a
-// batch of seeds, a last partial batch -- is paid per wave that works on it, and four waves sharing one from-string paid
-// it four times over (the 100 000-name self-match: 0.79 -> 0.49 s).  More waves per workgroup = fewer from-strings in flight.
-constexpr int kK7Waves = 1, kK7Threads = 64 * kK7Waves;
-#ifndef PFZ_K7_OCC
-#define PFZ_K7_OCC 4          // one-word rows: waves per SIMD the compiler budgets registers for (tuning builds: 3 = no spills)
-#endif
-constexpr float kBoundSlack = 0.05f;
 // log2 of the windows per run of a window sweep: 16, more for long forms -- at most 8 runs (forms are <= 256 symbols here)
 #ifndef PFZ_K7_SHARE_LOG2
 #define PFZ_K7_SHARE_LOG2 6
@@ -111,37 +84,6 @@ __device__ inline void wave_best(RowBest &b)
         const int oi = __shfl_xor(b.idx, d, 64);
         b.take(os, oi);
     }
-}
-
-// how many of the lanes below this one are set in a wave mask (v_mbcnt: two instructions)
-__device__ inline int lanes_below(unsigned long long mask)
-{
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
-
-// v where any of m's four components equals id (a wave-uniform value, in a scalar register), else 0
-__device__ inline int select_if_any_eq(const int4 &m, int id, int v)
-{
-    uint64_t e0, e1, e2, e3;
-    int r;
-    asm("v_cmp_eq_u32_e64 %0, %1, %2" : "=s"(e0) : "s"(id), "v"(m.x));
-    asm("v_cmp_eq_u32_e64 %0, %1, %2" : "=s"(e1) : "s"(id), "v"(m.y));
-    asm("v_cmp_eq_u32_e64 %0, %1, %2" : "=s"(e2) : "s"(id), "v"(m.z));
-    asm("v_cmp_eq_u32_e64 %0, %1, %2" : "=s"(e3) : "s"(id), "v"(m.w));
-    const uint64_t any = (e0 | e1) | (e2 | e3);
-    asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(r) : "v"(v), "s"(any));
-    return r;
-}
-
-__device__ inline bool mode_uses_tokens(int mode) { return mode != kPartialRatio && mode != kPartialTokenSortRatio; }
-
-// 64-bit word-steps a scored pair costs at most (work accounting for the roofline; an estimate from the lengths: one
-// pass over the to-form per LCS, |from| x |to| for a window sweep)
-__device__ inline int work_estimate(const Fz3<int> &la, const int4 &m, int mode, int W)
-{
-    const int pass = m.x + m.y + m.z;
-    if (mode == kTokenSetRatio || mode == kTokenRatio) return pass * W;
-    return (pass + fz_min(la[0], m.x) * fz_max(la[0], m.x) / 4) * W;
 }
 
 template <int W, int MODE = -1>
@@ -850,53 +792,48 @@ __global__ __launch_bounds__(256) void k_best_to_topn(const int32_t *__restrict_
 
 int fuzz_general_launch(pfz_ctx *ctx, FuzzArgs A, const pfz_strings *F, const pfz_strings *T, const std::vector<int32_t> &rows);   // k7_general.hip
 
-// rows [begin, end) of `from` against all of `to`: (first best index, score) into device buffers d_idx / d_score of end - begin entries
-static int fuzz_run(pfz_ctx *ctx, const pfz_strings *F_c, const pfz_strings *T_c, int32_t scorer, const int32_t *skip_idx, int64_t begin,
-                    int64_t end, int32_t *d_idx, double *d_score, unsigned long long *h_counters)
+int64_t fuzz_max_grid(const pfz_ctx *ctx) { return (int64_t)ctx->prop.multiProcessorCount * (4 * PFZ_K7_OCC / kK7Waves); }
+
+// how many workgroups share a from-string's to-groups (few from-strings: split, as K4 does)
+int32_t fuzz_parts(const pfz_ctx *ctx, const pfz_fuzz_plan *pl, int64_t n)
+{
+    const int64_t want = (2 * fuzz_max_grid(ctx) + n - 1) / n, cap = std::max<int64_t>(1, pl->n_groups / (4 * kK7Waves));
+    int32_t parts = (int32_t)std::max<int64_t>(1, std::min(want, cap));
+    if (const char *e = knob_str(knob::K7_PARTS)) parts = std::max(1, atoi(e));
+    return parts;
+}
+
+int fuzz_prepare(pfz_ctx *ctx, const pfz_strings *F_c, const pfz_strings *T_c, int32_t scorer, int64_t begin, int64_t end, FuzzPrep *P)
 {
     pfz_strings *F = const_cast<pfz_strings *>(F_c), *T = const_cast<pfz_strings *>(T_c);     // the caches live inside the handles
-    const int64_t n_rows = end - begin, n_to = T->n;
     if (T->n >= INT_MAX - 64 || F->n >= INT_MAX) {
         set_error("pfz_fuzz: list too long");
         return PFZ_ERR_UNSUPPORTED;
     }
     PFZ_TRY(ensure_forms(ctx, F));
     if (!T->fuzz_plan) PFZ_TRY(build_plan(ctx, T));
-    const pfz_fuzz_plan *pl = T->fuzz_plan;
+    const pfz_fuzz_plan *pl = P->plan = T->fuzz_plan;
     const pfz_fuzz_forms *ff = F->fuzz_forms;
 
     // token ids of the from-list in the to-list's table (the same handle: the plan's own)
-    DevBuf d_aid, d_skip, d_counters;
     const int32_t *a_tok_id = pl->t_tok_id;
     if (F != T) {
-        PFZ_TRY(d_aid.alloc(ctx, (size_t)ff->tok_cap * sizeof(int32_t)));
+        PFZ_TRY(P->d_aid.alloc(ctx, (size_t)ff->tok_cap * sizeof(int32_t)));
         if (F->n > 0) {
             ProfScope ps(ctx, "k7_prepare");
-            PFZ_TRY(from_token_ids(ctx, F, T, (int32_t *)d_aid.p));
+            PFZ_TRY(from_token_ids(ctx, F, T, P->d_aid.as<int32_t>()));
         }
-        a_tok_id = (const int32_t *)d_aid.p;
-    }
-    int skip_up_to = 0;
-    if (skip_idx) {
-        std::vector<int32_t> codes(skip_idx, skip_idx + F->n);
-        skip_up_to = decode_skip_codes(codes);
-        PFZ_REQUIRE(skip_up_to >= 0, "pfz_fuzz_extract_one: skip_idx mixes single choices (>= 0) and 'up to' codes (<= -2)");
-        PFZ_TRY(d_skip.upload(ctx, codes));
-    }
-    if (h_counters) {
-        PFZ_TRY(d_counters.alloc(ctx, 4 * sizeof(unsigned long long)));
-        PFZ_HIP(hipMemsetAsync(d_counters.p, 0, 4 * sizeof(unsigned long long), ctx->stream));
+        a_tok_id = P->d_aid.as<int32_t>();
     }
 
     // word classes of the from-strings; beyond 256 characters / 32 distinct tokens / a 60 KiB match table: the general kernel
-    static const int kWords[3] = {1, 2, 4};
-    std::vector<int32_t> cls[4], slot_of[4];
+    std::vector<int32_t> (&cls)[4] = P->rows, (&slot_of)[4] = P->slot;
     const bool force_general = knob_set(knob::K7_FORCE_GENERAL);
     for (int64_t i = begin; i < end; ++i) {
         const int64_t len = F->h_off[(size_t)i + 1] - F->h_off[(size_t)i];
         int c = len > 256 ? 3 : (len > 128 ? 2 : (len > 64 ? 1 : 0));
         if (ff->h_ntok[(size_t)i] > kFuzzMaxTokens || force_general) c = 3;
-        if (c < 3 && (size_t)(pl->n_sym + 1) * 3 * kWords[c] * sizeof(uint64_t) > 60 * 1024) c = 3;
+        if (c < 3 && (size_t)(pl->n_sym + 1) * 3 * kFuzzWords[c] * sizeof(uint64_t) > 60 * 1024) c = 3;
         cls[c].push_back((int32_t)i);
         slot_of[c].push_back((int32_t)(i - begin));
     }
@@ -922,7 +859,7 @@ static int fuzz_run(pfz_ctx *ctx, const pfz_strings *F_c, const pfz_strings *T_c
         slot_of[c].swap(slots);
     }
 
-    FuzzArgs A{};
+    FuzzArgs &A = P->A;
     A.a_form[0] = F->chars;
     A.a_form[1] = ff->form1;
     A.a_form[2] = ff->form2;
@@ -952,25 +889,49 @@ static int fuzz_run(pfz_ctx *ctx, const pfz_strings *F_c, const pfz_strings *T_c
     A.n_groups = (int32_t)pl->n_groups;
     A.n_sym1 = pl->n_sym + 1;
     A.mode = scorer;
+    return PFZ_OK;
+}
+
+// rows [begin, end) of `from` against all of `to`: (first best index, score) into device buffers d_idx / d_score of end - begin entries
+static int fuzz_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, int32_t scorer, const int32_t *skip_idx, int64_t begin,
+                    int64_t end, int32_t *d_idx, double *d_score, unsigned long long *h_counters)
+{
+    const int64_t n_rows = end - begin, n_to = T->n;
+    FuzzPrep prep;
+    PFZ_TRY(fuzz_prepare(ctx, F, T, scorer, begin, end, &prep));
+    const pfz_fuzz_plan *pl = prep.plan;
+    std::vector<int32_t> (&cls)[4] = prep.rows, (&slot_of)[4] = prep.slot;
+    FuzzArgs &A = prep.A;
+
+    DevBuf d_skip, d_counters;
+    int skip_up_to = 0;
+    if (skip_idx) {
+        std::vector<int32_t> codes(skip_idx, skip_idx + F->n);
+        skip_up_to = decode_skip_codes(codes);
+        PFZ_REQUIRE(skip_up_to >= 0, "pfz_fuzz_extract_one: skip_idx mixes single choices (>= 0) and 'up to' codes (<= -2)");
+        PFZ_TRY(d_skip.upload(ctx, codes));
+    }
+    if (h_counters) {
+        PFZ_TRY(d_counters.alloc(ctx, 4 * sizeof(unsigned long long)));
+        PFZ_HIP(hipMemsetAsync(d_counters.p, 0, 4 * sizeof(unsigned long long), ctx->stream));
+    }
     A.skip_idx = skip_idx ? (const int32_t *)d_skip.p : nullptr;
     A.skip_up_to = skip_up_to;
     A.counters = h_counters ? (unsigned long long *)d_counters.p : nullptr;
 
-    // how many workgroups share a from-string's to-groups (few from-strings: split, as K4 does), per class; then one slot for
-    // the general kernel's "to-strings with more than 32 tokens" pass and one for its own rows
-    const int64_t max_grid = (int64_t)ctx->prop.multiProcessorCount * (4 * PFZ_K7_OCC / kK7Waves);      // (persistent workgroups: units are handed out)
+    // how many workgroups share a from-string's to-groups, per class; then one slot for the general kernel's "to-strings with
+    // more than 32 tokens" pass and one for its own rows
+    const int64_t max_grid = fuzz_max_grid(ctx);      // (persistent workgroups: units are handed out)
     int32_t parts_of[3] = {1, 1, 1}, max_parts = 1;
     for (int c = 0; c < 3; ++c) {
         if (cls[c].empty()) continue;
         const int64_t n = (int64_t)cls[c].size();
-        const int64_t want = (2 * max_grid + n - 1) / n, cap = std::max<int64_t>(1, pl->n_groups / (4 * kK7Waves));
-        parts_of[c] = (int32_t)std::max<int64_t>(1, std::min(want, cap));
+        parts_of[c] = fuzz_parts(ctx, pl, n);
         // One-word from-strings that are ONE unit each hand their heavy rows over to continuation units (below) -- rows
         // that are split up front cannot, and a few thousand of them split in two are the worst of both: 5 000 x 20 000
         // titles, WRatio, 9.3 ms in two parts each against 5.2 ms whole (2 500: 5.2 against 4.6; 1 000 rows are better
         // split: 2.3 against 3.2).  From 2 048 rows on a row is one unit.
-        if (c == 0 && n >= 2048 && kK7Waves == 1) parts_of[c] = 1;
-        if (const char *e = knob_str(knob::K7_PARTS)) parts_of[c] = std::max(1, atoi(e));
+        if (c == 0 && n >= 2048 && kK7Waves == 1 && !knob_str(knob::K7_PARTS)) parts_of[c] = 1;
         max_parts = std::max(max_parts, parts_of[c]);
     }
     int32_t hand_batches = kHandBatches, hand_min_groups = kHandMinGroups, cont_parts = kContParts;
@@ -1050,7 +1011,7 @@ static int fuzz_run(pfz_ctx *ctx, const pfz_strings *F_c, const pfz_strings *T_c
         A.parts = parts_of[c];
         A.part0 = 0;
         // (the match table, the scratch columns -- bytes for a small alphabet --, the timers when asked for: see the kernel)
-        const size_t lds = (size_t)A.n_sym1 * 3 * (size_t)kWords[c] * sizeof(uint64_t) +
+        const size_t lds = (size_t)A.n_sym1 * 3 * (size_t)kFuzzWords[c] * sizeof(uint64_t) +
                            (size_t)kK7Waves * kFuzzStage * 64 * (A.n_sym1 <= 256 ? 1 : 2) + (A.phase_ticks ? 24 * sizeof(unsigned long long) : 0);
         // (only where a row is ONE unit: a row already split over several units would hand over several remainders, and they
         // would share the continuation's result slots)

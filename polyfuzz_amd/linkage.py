@@ -147,7 +147,9 @@ def connected_components(strings: List[str], model,
     "jaro" or "jaro_winkler" (K16): the components of the pairs among its symmetrised TF-IDF candidates that reach min_similarity --
     equal strings share one whenever the blocking stage lists one for the other.  A BlockedEditDistance with blocking_similarity
     set (K17) takes the pairs of the TF-IDF threshold join at that cosine for its candidates instead: equal strings that have an
-    n-gram then share a component however many copies the list holds."""
+    n-gram then share a component however many copies the list holds.  Or a RapidFuzz under one of K7's seven scorers (K18; WRatio
+    by default): the components of "score >= min_similarity * 100" -- equal strings share one whenever they have a token; under
+    WRatio, min_similarity <= 0.855 links everything that shares a word with a string 1.5 times its length or more."""
     strings = list(strings)
     extra = {} if embeddings is None else {"embeddings": embeddings}
     return dicts_from_labels(strings, model.components(strings, min_similarity, **extra))

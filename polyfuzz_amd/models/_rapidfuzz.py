@@ -24,6 +24,9 @@ a bug).  `reference_self_match = True` (attribute, or keyword of `match`) reprod
 device: every choice up to and including the row itself is left out (skip codes, csrc/pfz_internal.h) -- held to frames of
 the reference class itself (tests/golden/make_golden_rapidfuzz_self.py).
 
+Threshold forms (K18, k18_fuzz_join.hip), under the seven K7 scorers: `join` -- every pair at least `min_similarity` similar, what
+rapidfuzz.process.cdist(..., score_cutoff=c) keeps -- and `components` -- the clusters of that relation over one list.
+
 PARITY UNPINNED: rapidfuzz is not installable in the build container; the scorer is the oracle's restatement
 (oracle/indel.c), extractOne's tie / cut-off rules are restated from rapidfuzz's documentation.
 """
@@ -34,7 +37,7 @@ import pandas as pd
 
 from .. import _lib
 from ._base import BaseMatcher
-from ._utils import pair_frame, pair_frame_blocks
+from ._utils import gather_column, pair_frame, pair_frame_blocks
 
 _K4_SCORERS = ("ratio", "QRatio", "token_sort_ratio")
 _DEVICE_SCORERS = _K4_SCORERS + tuple(_lib.FUZZ_SCORERS)
@@ -145,6 +148,8 @@ class RapidFuzz(BaseMatcher):
         scorer: a rapidfuzz.fuzz scorer or its name; default (None) = fuzz.WRatio as in the reference.  Every
                 rapidfuzz.fuzz scorer runs on the device; other callables raise NotImplementedError
         model_id: The name of the particular instance, used when comparing models
+
+    Beyond the reference: `join` (every pair above a similarity) and `components` (the clusters of that relation), K18.
     """
     def __init__(self,
                  n_jobs: int = 1,
@@ -210,6 +215,84 @@ class RapidFuzz(BaseMatcher):
         hit = (idx >= 0) & (score >= self.score_cutoff)                       # extractOne: best score >= score_cutoff
         sim = np.where(hit, score / 100, 0.0)
         return pair_frame(from_list, names, idx, sim, keep=hit, blocks=blocks)
+
+    def _threshold_cutoff(self, what, min_similarity):
+        """the checks of join / components, before any device call: the scorer has a threshold kernel, min_similarity is a number
+        in [0, 1]; returns the cutoff on rapidfuzz's 0..100 scale -- the expression __init__ uses for score_cutoff"""
+        if self._scorer_name not in _lib.FUZZ_SCORERS:
+            raise NotImplementedError(
+                f"RapidFuzz.{what} runs on the GPU for the scorers {tuple(_lib.FUZZ_SCORERS)}; scorer {self._scorer_name!r} is one "
+                "fixed string per list element and has no threshold kernel here -- the same metric on the 0..1 scale is "
+                'EditDistance(scorer="indel"), which has join and components')
+        return _lib.check_min_similarity(min_similarity) * 100.0
+
+    def join(self,
+             from_list: List[str],
+             to_list: List[str] = None,
+             min_similarity: float = 0.8,
+             **kwargs) -> pd.DataFrame:
+        """ Every pair at least `min_similarity` similar under the matcher's scorer (K18): the frame From, To, Similarity with one
+        row per pair, ordered by from-index, then to-index.  A from-string without a partner has no row.  A pair is kept iff its
+        score -- the float64 `match` would report for it, on rapidfuzz's 0..100 scale -- is >= min_similarity * 100.0 (that
+        product, in float64, is the cutoff; equal is kept: rapidfuzz's score_cutoff); Similarity = score / 100, unrounded.
+        Exact: every such pair is found, whatever their number.  The constructor's `score_cutoff` plays no part.
+
+        to_list None: the self-join of from_list -- every pair of positions i < j once, as From = from_list[i],
+        To = from_list[j] (From is always the EARLIER position), scored as scorer(from_list[i], from_list[j]); never a string
+        with itself, but equal strings at different positions are a pair like any other.  Equal strings do not always score
+        100: WRatio("", "") is 0, and token_set_ratio, partial_token_set_ratio and partial_token_ratio of two strings without
+        a token ("", "  ") are 0 -- such copies are no pair above min_similarity = 0.
+
+        Under WRatio any two strings that share a token score at least 85.5 (100 * 0.95 * 0.9) when their lengths differ by a
+        factor of 1.5 or more: min_similarity <= 0.855 joins everything that shares a word.
+
+        `re_train=False` follows `match`'s rule: when to_list IS the previous call's (the same object, or an equal list), its
+        device copy, token forms and plan are used again.
+
+        The seven K7 scorers only (NotImplementedError under ratio / QRatio / token_sort_ratio); min_similarity: a number in
+        [0, 1] (ValueError otherwise).  For the clusters of the self-join's graph see `components`, which never builds the
+        frame. """
+        cutoff = self._threshold_cutoff("join", min_similarity)
+        self_join = to_list is None
+        names = from_list if self_join else to_list
+        snap = None if self_join else tuple(to_list)
+        reuse = kwargs.get("re_train", True) is False and not self_join and self._to_dev is not None and snap == self._to_names
+        held = self._to_dev
+        self._to_dev = self._to_names = None      # set again below, once this call's to-list is resident
+        if len(from_list) == 0 or len(names) == 0:
+            return pd.DataFrame({"From": np.empty(0, object), "To": np.empty(0, object), "Similarity": np.empty(0, np.float64)})
+        ctx = _lib.Context.default()
+        f_dev = upload_for(ctx, self._scorer_name, from_list)
+        if not self_join:
+            self._to_dev, self._to_names = (held if reuse else upload_for(ctx, self._scorer_name, names)), snap
+        row_ptr, idx, score = _lib.fuzz_join(ctx, f_dev, None if self_join else self._to_dev, self._scorer_name, cutoff)
+        frm = np.repeat(np.arange(len(from_list), dtype=np.int32), np.diff(row_ptr))
+        return pd.DataFrame({"From": gather_column(from_list, frm), "To": gather_column(names, idx), "Similarity": score / 100},
+                            copy=False)
+
+    def components(self,
+                   strings: List[str],
+                   min_similarity: float = 0.8) -> np.ndarray:
+        """ Near-duplicate clusters of `strings` under the matcher's scorer (K18): int32 labels, label[i] = the smallest position
+        in i's connected component of the graph whose edges are the pairs `join(strings, min_similarity=...)` reports (the
+        self-join: From is the earlier position, To the later) -- "A ~ B and B ~ C put A, B and C together".  A string with no
+        partner is its own component (label[i] == i).  Exact and deterministic.  The pairs are united on the device where they are
+        found and never stored: device memory is O(len(strings)) whatever their number.
+        polyfuzz_amd.linkage.connected_components turns the labels into the three dicts single_linkage returns.
+
+        Equal strings share a component whenever they have a token (they score 100); empty or token-less copies score 0 under
+        WRatio and the token-set scorers (see `join`) and stay apart above min_similarity = 0.  Under WRatio two strings that share a token score
+        at least 85.5 (100 * 0.95 * 0.9) when their lengths differ by a factor of 1.5 or more: min_similarity <= 0.855 chains
+        together everything that shares a word.
+
+        The seven K7 scorers only (NotImplementedError otherwise); min_similarity: a number in [0, 1] (ValueError otherwise). """
+        cutoff = self._threshold_cutoff("components", min_similarity)
+        if len(strings) == 0:
+            return np.empty(0, np.int32)
+        ctx = _lib.Context.default()
+        label, pairs, components = _lib.fuzz_components(ctx, upload_for(ctx, self._scorer_name, strings), self._scorer_name, cutoff)
+        self.last_counts = {"pairs": pairs, "components": components}
+        return label
 
     # a matcher is pickled by joblib (reference polyfuzz.py:429-457): device handles stay behind
     def __getstate__(self):
