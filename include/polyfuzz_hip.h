@@ -392,6 +392,24 @@ int pfz_fuzz_join(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strin
  * Errors as pfz_fuzz_join (there is no capacity).  Blocks. */
 int pfz_fuzz_components(pfz_ctx *ctx, const pfz_strings *strings, int32_t scorer, double score_cutoff, int32_t *out_label,
                         int64_t *out_pairs, int64_t *out_components, int64_t *out_counters);
+/* K19: the ntop best choices of every from-string of rows [from_begin, from_end) under the per-pair scorers --
+ * rapidfuzz.process.extract(query, choices, scorer=fuzz.WRatio, limit=ntop, score_cutoff=c), where the reference's matcher
+ * (_rapidfuzz.py:99-113) asks for the one best.  Per row: the choices not left out (skip_idx as in pfz_fuzz_extract_one: >= 0 one
+ * choice, <= -2 every choice up to -2 - code, -1 none) whose score -- exactly the float64 pfz_fuzz_extract_one computes for the
+ * pair -- is >= score_cutoff (equal is kept), in the order np.argsort(-scores, kind="stable")[:ntop]: score descending, equal
+ * scores by ascending to-index.  Column 0 at score_cutoff = 0 is pfz_fuzz_extract_one's result.  out_idx / out_score: host
+ * buffers of (from_end - from_begin) * ntop entries, row-major; the slots beyond the choices a row has (ntop may exceed the
+ * to-list) carry -1 / 0.0.  An empty row range writes nothing; an empty to-list gives rows of -1 / 0.0; neither launches a kernel.
+ * out_counters: NULL, or uint64[3] as pfz_fuzz_join's ([0] pairs bounded, [1] pairs scored, [2] word-steps).
+ * Exact: the walk is pfz_fuzz_join's with the floor moving -- a pair is left unscored only where K7's upper bound of its score,
+ * plus K7's slack, is STRICTLY below the score of the ntop-th best choice the wave holds (or below score_cutoff before it holds
+ * ntop), so a tie with the ntop-th best is still scored and placed by its index (csrc/k7_join_walk.h, csrc/topn_wave.h).
+ * Argument checks: a NULL handle, scorer outside 0..6, a row range outside the from-list, ntop < 1, a NaN score_cutoff or one
+ * outside [0, 100], skip_idx mixing both code forms: PFZ_ERR_INVALID.  ntop > 64 (one list entry per lane of a wave), K7's list
+ * limits: PFZ_ERR_UNSUPPORTED.  Blocks. */
+int pfz_fuzz_topn(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings, int32_t scorer, const int32_t *skip_idx,
+                  int64_t from_begin, int64_t from_end, int32_t ntop, double score_cutoff, int32_t *out_idx, double *out_score,
+                  uint64_t *out_counters);
 
 /* ---- K8: all-pairs Jaro / Jaro-Winkler similarity + row arg-max --------------
  * Replaces the hot loop of EditDistance._calculate_edit_distance (reference

@@ -119,6 +119,7 @@ SIGNATURES = {
     "pfz_fuzz_plan_info": (ctypes.c_int, [c_vp, c_vp, P(c_i64), P(c_i64), P(c_i64), P(c_i64)]),
     "pfz_fuzz_join": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_f64, c_i64, c_vp, c_vp, c_vp, P(c_i64), c_vp]),
     "pfz_fuzz_components": (ctypes.c_int, [c_vp, c_vp, c_i32, c_f64, c_vp, P(c_i64), P(c_i64), c_vp]),
+    "pfz_fuzz_topn": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_i32, c_f64, c_vp, c_vp, c_vp]),
     "pfz_dense_cossim_topn_host": (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_f32, c_i32,
                                                   c_vp, c_vp]),
     "pfz_dense_dot_topn_host": (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_f32, c_i32,
@@ -1303,6 +1304,24 @@ def fuzz_components(ctx, dev, scorer, score_cutoff, counters=False):
     appends a dict of FUZZ_JOIN_COUNTERS."""
     return _components_call(dev.n, FUZZ_JOIN_COUNTERS, counters, lambda label, pairs, components, wk: ctx.lib.pfz_fuzz_components(
         ctx.h, dev.h, FUZZ_SCORERS[scorer], float(score_cutoff), label, pairs, components, wk))
+
+
+def fuzz_topn(ctx, from_dev, to_dev, scorer, ntop, skip_idx=None, score_cutoff=0.0, begin=0, end=None, counters=False):
+    """K19: the ntop best choices of from-rows [begin, end) under the K7 scorer `scorer` (a name of FUZZ_SCORERS) --
+    rapidfuzz.process.extract(..., limit=ntop, score_cutoff=score_cutoff): (index int32[n, ntop], score float64[n, ntop]) in the
+    order (score descending, to-index ascending) over the choices not left out (skip_idx: fuzz_extract_one's codes) whose score --
+    fuzz_extract_one's float64 on the 0..100 scale, bit for bit -- is >= score_cutoff (equal is kept); -1 / 0.0 beyond the choices a
+    row has.  Column 0 at score_cutoff 0 is fuzz_extract_one's answer.  ntop <= 64 (PfzUnsupported beyond).  counters=True
+    appends a dict of FUZZ_JOIN_COUNTERS."""
+    end = from_dev.n if end is None else end
+    n = end - begin
+    idx = np.empty((n, max(int(ntop), 0)), np.int32)           # (ntop < 1 is the library's to refuse)
+    score = np.empty((n, max(int(ntop), 0)), np.float64)
+    skip_idx = _skip_array(skip_idx, from_dev.n)
+    work = np.zeros(len(FUZZ_JOIN_COUNTERS), np.uint64) if counters else None
+    check(ctx.lib.pfz_fuzz_topn(ctx.h, from_dev.h, to_dev.h, FUZZ_SCORERS[scorer], _ptr(skip_idx), int(begin), int(end), int(ntop),
+                                float(score_cutoff), _ptr(idx), _ptr(score), _ptr(work)))
+    return (idx, score, dict(zip(FUZZ_JOIN_COUNTERS, (int(w) for w in work)))) if counters else (idx, score)
 
 
 # ---- K15: the sparse-cosine threshold join and its components --------------------------------------------------------

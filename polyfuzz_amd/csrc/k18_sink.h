@@ -1,4 +1,4 @@
-// K18: what the threshold kernels over K7's plan (k18_fuzz_join.hip: k7_join_kernel; k7_general.hip: k7_general_join_kernel) do
+// K18: what the threshold kernels over K7's plan (k7_join_walk.h: k7_join_kernel; k7_general.hip: k7_general_join_kernel) do
 // with a hit, and the fields of a call beside K7's argument block.  The sinks are edit_walk.h's KeyAppend / ForestHook with a
 // float64 score: called by a whole wave, the hits of one call behind ONE atomic.
 #pragma once
@@ -7,6 +7,13 @@
 #include "k18_core.h"
 
 namespace pfz {
+
+// what the kernels ask of a sink type at compile time: topn -- the sink is a wave's sorted list and the floor rises with it
+// (k19_sink.h: FuzzTopn); the sinks below are called with every scored pair against a floor that never moves
+template <typename SINK>
+struct FuzzSinkTrait {
+    static constexpr bool topn = false;
+};
 
 struct FuzzJoinArgs {
     double cutoff;               // 0..100; a pair is a hit iff score >= cutoff

@@ -1,5 +1,5 @@
 // K7 / K18: what the register / LDS kernels over K7's plan share -- the arg-max kernel (k7_fuzz.hip: k7_fuzz_kernel) and the
-// threshold join (k18_fuzz_join.hip: k7_join_kernel).  The device-side settings k7_core.h is compiled under, the few lane helpers
+// threshold join and the top-n form (k7_join_walk.h: k7_join_kernel).  The device-side settings k7_core.h is compiled under, the few lane helpers
 // both kernels use, and the host-side preparation of a call (forms, plan, from-token ids, the FuzzArgs fill, the word-class split).
 #pragma once
 #include "pfz_internal.h"

@@ -7,7 +7,8 @@
 // over the device-resident forms and plan; slow -- everything is a global-memory access -- and only ever sees the rare
 // strings the fast kernel cannot hold.   PARITY UNPINNED (rapidfuzz is not installable).
 // Two kernels share that per-pair statement (general_pair_score): k7_general_kernel keeps every row's first best choice (K7),
-// k7_general_join_kernel holds every pair's score against a cutoff and hands the hits to a sink (K18, k18_fuzz_join.hip).
+// k7_general_join_kernel holds every pair's score against a cutoff and hands the hits to a sink (K18, k18_fuzz_join.hip) or keeps
+// each wave's n best (K19, k19_fuzz_topn.hip).
 #include "pfz_internal.h"
 
 #include <algorithm>
@@ -19,7 +20,7 @@
 #define PFZ_LDS_U8 __attribute__((address_space(3))) uint8_t
 #include "k7_core.h"
 #include "k7_args.h"
-#include "k18_sink.h"
+#include "k19_sink.h"
 
 namespace pfz {
 
@@ -337,9 +338,14 @@ __global__ __launch_bounds__(256) void k7_general_join_kernel(FuzzArgs A, FuzzJo
     const int64_t stride = 256;
     const int64_t n_slots = A.n_big > 0 ? A.n_big : (int64_t)A.n_groups * 64;
     unsigned long long n_pairs = 0;
+    constexpr bool kTopn = FuzzSinkTrait<SINK>::topn;
     for (int r = blockIdx.x; r < A.n_rows; r += gridDim.x) {
         const int frow = A.rows[r];
         const GeneralFrom G = general_from(A, frow);
+        // K19: the wave's list of this row, and the choices left out by K7's skip codes (the join's rule is J.self)
+        [[maybe_unused]] TopnList list = topn_empty();
+        [[maybe_unused]] int skip = -1;
+        if constexpr (kTopn) skip = A.skip_idx ? A.skip_idx[frow] : -1;
         // (every wave makes the same number of trips: the sink is a wave's call)
         for (int64_t k0 = 0; k0 < n_slots; k0 += 256) {
             const int64_t k = k0 + tid;
@@ -348,14 +354,19 @@ __global__ __launch_bounds__(256) void k7_general_join_kernel(FuzzArgs A, FuzzJo
             if (k < n_slots) {
                 const int slot = A.n_big > 0 ? A.big_slots[k] : (int)k;
                 orig = A.b_meta2[slot].w;
-                if (orig >= 0 && !(J.self && orig <= frow)) {
+                bool out;
+                if constexpr (kTopn) out = choice_left_out(orig, skip, A.skip_up_to);
+                else out = J.self && orig <= frow;
+                if (orig >= 0 && !out) {
                     score = general_pair_score(A, mode, G, a_tok_pos, slot, A.b_meta[slot], row, dpa, dpb, stride);
                     n_pairs += 1;
                 }
                 else orig = -1;
             }
-            sink(orig >= 0 && fuzz_join_hit(score, J.cutoff), frow, orig, score);
+            if constexpr (kTopn) topn_insert(list, sink.ntop, orig >= 0 && fuzz_join_hit(score, J.cutoff), score, orig);
+            else sink(orig >= 0 && fuzz_join_hit(score, J.cutoff), frow, orig, score);
         }
+        if constexpr (kTopn) topn_store(list, sink.ntop, sink.slot(frow, sink.general0 + (tid >> 6)));
     }
     if (A.counters) {
 #pragma unroll
@@ -426,6 +437,14 @@ int fuzz_general_join_launch(pfz_ctx *ctx, FuzzArgs A, const FuzzJoinArgs &J, co
 {
     return general_launch(ctx, A, F, T, rows, [&](dim3 grid, const FuzzArgs &L, const GeneralScratch &S, const int32_t *tok_pos) {
         hipLaunchKernelGGL(k7_general_join_kernel<FuzzUnite>, grid, dim3(256), 0, ctx->stream, L, J, sink, S, tok_pos);
+    });
+}
+
+int fuzz_general_join_launch(pfz_ctx *ctx, FuzzArgs A, const FuzzJoinArgs &J, const FuzzTopn &sink, const pfz_strings *F,
+                             const pfz_strings *T, const std::vector<int32_t> &rows)
+{
+    return general_launch(ctx, A, F, T, rows, [&](dim3 grid, const FuzzArgs &L, const GeneralScratch &S, const int32_t *tok_pos) {
+        hipLaunchKernelGGL(k7_general_join_kernel<FuzzTopn>, grid, dim3(256), 0, ctx->stream, L, J, sink, S, tok_pos);
     });
 }
 

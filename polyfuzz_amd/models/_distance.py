@@ -204,7 +204,8 @@ class EditDistance(BaseMatcher):
     "token_sort_ratio", "indel" (K4), "levenshtein" and "osa" (K9).  The scores are the scorer's own float64, unrounded; `normalize` takes
     ONE minimum and maximum over all Similarity columns.  top_n is clipped to the number of choices every row has (the
     reference's clip, _utils.py:55-56); more than 64 after clipping raises _lib.PfzUnsupported; the Jaro scorers and the
-    per-pair scorers (K7) raise NotImplementedError from `match` -- their kernels keep a single best.  An int >= 1, else
+    per-pair scorers (K7) raise NotImplementedError from `match` -- their kernels keep a single best (for the per-pair scorers the
+    top-n form is RapidFuzz.top_n, K19).  An int >= 1, else
     ValueError; kept through pickling.
 
     join (method, "levenshtein", "osa" and "indel"): every pair at least `min_similarity` similar instead of each string's best --

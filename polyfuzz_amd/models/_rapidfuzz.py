@@ -27,6 +27,9 @@ the reference class itself (tests/golden/make_golden_rapidfuzz_self.py).
 Threshold forms (K18, k18_fuzz_join.hip), under the seven K7 scorers: `join` -- every pair at least `min_similarity` similar, what
 rapidfuzz.process.cdist(..., score_cutoff=c) keeps -- and `components` -- the clusters of that relation over one list.
 
+Top-n (`top_n` attribute; K19, k19_fuzz_topn.hip): the n best choices of every from-string, rapidfuzz.process.extract(..., limit=n,
+score_cutoff=c) -- K18's walk with the floor rising to the n-th best a wave holds; the K4 scorers through K4's own top-n.
+
 PARITY UNPINNED: rapidfuzz is not installable in the build container; the scorer is the oracle's restatement
 (oracle/indel.c), extractOne's tie / cut-off rules are restated from rapidfuzz's documentation.
 """
@@ -37,7 +40,7 @@ import pandas as pd
 
 from .. import _lib
 from ._base import BaseMatcher
-from ._utils import gather_column, pair_frame, pair_frame_blocks
+from ._utils import gather_column, object_column, pair_frame, pair_frame_blocks
 
 _K4_SCORERS = ("ratio", "QRatio", "token_sort_ratio")
 _DEVICE_SCORERS = _K4_SCORERS + tuple(_lib.FUZZ_SCORERS)
@@ -150,6 +153,15 @@ class RapidFuzz(BaseMatcher):
         model_id: The name of the particular instance, used when comparing models
 
     Beyond the reference: `join` (every pair above a similarity) and `components` (the clusters of that relation), K18.
+
+    top_n (attribute, default 1; the constructor keeps the reference's signature: `m = RapidFuzz(); m.top_n = 5`): the number of
+    best choices per from-string -- rapidfuzz.process.extract(..., limit=top_n, score_cutoff=...) where the reference asks
+    extractOne.  `match` then returns the columns To, Similarity, To_2, Similarity_2, ... in the order np.argsort(-scores,
+    kind="stable") gives: score descending, equal scores in list order, exact, on the device, under all ten scorers (the seven
+    per-pair scorers: K19; ratio / QRatio / token_sort_ratio: K4's top-n).  Similarity = score / 100; a cell whose choice is
+    missing or scores below `score_cutoff` is None / 0.0.  top_n is clipped to the number of choices every row has (one less in
+    a self-match); more than 64 after clipping raises _lib.PfzUnsupported before any device call.  An int >= 1, else
+    ValueError; kept through pickling.  top_n = 1 is the frame and the code path it always was.
     """
     def __init__(self,
                  n_jobs: int = 1,
@@ -169,6 +181,18 @@ class RapidFuzz(BaseMatcher):
         self.n_jobs = n_jobs
         self.reference_self_match = False        # True: a self-match as the reference's shared, shrinking list gives it (n_jobs = 1)
         self._to_dev = self._to_names = None     # device copy (+ cached plan) of the last to-list
+        self._top_n = 1
+
+    @property
+    def top_n(self) -> int:
+        """best choices per from-string (class docstring); 1: the best match, the reference's frame"""
+        return self.__dict__.get("_top_n", 1)          # (a matcher pickled before the attribute existed)
+
+    @top_n.setter
+    def top_n(self, value):
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < 1:
+            raise ValueError(f"top_n must be an int >= 1, not {value!r}")
+        self._top_n = int(value)
 
     def match(self,
               from_list: List[str],
@@ -180,6 +204,8 @@ class RapidFuzz(BaseMatcher):
         polyfuzz.py:234-240).  `re_train=False` only lets this matcher re-use what is resident: when the list it is handed IS
         the previous call's (the same object, or an equal list), its device copy, token forms and plan are used again -- no
         upload, no preparation.  Any other list is uploaded. """
+        if self.top_n > 1:
+            return self._match_top_n(from_list, to_list, **kwargs)
         ctx = _lib.Context.default()
         self_match = to_list is None
         # the resident copy stands for the list it was made from and for no other (ADVICE r3)
@@ -191,16 +217,7 @@ class RapidFuzz(BaseMatcher):
         self._to_dev = self._to_names = None      # set again below, once this call's to-list is resident
         names = from_list if self_match else to_list
         n = len(from_list)
-        skip = None
-        if self_match and kwargs.get("reference_self_match", self.reference_self_match):
-            # _rapidfuzz.py:86-104 with n_jobs = 1: when row i is scored, list.remove has taken the rows 0 .. i out of the shared
-            # list (the first remaining element equal to from_list[i] is row i itself), and what is left keeps its order
-            skip = (-2 - np.arange(n, dtype=np.int64)).astype(np.int32)
-        elif self_match:
-            first = {}
-            for j, s in enumerate(names):
-                first.setdefault(s, j)
-            skip = np.fromiter((first[s] for s in from_list), np.int32, n)
+        skip = self._self_match_skip(from_list, kwargs) if self_match else None
         blocks = None
         if n == 0 or len(names) - (1 if self_match else 0) <= 0:
             idx, score = np.full(n, -1, np.int32), np.zeros(n)             # extractOne over no choices: None
@@ -215,6 +232,56 @@ class RapidFuzz(BaseMatcher):
         hit = (idx >= 0) & (score >= self.score_cutoff)                       # extractOne: best score >= score_cutoff
         sim = np.where(hit, score / 100, 0.0)
         return pair_frame(from_list, names, idx, sim, keep=hit, blocks=blocks)
+
+    def _self_match_skip(self, from_list, kwargs):
+        """the skip codes of a self-match (csrc/pfz_internal.h), one per from-string"""
+        n = len(from_list)
+        if kwargs.get("reference_self_match", self.reference_self_match):
+            # _rapidfuzz.py:86-104 with n_jobs = 1: when row i is scored, list.remove has taken the rows 0 .. i out of the shared
+            # list (the first remaining element equal to from_list[i] is row i itself), and what is left keeps its order
+            return (-2 - np.arange(n, dtype=np.int64)).astype(np.int32)
+        first = {}
+        for j, s in enumerate(from_list):
+            first.setdefault(s, j)
+        return np.fromiter((first[s] for s in from_list), np.int32, n)
+
+    def _match_top_n(self, from_list, to_list=None, **kwargs):
+        """the frame From, To, Similarity, To_2, Similarity_2, ... of the top_n best choices (class docstring); `match`'s rules for
+        the self-match, reference_self_match and re_train=False"""
+        from ._distance import _TOP_N_MAX, _top_n_choices
+        self_match = to_list is None
+        names = from_list if self_match else to_list
+        n = len(from_list)
+        # every row has len(to_list) choices, or one less in a self-match (reference _utils.py:55-56, applied to choices)
+        ntop = max(1, min(self.top_n, len(names) - (1 if self_match else 0)))
+        if ntop > _TOP_N_MAX:
+            raise _lib.PfzUnsupported(-4, f"RapidFuzz.top_n = {ntop} exceeds the limit of {_TOP_N_MAX} best choices per from-string")
+        snap = None if self_match else tuple(to_list)
+        reuse = kwargs.get("re_train", True) is False and not self_match and self._to_dev is not None and snap == self._to_names
+        held = self._to_dev
+        self._to_dev = self._to_names = None      # set again below, once this call's to-list is resident
+        skip = self._self_match_skip(from_list, kwargs) if self_match else None
+        if n == 0 or len(names) - (1 if self_match else 0) <= 0:
+            idx, score = np.full((n, ntop), -1, np.int32), np.zeros((n, ntop))             # extract over no choices: nothing
+        else:
+            ctx = _lib.Context.default()
+            name = self._scorer_name
+            if not self_match:
+                self._to_dev, self._to_names = (held if reuse else upload_for(ctx, name, names)), snap
+            if name in _lib.FUZZ_SCORERS:
+                f_dev = upload_for(ctx, name, from_list)
+                # the matcher's cut-off is the kernel's first floor (K19); the entry takes 0 .. 100 only, so one outside is clamped
+                # for the kernel and `hit` below applies it as it is
+                floor = min(max(float(self.score_cutoff), 0.0), 100.0) if self.score_cutoff == self.score_cutoff else 0.0
+                idx, score = _lib.fuzz_topn(ctx, f_dev, f_dev if self_match else self._to_dev, name, ntop, skip, score_cutoff=floor)
+            else:
+                idx, score = _top_n_choices(ctx, name, from_list, names, skip, self_match, None if self_match else self._to_dev, ntop)
+        hit = (idx >= 0) & (score >= self.score_cutoff)
+        data = {"From": object_column(from_list)}
+        for r in range(ntop):
+            data["To" if r == 0 else f"To_{r + 1}"] = gather_column(names, np.ascontiguousarray(idx[:, r]), np.ascontiguousarray(hit[:, r]))
+            data["Similarity" if r == 0 else f"Similarity_{r + 1}"] = np.where(hit[:, r], score[:, r] / 100, 0.0)
+        return pd.DataFrame(data, copy=False)
 
     def _threshold_cutoff(self, what, min_similarity):
         """the checks of join / components, before any device call: the scorer has a threshold kernel, min_similarity is a number
