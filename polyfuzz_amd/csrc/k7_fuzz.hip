@@ -4,7 +4,8 @@
 // (ratio / QRatio / token_sort_ratio are one fixed string per list element: K4, k4_indel.hip.)
 //
 // The arithmetic of one pair -- exact score, and a cheap upper bound of it -- is k7_core.h; the preparation of the lists (the
-// first two items below) is k7_plan.hip / k7_plan.h; this file is the match kernel and its launch.  All of it on the device:
+// first two items below) is k7_plan.hip / k7_plan.h; the set-up of a from-string and the bound of a pair from registers, shared
+// with K18 / K19, are k7_row.h; this file is the match kernel and its launch.  All of it on the device:
 //
 //  * the three FORMS of a list (the strings; their whitespace tokens sorted and joined; their distinct tokens sorted and
 //    joined, with the tokens' positions / lengths / hashes) -- k7_tokenize, one thread per string, cached on the list's
@@ -40,6 +41,7 @@
 // scratch -- slow, but the reference accepts such inputs.   PARITY UNPINNED (rapidfuzz is not installable): the oracle
 // is oracle/fuzz_scorers.{py,c}, anchored on rapidfuzz's published values.
 #include "k7_device.h"
+#include "k7_row.h"
 
 #include <algorithm>
 #include <climits>
@@ -96,12 +98,7 @@ __global__ __launch_bounds__(kK7Threads, W == 1 ? PFZ_K7_OCC : (W == 2 ? 3 : 2))
     const bool narrow = A.n_sym1 <= 256;
     unsigned char *s_stage = smem_raw + (size_t)A.n_sym1 * 3 * W * sizeof(uint64_t);
     unsigned long long *s_ticks = (unsigned long long *)(s_stage + (size_t)kK7Waves * kFuzzStage * 64 * (narrow ? 1 : 2));
-    __shared__ int s_la[3], s_ta, s_nspace, s_usum;
-    __shared__ int s_tid[kFuzzMaxTokens], s_tlen[kFuzzMaxTokens];
-    __shared__ uint64_t s_tmask[kFuzzMaxTokens * W], s_smask[kFuzzMaxTokens * W];
-    __shared__ int s_cnt[4 * kFuzzHistWords];
-    __shared__ uint32_t s_hist[kFuzzHistWords], s_sig[2];
-    __shared__ uint32_t s_pres[2];
+    __shared__ FuzzRow<W> s_row;                  // the from-string (k7_row.h)
     __shared__ double red_s[kK7Waves];
     __shared__ int red_i[kK7Waves];
     __shared__ unsigned long long s_best;          // bits of the best score any lane of the workgroup has found so far (>= 0)
@@ -109,8 +106,6 @@ __global__ __launch_bounds__(kK7Threads, W == 1 ? PFZ_K7_OCC : (W == 2 ? 3 : 2))
     __shared__ int s_sweeps[kK7Waves][3][64];     // runs of windows waiting for a lane (see sweep_rounds): item, lengths, symbols
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int mode = MODE >= 0 ? MODE : A.mode, parts = A.parts;      // (MODE >= 0: the scorer a compile-time constant)
-    const bool use_tokens = mode_uses_tokens(mode);
-    const bool use_pres = mode != kTokenSetRatio && mode != kTokenRatio;      // the symbol-presence term of the bound (see bound_of)
 
     for (int p = tid; p < A.n_sym1 * 3 * W; p += kK7Threads) pm[p] = 0ull;
     __syncthreads();
@@ -193,192 +188,20 @@ __global__ __launch_bounds__(kK7Threads, W == 1 ? PFZ_K7_OCC : (W == 2 ? 3 : 2))
             cur0 = __hip_atomic_load(&A.cont_cur[cont_rec], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         const int row = A.rows[r];
-        const int64_t a0 = A.a_off[row];
-        // ---- the from-string's tables, class histogram, tokens
-        if (tid < 4 * kFuzzHistWords) s_cnt[tid] = 0;
-        if (tid < 2) s_pres[tid] = 0u;
-        if (tid == 0) {
-            s_nspace = 0;
-            s_best = cur0;
-        }
-        __syncthreads();
-        for (int v = 0; v < 3; ++v) {
-            const int m = v == 0 ? (int)(A.a_off[row + 1] - a0) : (v == 1 ? A.a_len1[row] : A.a_len2[row]);
-            if (tid == 0) s_la[v] = m;
-            for (int p = tid; p < m; p += kK7Threads) {
-                const uint32_t c = load_unit(A.a_form[v], A.a_width, a0 + p);
-                const int sy = c < A.lut_len ? (int)A.lut[c] : 0;
-                if (sy) {
-                    atomicOr((unsigned long long *)&pm[(sy * 3 + v) * W + (p >> 6)], 1ull << (p & 63));
-                    if (v == 0) {
-                        atomicAdd(&s_cnt[A.cls[sy]], 1);
-                        if (sy == A.space_rank) atomicAdd(&s_nspace, 1);
-                        if (!is_space_cp(c)) atomicOr(&s_pres[(sy & 63) >> 5], 1u << (sy & 31));      // (no whitespace symbol: see k7_pack)
-                    }
-                }
-            }
-        }
-        if (tid == 0) {
-            const int64_t tb = tok_base(a0, row);
-            const int ta = A.a_ntok[row];
-            s_ta = ta;
-            int start = 0;
-            uint64_t sig = 0ull;
-            for (int i = 0; i < ta; ++i) {
-                const int len = A.a_tok_len[tb + i];
-                s_tid[i] = A.a_tok_id[tb + i];
-                s_tlen[i] = len;
-                sig |= fz_sig_bit(s_tid[i]);
-                uint64_t tm[W], sm[W];
-                fz_range_mask<W>(tm, start, start + len);
-                fz_range_mask<W>(sm, start + len, i + 1 < ta ? start + len + 1 : start + len);
-#pragma unroll
-                for (int w = 0; w < W; ++w) {
-                    s_tmask[i * W + w] = tm[w];
-                    s_smask[i * W + w] = sm[w];
-                }
-                start += len + 1;
-            }
-            s_sig[0] = (uint32_t)sig;
-            s_sig[1] = (uint32_t)(sig >> 32);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            const int nt_all = A.a_ntok_all[row];
-            const int extra = (nt_all - 1) - s_nspace;
-            if (extra > 0) s_cnt[A.space_class] += extra;
-            int usum = 0, big = 0;
-            for (int c = 0; c < 4 * kFuzzHistWords; ++c) {
-                usum += s_cnt[c];
-                big |= s_cnt[c] > 255;
-            }
-            for (int d = 0; d < kFuzzHistWords; ++d)
-                s_hist[d] = (uint32_t)s_cnt[4 * d] | (uint32_t)s_cnt[4 * d + 1] << 8 | (uint32_t)s_cnt[4 * d + 2] << 16 | (uint32_t)s_cnt[4 * d + 3] << 24;
-            s_usum = big ? -1 : usum;
-        }
-        __syncthreads();
+        const int64_t a0 = A.a_off[row];          // (held through the unit for the clean-up: reading it again there measured 6 % slower under partial_ratio)
+        // ---- the from-string's tables, class histogram, tokens (k7_row.h; its first barrier covers s_best)
+        if (tid == 0) s_best = cur0;
+        fuzz_row_setup<W>(A, s_row, pm, row, tid);
         FuzzFrom<W> F;
-        F.pm = pm;
-        F.la = {s_la[0], s_la[1], s_la[2]};
-        F.ta = s_ta;
-        F.tid = s_tid;
-        F.tlen = s_tlen;
-        F.tmask = s_tmask;
-        F.smask = s_smask;
-        FuzzSummary sa;
-#pragma unroll
-        for (int v = 0; v < 3; ++v) sa.len[v] = F.la[v];
-        sa.ntok = F.ta;
-#pragma unroll
-        for (int d = 0; d < kFuzzHistWords; ++d) sa.hist[d] = s_hist[d];
-        sa.usum = s_usum;
-        sa.sig = (uint64_t)s_sig[0] | (uint64_t)s_sig[1] << 32;
-        const uint32_t pres_a0 = s_pres[0], pres_a1 = s_pres[1];
-        const int n_pres_a = __popc(pres_a0) + __popc(pres_a1);
+        FuzzRowSide B;
+        fuzz_row_read<W>(s_row, pm, F, B);
         const int skip = A.skip_idx ? A.skip_idx[row] : -1;
-        // choice_left_out(w, skip, up_to) for w >= 0 as ONE unsigned range test (sweep 1 runs it for every pair): the choices
-        // skip_lo .. skip_lo + skip_span are left out -- "equal": skip alone; "up to": 0 .. skip; none (-1): the empty range at -1
-        const int skip_lo = A.skip_up_to && skip >= 0 ? 0 : skip;
-        const unsigned skip_span = (unsigned)(skip - skip_lo);
+        // the choices left out -- "equal": skip alone; "up to": 0 .. skip; none (-1): the empty range at -1
+        B.skip_lo = A.skip_up_to && skip >= 0 ? 0 : skip;
+        B.skip_span = (unsigned)(skip - B.skip_lo);
 
         auto cur_now = [&]() {
             return __longlong_as_double((long long)__hip_atomic_load(&s_best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-        };
-        auto to_of = [&](int slot, const int4 &m) {
-            const int4 rec = A.b_meta3[slot];
-            FuzzTo T;
-            T.sym = {A.b_sym + rec.x, A.b_sym + rec.x + rec.w, A.b_sym + rec.x + 2 * rec.w};
-            T.tag = A.b_tag + rec.y;
-            T.tok_id = A.b_tok_id + rec.z;
-            T.tok_len = A.b_tok_len + rec.z;
-            T.lb = {m.x, m.y, m.z};
-            T.tb = m.w;
-            T.stage = nullptr;
-            T.stage_stride = 0;          // (the scratch columns belong to the window sweeps: sweep_rounds)
-            T.staged = -1;
-            T.n_windows = 0;
-            return T;
-        };
-        // what a sweep reads of one to-string: five 128-bit loads, all issued one group ahead of their use
-        struct Meta {
-            int4 m, m2, m4;
-            uint4 h0, h1;
-            uint2 p;
-        };
-        // (byte offsets in 32 bits: a scalar base + one vector offset per load instead of 64-bit address arithmetic per lane
-        // and array -- the to-side holds at most 2^26 strings, 2^30 B of its widest array)
-        auto load_meta = [&](int g) {
-            const uint32_t off = ((uint32_t)g * 64u + (uint32_t)lane) * 16u;
-            Meta x;
-            x.m = *(const int4 *)((const char *)A.b_meta + off);
-            x.m2 = *(const int4 *)((const char *)A.b_meta2 + off);
-            x.m4 = *(const int4 *)((const char *)A.b_meta4 + off);
-            const uint32_t hoff = ((uint32_t)g * 128u + (uint32_t)lane) * 16u;
-            x.h0 = *(const uint4 *)((const char *)A.b_hist + hoff);
-            x.h1 = *(const uint4 *)((const char *)A.b_hist + hoff + 1024u);
-            x.p = use_pres ? *(const uint2 *)((const char *)A.b_pres + (off >> 1)) : make_uint2(0u, 0u);
-            return x;
-        };
-        // float32 upper bound of the pair (from-string, to-string x) FROM REGISTERS ONLY; valid = a real candidate of this
-        // kernel.  When the token signatures meet, the exact intersection is taken from the first four token ids (nearly
-        // every to-string has no more); `coarse` = the signatures meet but the string has more tokens: the bound assumes
-        // the best, and the pair is looked at again -- with its record -- when it is popped from the queue.
-        auto summary_of = [&](const Meta &x) {
-            FuzzSummary sb;
-            sb.len[0] = x.m.x;
-            sb.len[1] = x.m.y;
-            sb.len[2] = x.m.z;
-            sb.ntok = x.m.w;
-            sb.hist[0] = x.h0.x;
-            sb.hist[1] = x.h0.y;
-            sb.hist[2] = x.h0.z;
-            sb.hist[3] = x.h0.w;
-            sb.hist[4] = x.h1.x;
-            sb.hist[5] = x.h1.y;
-            sb.hist[6] = x.h1.z;
-            sb.hist[7] = x.h1.w;
-            sb.usum = x.m2.z;
-            sb.sig = (uint64_t)(uint32_t)x.m2.x | (uint64_t)(uint32_t)x.m2.y << 32;
-            return sb;
-        };
-        auto bound_of = [&](const Meta &x, bool &valid, bool &coarse) -> float {
-            const int4 m = x.m;
-            valid = x.m2.w >= 0 && (unsigned)(x.m2.w - skip_lo) > skip_span && m.w <= kFuzzMaxTokens;
-            const FuzzSummary sb = summary_of(x);
-            const int uu = fz_common_chars(sa, sb);
-            const bool maybe = use_tokens && (sa.sig & sb.sig) != 0ull;
-            coarse = maybe && m.w > 4;
-            // the common tokens: every lane compares its (up to four) to-token ids with the from-string's, which sit in
-            // scalar registers -- one pass, no branch (disjoint signatures simply find nothing)
-            // (the four compares leave lane masks in scalar registers, or-ed there; one select and one add per from-token carry
-            // both sums -- common tokens << 16 | their characters, a form is shorter than 2^16: 8 vector instructions per token
-            // where the compiler's own rendering of `hit ? .. : ..` took 18, and the kernel is bound by its vector issue rate)
-            int nc = 0, sect_chars = 0;
-            if (use_tokens) {
-                int acc = 0;
-                for (int i = 0; i < F.ta; ++i) {
-                    const int ida = __builtin_amdgcn_readfirstlane(s_tid[i]);          // (absent to-tokens are -1, unknown from-tokens <= -2)
-                    acc += select_if_any_eq(x.m4, ida, s_tlen[i] | 0x10000);
-                }
-                nc = acc >> 16;
-                sect_chars = acc & 0xffff;
-            }
-            // symbols of the one string that the other lacks (fz_presence_miss, the from-side's bits in scalar registers)
-            // (only where it pays: the scorers that sweep windows, WRatio included -- 20k x 20k titles, WRatio 8.38 -> 8.04 ms
-            // with 3.8 % of the pairs scored instead of 6.0 %; token_ratio, which sweeps none, 5.33 -> 5.86 ms for 2.5 %
-            // instead of 2.9 %: there the bits stay out, a wave-uniform choice)
-            int miss_a = 0, miss_b = 0;
-            if (use_pres) {
-                const int pres_common = __popc(pres_a0 & x.p.x) + __popc(pres_a1 & x.p.y);
-                miss_a = n_pres_a - pres_common;
-                miss_b = __popc(x.p.x) + __popc(x.p.y) - pres_common;
-            }
-            // (WRatio reads the token-set bound in one of its two families only -- fz_upper_bound; groups are sorted by length,
-            // so whole waves skip it)
-            const bool wants_tset = mode == kTokenSetRatio || mode == kTokenRatio ||
-                                    (mode == kWRatio && 2 * max(sa.len[0], m.x) < 3 * min(sa.len[0], m.x));
-            const float tset = nc != 0 && wants_tset ? fz_token_set_bound_n(F.la[2], F.ta, m.z, m.w, uu, nc, sect_chars, miss_a, miss_b) : -1.0f;
-            return fz_upper_bound(sa, sb, mode, uu, coarse ? -1 : (nc != 0 ? 1 : 0), coarse ? -1.0f : tset, miss_a, miss_b);
         };
         RowBest best = {-1.0, INT_MAX};
         tick(0);
@@ -459,23 +282,9 @@ __global__ __launch_bounds__(kK7Threads, W == 1 ? PFZ_K7_OCC : (W == 2 ? 3 : 2))
                 const int slot = entry & 0x7fffffff;
                 const int4 m = A.b_meta[slot];
                 orig = A.b_meta2[slot].w;
-                FuzzTo T = to_of(slot, m);
-                bool go = true;
+                FuzzTo T = fuzz_to_of(A, slot, m, nullptr, 0);      // (the scratch columns belong to the window sweeps: sweep_rounds)
                 const double cur = cur_now();
-                if (entry < 0) {
-                    Meta x;
-                    x.m = m;
-                    x.m2 = A.b_meta2[slot];
-                    x.m4 = make_int4(-1, -1, -1, -1);
-                    x.h0 = A.b_hist[((slot >> 6) * 2 + 0) * 64 + (slot & 63)];
-                    x.h1 = A.b_hist[((slot >> 6) * 2 + 1) * 64 + (slot & 63)];
-                    const FuzzSummary sb = summary_of(x);
-                    const int uu = fz_common_chars(sa, sb);
-                    uint32_t ca, cb;
-                    fz_intersect<W>(F, T, ca, cb);
-                    const float ub = fz_upper_bound(sa, sb, mode, uu, ca ? 1 : 0, ca ? fz_token_set_bound<W>(F, ca, m.z, m.w, uu) : -1.0f);
-                    go = !(ub + kBoundSlack < (float)cur);
-                }
+                const bool go = entry >= 0 || !(fuzz_second_bound<W>(A, B, F, T, slot, m, A.b_meta2[slot], mode) + kBoundSlack < (float)cur);
 #ifdef PFZ_K7_PROFILE
                 T.t0 = t_pop;
                 for (int k = 0; k < 6; ++k) T.tk[k] = 0;
@@ -568,9 +377,9 @@ __global__ __launch_bounds__(kK7Threads, W == 1 ? PFZ_K7_OCC : (W == 2 ? 3 : 2))
         uint8_t *const ubc_row = A.ub_cache + (int64_t)(row_region >= 0 ? row_region : my_region) * A.n_groups * 64;
         auto ubc_at = [&](int g) -> uint8_t & { return ubc_row[(uint32_t)g * 64u + (uint32_t)lane]; };
         if (row_region < 0) {
-            auto bound_group = [&](const Meta &x, int g) {
+            auto bound_group = [&](const FuzzMeta &x, int g) {
                 bool valid, coarse;
-                const float ub = bound_of(x, valid, coarse);
+                const float ub = fuzz_bound_of(B, x, mode, valid, coarse);
                 n_bounded += 1;
                 if (!is_cont && valid && !coarse && ub > seed_ub) {       // (a coarse bound says little: not a seed)
                     seed_ub = ub;
@@ -580,11 +389,11 @@ __global__ __launch_bounds__(kK7Threads, W == 1 ? PFZ_K7_OCC : (W == 2 ? 3 : 2))
             };
             // two groups per trip, each record fetched a group ahead into registers of its own (one record handed from trip
             // to trip cost seventeen register moves per group; the last trips re-read a group: harmless)
-            Meta xa = load_meta(min(g_first, A.n_groups - 1));
+            FuzzMeta xa = fuzz_load_meta(A, min(g_first, A.n_groups - 1), lane, mode);
             for (int g = g_first; g < A.n_groups; g += 2 * g_step) {
-                const Meta xb = load_meta(min(g + g_step, A.n_groups - 1));
+                const FuzzMeta xb = fuzz_load_meta(A, min(g + g_step, A.n_groups - 1), lane, mode);
                 bound_group(xa, g);
-                xa = load_meta(min(g + 2 * g_step, A.n_groups - 1));
+                xa = fuzz_load_meta(A, min(g + 2 * g_step, A.n_groups - 1), lane, mode);
                 if (g + g_step < A.n_groups) bound_group(xb, g + g_step);
             }
         }
@@ -733,31 +542,8 @@ __global__ __launch_bounds__(kK7Threads, W == 1 ? PFZ_K7_OCC : (W == 2 ? 3 : 2))
                 atomicMax(&A.phase_ticks[24 + 2 * (int64_t)A.row_slot[r] + 1], (unsigned long long)t_end);
             }
         }
-        if (A.counters) {
-            unsigned long long nb = n_bounded, nsc = n_scored, nst = n_steps;
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) {
-                nb += __shfl_xor(nb, d, 64);
-                nsc += __shfl_xor(nsc, d, 64);
-                nst += __shfl_xor(nst, d, 64);
-            }
-            if (lane == 0) {
-                atomicAdd(&A.counters[0], nb);
-                atomicAdd(&A.counters[1], nsc);
-                atomicAdd(&A.counters[2], nst);
-            }
-        }
-        // clear this from-string's table entries
-        for (int v = 0; v < 3; ++v) {
-            const int m = s_la[v];
-            for (int p = tid; p < m; p += kK7Threads) {
-                const uint32_t c = load_unit(A.a_form[v], A.a_width, a0 + p);
-                const int sy = c < A.lut_len ? (int)A.lut[c] : 0;
-#pragma unroll
-                for (int w = 0; w < W; ++w) pm[(sy * 3 + v) * W + w] = 0ull;
-            }
-        }
-        __syncthreads();
+        fuzz_add_counters(A.counters, n_bounded, n_scored, n_steps, lane);
+        fuzz_row_clear<W>(A, s_row, pm, a0, tid);
     }
     if (A.phase_ticks) {
         __syncthreads();

@@ -39,14 +39,15 @@
 // best is never above its row's, so parts with floors of their own lose nothing.  The choices left out are K7's per-row skip
 // codes (A.skip_idx / A.skip_up_to) as K7's one unsigned range test, not J.self.
 //
-// The set-up of a row, load_meta, summary_of, bound_of and to_of are K7's, restated here: k7_fuzz_kernel's body is left byte for
-// byte as it was (its registers and LDS sit on occupancy steps), so these roughly 150 lines exist twice -- debt, DESIGN.md §8.
+// The set-up of a row, the record of a to-string, both bounds of a pair, to_of and the counters are K7's own: both kernels read
+// them from k7_row.h, so a change of the bound is one edit (and moves every instance: tests/test_kernel_budget_cpu.py).
 //
 // What the fast kernel leaves out takes the general join kernel (k7_general.hip), three regions in all, each pair in exactly one:
 // fast rows x ordinary to-strings (here), general rows (beyond 256 characters / 32 distinct tokens / a 60 KiB table, or all under
 // PFZ_K7_FORCE_GENERAL) x all to-strings, fast rows x the to-strings with more than 32 distinct tokens.
 #pragma once
 #include "k7_device.h"
+#include "k7_row.h"
 #include "k19_sink.h"
 
 #include <algorithm>
@@ -75,18 +76,11 @@ __global__ __launch_bounds__(kK7Threads, W == 1 ? PFZ_K7_OCC : (W == 2 ? 3 : 2))
     // dynamic part: the from-string's match table [symbol][form][word]; the scratch columns [position][lane]
     uint64_t *pm = (uint64_t *)smem_raw;
     unsigned char *s_stage = smem_raw + (size_t)A.n_sym1 * 3 * W * sizeof(uint64_t);
-    __shared__ int s_la[3], s_ta, s_nspace, s_usum;
-    __shared__ int s_tid[kFuzzMaxTokens], s_tlen[kFuzzMaxTokens];
-    __shared__ uint64_t s_tmask[kFuzzMaxTokens * W], s_smask[kFuzzMaxTokens * W];
-    __shared__ int s_cnt[4 * kFuzzHistWords];
-    __shared__ uint32_t s_hist[kFuzzHistWords], s_sig[2];
-    __shared__ uint32_t s_pres[2];
+    __shared__ FuzzRow<W> s_row;                  // the from-string (k7_row.h)
     __shared__ int s_queue[128];
     __shared__ int s_unit;
     const int tid = threadIdx.x, lane = tid & 63;
     const int mode = MODE >= 0 ? MODE : A.mode, parts = A.parts;      // (MODE >= 0: the scorer a compile-time constant)
-    const bool use_tokens = mode_uses_tokens(mode);
-    const bool use_pres = mode != kTokenSetRatio && mode != kTokenRatio;      // the symbol-presence term of the bound (K7: bound_of)
     const double cutoff = J.cutoff;
     constexpr bool kTopn = FuzzSinkTrait<SINK>::topn;
     double cur = cutoff;                            // the floor a pair is bounded and scored against: the cutoff, until a full list raises it (K19)
@@ -104,95 +98,21 @@ __global__ __launch_bounds__(kK7Threads, W == 1 ? PFZ_K7_OCC : (W == 2 ? 3 : 2))
         if (u >= n_units) break;                   // (no unit is ever waited for: past the end, the workgroup leaves)
         const int r = u / parts, part = u - r * parts;
         const int row = A.rows[r];
-        const int64_t a0 = A.a_off[row];
-        // ---- the from-string's tables, class histogram, tokens (K7's set-up)
-        if (tid < 4 * kFuzzHistWords) s_cnt[tid] = 0;
-        if (tid < 2) s_pres[tid] = 0u;
-        if (tid == 0) s_nspace = 0;
-        __syncthreads();
-        for (int v = 0; v < 3; ++v) {
-            const int m = v == 0 ? (int)(A.a_off[row + 1] - a0) : (v == 1 ? A.a_len1[row] : A.a_len2[row]);
-            if (tid == 0) s_la[v] = m;
-            for (int p = tid; p < m; p += kK7Threads) {
-                const uint32_t c = load_unit(A.a_form[v], A.a_width, a0 + p);
-                const int sy = c < A.lut_len ? (int)A.lut[c] : 0;
-                if (sy) {
-                    atomicOr((unsigned long long *)&pm[(sy * 3 + v) * W + (p >> 6)], 1ull << (p & 63));
-                    if (v == 0) {
-                        atomicAdd(&s_cnt[A.cls[sy]], 1);
-                        if (sy == A.space_rank) atomicAdd(&s_nspace, 1);
-                        if (!is_space_cp(c)) atomicOr(&s_pres[(sy & 63) >> 5], 1u << (sy & 31));      // (no whitespace symbol: see k7_pack)
-                    }
-                }
-            }
-        }
-        if (tid == 0) {
-            const int64_t tb = tok_base(a0, row);
-            const int ta = A.a_ntok[row];
-            s_ta = ta;
-            int start = 0;
-            uint64_t sig = 0ull;
-            for (int i = 0; i < ta; ++i) {
-                const int len = A.a_tok_len[tb + i];
-                s_tid[i] = A.a_tok_id[tb + i];
-                s_tlen[i] = len;
-                sig |= fz_sig_bit(s_tid[i]);
-                uint64_t tm[W], sm[W];
-                fz_range_mask<W>(tm, start, start + len);
-                fz_range_mask<W>(sm, start + len, i + 1 < ta ? start + len + 1 : start + len);
-#pragma unroll
-                for (int w = 0; w < W; ++w) {
-                    s_tmask[i * W + w] = tm[w];
-                    s_smask[i * W + w] = sm[w];
-                }
-                start += len + 1;
-            }
-            s_sig[0] = (uint32_t)sig;
-            s_sig[1] = (uint32_t)(sig >> 32);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            const int nt_all = A.a_ntok_all[row];
-            const int extra = (nt_all - 1) - s_nspace;
-            if (extra > 0) s_cnt[A.space_class] += extra;
-            int usum = 0, big = 0;
-            for (int c = 0; c < 4 * kFuzzHistWords; ++c) {
-                usum += s_cnt[c];
-                big |= s_cnt[c] > 255;
-            }
-            for (int d = 0; d < kFuzzHistWords; ++d)
-                s_hist[d] = (uint32_t)s_cnt[4 * d] | (uint32_t)s_cnt[4 * d + 1] << 8 | (uint32_t)s_cnt[4 * d + 2] << 16 | (uint32_t)s_cnt[4 * d + 3] << 24;
-            s_usum = big ? -1 : usum;
-        }
-        __syncthreads();
+        // ---- the from-string's tables, class histogram, tokens (k7_row.h)
+        fuzz_row_setup<W>(A, s_row, pm, row, tid);
         FuzzFrom<W> F;
-        F.pm = pm;
-        F.la = {s_la[0], s_la[1], s_la[2]};
-        F.ta = s_ta;
-        F.tid = s_tid;
-        F.tlen = s_tlen;
-        F.tmask = s_tmask;
-        F.smask = s_smask;
-        FuzzSummary sa;
-#pragma unroll
-        for (int v = 0; v < 3; ++v) sa.len[v] = F.la[v];
-        sa.ntok = F.ta;
-#pragma unroll
-        for (int d = 0; d < kFuzzHistWords; ++d) sa.hist[d] = s_hist[d];
-        sa.usum = s_usum;
-        sa.sig = (uint64_t)s_sig[0] | (uint64_t)s_sig[1] << 32;
-        const uint32_t pres_a0 = s_pres[0], pres_a1 = s_pres[1];
-        const int n_pres_a = __popc(pres_a0) + __popc(pres_a1);
+        FuzzRowSide B;
+        fuzz_row_read<W>(s_row, pm, F, B);
         // the choices left out, as K7's ONE unsigned range test: a self-join leaves out 0 .. row, two lists the empty range at -1
-        int skip_lo = J.self ? 0 : -1;
-        unsigned skip_span = J.self ? (unsigned)row : 0u;
+        B.skip_lo = J.self ? 0 : -1;
+        B.skip_span = J.self ? (unsigned)row : 0u;
         // the unit's list, and the floor back at the cutoff (K19); the range from K7's per-row skip codes -- "equal": skip alone;
         // "up to": 0 .. skip; none (-1): the empty range at -1
         [[maybe_unused]] TopnList list = topn_empty();
         if constexpr (kTopn) {
             const int skip = A.skip_idx ? A.skip_idx[row] : -1;
-            skip_lo = A.skip_up_to && skip >= 0 ? 0 : skip;
-            skip_span = (unsigned)(skip - skip_lo);
+            B.skip_lo = A.skip_up_to && skip >= 0 ? 0 : skip;
+            B.skip_span = (unsigned)(skip - B.skip_lo);
             cur = cutoff;
         }
         // (wave-uniform: every lane reads entry ntop - 1 from its lane)
@@ -203,87 +123,6 @@ __global__ __launch_bounds__(kK7Threads, W == 1 ? PFZ_K7_OCC : (W == 2 ? 3 : 2))
             }
         };
 
-        auto to_of = [&](int slot, const int4 &m) {
-            const int4 rec = A.b_meta3[slot];
-            FuzzTo T;
-            T.sym = {A.b_sym + rec.x, A.b_sym + rec.x + rec.w, A.b_sym + rec.x + 2 * rec.w};
-            T.tag = A.b_tag + rec.y;
-            T.tok_id = A.b_tok_id + rec.z;
-            T.tok_len = A.b_tok_len + rec.z;
-            T.lb = {m.x, m.y, m.z};
-            T.tb = m.w;
-            T.stage = (PFZ_LDS_U16 *)(s_stage + lane * sizeof(uint16_t));      // the lane's column
-            T.stage_stride = 64;
-            T.staged = -1;
-            T.n_windows = 0;
-            return T;
-        };
-        // what the walk reads of one to-string: five 128-bit loads, all issued one group ahead of their use
-        struct Meta {
-            int4 m, m2, m4;
-            uint4 h0, h1;
-            uint2 p;
-        };
-        auto load_meta = [&](int g) {
-            const uint32_t off = ((uint32_t)g * 64u + (uint32_t)lane) * 16u;
-            Meta x;
-            x.m = *(const int4 *)((const char *)A.b_meta + off);
-            x.m2 = *(const int4 *)((const char *)A.b_meta2 + off);
-            x.m4 = *(const int4 *)((const char *)A.b_meta4 + off);
-            const uint32_t hoff = ((uint32_t)g * 128u + (uint32_t)lane) * 16u;
-            x.h0 = *(const uint4 *)((const char *)A.b_hist + hoff);
-            x.h1 = *(const uint4 *)((const char *)A.b_hist + hoff + 1024u);
-            x.p = use_pres ? *(const uint2 *)((const char *)A.b_pres + (off >> 1)) : make_uint2(0u, 0u);
-            return x;
-        };
-        auto summary_of = [&](const Meta &x) {
-            FuzzSummary sb;
-            sb.len[0] = x.m.x;
-            sb.len[1] = x.m.y;
-            sb.len[2] = x.m.z;
-            sb.ntok = x.m.w;
-            sb.hist[0] = x.h0.x;
-            sb.hist[1] = x.h0.y;
-            sb.hist[2] = x.h0.z;
-            sb.hist[3] = x.h0.w;
-            sb.hist[4] = x.h1.x;
-            sb.hist[5] = x.h1.y;
-            sb.hist[6] = x.h1.z;
-            sb.hist[7] = x.h1.w;
-            sb.usum = x.m2.z;
-            sb.sig = (uint64_t)(uint32_t)x.m2.x | (uint64_t)(uint32_t)x.m2.y << 32;
-            return sb;
-        };
-        // float32 upper bound of the pair FROM REGISTERS ONLY (K7's bound_of, word for word); valid = a real candidate of this
-        // kernel; coarse = the signatures meet but the to-string has more than four tokens: bounded again when popped
-        auto bound_of = [&](const Meta &x, bool &valid, bool &coarse) -> float {
-            const int4 m = x.m;
-            valid = x.m2.w >= 0 && (unsigned)(x.m2.w - skip_lo) > skip_span && m.w <= kFuzzMaxTokens;
-            const FuzzSummary sb = summary_of(x);
-            const int uu = fz_common_chars(sa, sb);
-            const bool maybe = use_tokens && (sa.sig & sb.sig) != 0ull;
-            coarse = maybe && m.w > 4;
-            int nc = 0, sect_chars = 0;
-            if (use_tokens) {
-                int acc = 0;
-                for (int i = 0; i < F.ta; ++i) {
-                    const int ida = __builtin_amdgcn_readfirstlane(s_tid[i]);          // (absent to-tokens are -1, unknown from-tokens <= -2)
-                    acc += select_if_any_eq(x.m4, ida, s_tlen[i] | 0x10000);
-                }
-                nc = acc >> 16;
-                sect_chars = acc & 0xffff;
-            }
-            int miss_a = 0, miss_b = 0;
-            if (use_pres) {
-                const int pres_common = __popc(pres_a0 & x.p.x) + __popc(pres_a1 & x.p.y);
-                miss_a = n_pres_a - pres_common;
-                miss_b = __popc(x.p.x) + __popc(x.p.y) - pres_common;
-            }
-            const bool wants_tset = mode == kTokenSetRatio || mode == kTokenRatio ||
-                                    (mode == kWRatio && 2 * max(sa.len[0], m.x) < 3 * min(sa.len[0], m.x));
-            const float tset = nc != 0 && wants_tset ? fz_token_set_bound_n(F.la[2], F.ta, m.z, m.w, uu, nc, sect_chars, miss_a, miss_b) : -1.0f;
-            return fz_upper_bound(sa, sb, mode, uu, coarse ? -1 : (nc != 0 ? 1 : 0), coarse ? -1.0f : tset, miss_a, miss_b);
-        };
         // one batch: up to 64 queued pairs, one per lane -- a coarse entry's refined bound, the score, the sink
         auto score_batch = [&](int entry, bool active) {
             double sc = 0.0;
@@ -295,24 +134,8 @@ __global__ __launch_bounds__(kK7Threads, W == 1 ? PFZ_K7_OCC : (W == 2 ? 3 : 2))
                 const int4 m = A.b_meta[slot];
                 const int4 m2 = A.b_meta2[slot];
                 orig = m2.w;
-                FuzzTo T = to_of(slot, m);
-                bool go = true;
-                if (entry < 0) {
-                    Meta x;
-                    x.m = m;
-                    x.m2 = m2;
-                    x.m4 = make_int4(-1, -1, -1, -1);
-                    x.h0 = A.b_hist[((slot >> 6) * 2 + 0) * 64 + (slot & 63)];
-                    x.h1 = A.b_hist[((slot >> 6) * 2 + 1) * 64 + (slot & 63)];
-                    x.p = make_uint2(0u, 0u);
-                    const FuzzSummary sb = summary_of(x);
-                    const int uu = fz_common_chars(sa, sb);
-                    uint32_t ca, cb;
-                    fz_intersect<W>(F, T, ca, cb);
-                    const float ub = fz_upper_bound(sa, sb, mode, uu, ca ? 1 : 0, ca ? fz_token_set_bound<W>(F, ca, m.z, m.w, uu) : -1.0f);
-                    go = fuzz_join_go(ub, cur);
-                }
-                if (go) {
+                FuzzTo T = fuzz_to_of(A, slot, m, (PFZ_LDS_U16 *)(s_stage + lane * sizeof(uint16_t)), 64);      // (the lane's column)
+                if (entry >= 0 || fuzz_join_go(fuzz_second_bound<W>(A, B, F, T, slot, m, m2, mode), cur)) {
                     sc = fz_score<W, false>(F, T, mode, cur);
                     hit = fuzz_join_hit(sc, cutoff);
                     n_scored += 1;
@@ -329,9 +152,9 @@ __global__ __launch_bounds__(kK7Threads, W == 1 ? PFZ_K7_OCC : (W == 2 ? 3 : 2))
         //      64 pairs wait in the queue (nothing but the bound, a ballot and a push: no barrier, no scoring code), and around it
         //      the ONE place where pairs are scored -- that code, by far the largest part of the kernel, is inlined exactly once.
         int q_head = 0, q_tail = 0;             // wave-uniform; entries [q_head, q_tail) of a ring of 128
-        auto visit = [&](const Meta &x, int g) {
+        auto visit = [&](const FuzzMeta &x, int g) {
             bool valid, coarse;
-            const float ub = bound_of(x, valid, coarse);
+            const float ub = fuzz_bound_of(B, x, mode, valid, coarse);
             n_bounded += valid ? 1u : 0u;
             const bool go = valid && fuzz_join_go(ub, cur);
             const unsigned long long bal = FZ_BALLOT(go);
@@ -341,18 +164,18 @@ __global__ __launch_bounds__(kK7Threads, W == 1 ? PFZ_K7_OCC : (W == 2 ? 3 : 2))
         int g = part;
         // two groups per trip, each record fetched a group ahead into registers of its own (K7's first sweep: a record handed
         // from trip to trip costs seventeen register moves per group; the last trips re-read a group: harmless)
-        Meta xa = load_meta(min(g, A.n_groups - 1));
+        FuzzMeta xa = fuzz_load_meta(A, min(g, A.n_groups - 1), lane, mode);
         for (;;) {
             raise_floor();          // (a bounding trip: the list changes in the batches below only)
             while (g < A.n_groups && q_tail - q_head < 64) {
-                const Meta xb = load_meta(min(g + parts, A.n_groups - 1));
+                const FuzzMeta xb = fuzz_load_meta(A, min(g + parts, A.n_groups - 1), lane, mode);
                 visit(xa, g);
                 g += parts;
                 if (!(g < A.n_groups && q_tail - q_head < 64)) {
                     xa = xb;
                     break;
                 }
-                xa = load_meta(min(g + parts, A.n_groups - 1));
+                xa = fuzz_load_meta(A, min(g + parts, A.n_groups - 1), lane, mode);
                 visit(xb, g);
                 g += parts;
             }
@@ -367,33 +190,9 @@ __global__ __launch_bounds__(kK7Threads, W == 1 ? PFZ_K7_OCC : (W == 2 ? 3 : 2))
             if (last) break;
         }
         if constexpr (kTopn) topn_store(list, sink.ntop, sink.slot(row, part));
-
-        // clear this from-string's table entries
-        for (int v = 0; v < 3; ++v) {
-            const int m = s_la[v];
-            for (int p = tid; p < m; p += kK7Threads) {
-                const uint32_t c = load_unit(A.a_form[v], A.a_width, a0 + p);
-                const int sy = c < A.lut_len ? (int)A.lut[c] : 0;
-#pragma unroll
-                for (int w = 0; w < W; ++w) pm[(sy * 3 + v) * W + w] = 0ull;
-            }
-        }
-        __syncthreads();
+        fuzz_row_clear<W>(A, s_row, pm, A.a_off[row], tid);      // (a_off[row] read again: held through the unit, as K7 holds it, the walk measured slower)
     }
-    if (A.counters) {
-        unsigned long long nb = n_bounded, nsc = n_scored, nst = n_steps;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            nb += __shfl_xor(nb, d, 64);
-            nsc += __shfl_xor(nsc, d, 64);
-            nst += __shfl_xor(nst, d, 64);
-        }
-        if (lane == 0) {
-            atomicAdd(&A.counters[0], nb);
-            atomicAdd(&A.counters[1], nsc);
-            atomicAdd(&A.counters[2], nst);
-        }
-    }
+    fuzz_add_counters(A.counters, n_bounded, n_scored, n_steps, lane);
 }
 
 template <int W, typename SINK>

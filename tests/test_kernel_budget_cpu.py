@@ -45,6 +45,20 @@ def test_k7_longer_classes(kernels):
         assert _one(kernels, f"void pfz::k7_fuzz_kernel<4, {scorer}>(")["vgpr"] <= 256          # 2
 
 
+def test_k7_join_kernels_keep_their_register_classes(kernels):
+    """k7_join_kernel (K18 / K19) shares the row set-up and the bound with k7_fuzz_kernel (k7_row.h): one edit there moves all
+    18 instances -- three word classes x three sinks x (the scorer at run time, WRatio's own) -- and each must stay in the
+    register class its __launch_bounds__ ask for, K7's limits."""
+    seen = 0
+    for words, limit in ((1, 128), (2, 170), (4, 256)):
+        for sink in ("FuzzAppend", "FuzzUnite", "FuzzTopn"):
+            for scorer in ("-1", "0"):
+                k = _one(kernels, f"void pfz::k7_join_kernel<{words}, pfz::{sink}, {scorer}>(")
+                assert k["vgpr"] <= limit, (words, sink, scorer, k)
+                seen += 1
+    assert seen == 18 and sum(k.startswith("void pfz::k7_join_kernel<") for k in kernels) == 18
+
+
 def test_k3_headline_kernel_keeps_18_workgroups_per_cu(kernels):
     """2048 accumulator columns + the 96-key candidate buffer: 8960 B; one more 256-B step is a workgroup per CU less."""
     k = _one(kernels, "void pfz::k3_cossim_topn_kernel<2048, 96, false>(")
