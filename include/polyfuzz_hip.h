@@ -441,6 +441,42 @@ int pfz_jaro_argmax_dev(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz
 int pfz_jaro_matrix_host(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings, int32_t scorer,
                          int64_t from_begin, int64_t from_end, double *out_matrix);
 
+/* ---- K20: all pairs at or above a Jaro / Jaro-Winkler score, and their components ------
+ * The threshold form of K8, the textbook rule of record linkage ("Jaro-Winkler >= 0.9"): every pair (from i, to j) with
+ * w(i, j) >= min_similarity, w as defined for K8 (scorer = 0: Jaro, 1: Jaro-Winkler) and computed by the very function
+ * pfz_jaro_argmax / pfz_jaro_matrix_host score with -- the same bits --, float64 against float64: equal is a hit, below is a
+ * miss.  An empty string on either side scores 0.0: a hit iff min_similarity == 0.
+ * pfz_jaro_join: the contract is pfz_lev_join's, word for word, without the distance array: to_strings == NULL or the
+ * from-list's own handle is the self-join (every unordered pair i < j once, as row i, to-index j, scored as w(i, j) = w(j, i);
+ * never (i, i); equal strings at different positions are pairs); the output is CSR over the from-rows in host buffers, the
+ * to-index ascending within a row, out_sim[p] = w; the same call gives the same bytes every time; *out_total is always the
+ * exact number of hits, and when it exceeds `capacity` the call returns PFZ_OK, has written NONE of the three output arrays
+ * (the device never writes a hit past the capacity either) and is to be repeated with capacity >= *out_total.
+ * out_counters: NULL, or int64[4] of work counts -- [0] pairs inside the length window (pairs of the call, in a self-join the
+ * unordered ones, whose lengths alone do not put them below min_similarity), [1] those of them alive after the matching sweep
+ * (not abandoned in it, their number of matches not below what min_similarity needs), [2] those of them whose float64 score
+ * was computed, [3] to-characters the matching sweep walked for lanes still alive.
+ * Exact: a pair is left out of the window, abandoned or left unscored only where K8's float32 upper bound of its score -- with
+ * every character of the shorter string matched, or with the matches it has plus the to-characters still to come, none
+ * transposed and the longest common prefix it can have, or with its own matches, prefix and transpositions -- plus the bound's
+ * margin is below min_similarity (csrc/k8_core.h).
+ * From-strings of up to 64 characters against to-strings of up to 256 run in registers, all other pairs (and alphabets whose
+ * match table exceeds 60 KiB) in a general -- slow -- kernel that scores every pair of the window to its end.  The to-side
+ * preparation is pfz_indel_*'s, cached on the to-list's handle.
+ * Limits (PFZ_ERR_UNSUPPORTED beyond): K8's on lists and strings; a capacity of at most 2^32 - 1 hits.  scorer outside
+ * {0, 1}, a NaN min_similarity or one outside [0, 1], capacity < 0: PFZ_ERR_INVALID.  Blocks. */
+int pfz_jaro_join(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings, int32_t scorer,
+                  double min_similarity, int64_t capacity, int64_t *out_row_ptr, int32_t *out_idx, double *out_sim,
+                  int64_t *out_total, int64_t *out_counters);
+/* pfz_jaro_components: pfz_lev_components's contract under these scores -- out_label[i] = the smallest position in i's
+ * component of the graph of pfz_jaro_join's self-join, found by the same walk, the pairs united on the device (csrc/k12_core.h)
+ * and never stored: O(n) device memory, no capacity, no repeat; deterministic.  *out_pairs == pfz_jaro_join's *out_total for
+ * the same arguments, *out_components counts singletons too; out_counters: NULL or int64[4] as above.  Equal non-empty strings
+ * always share a component (they score 1.0); empty ones score 0.0 and stay apart above min_similarity = 0.  strings->n == 0:
+ * PFZ_OK, *out_pairs = *out_components = 0, nothing else is written.  Errors as pfz_jaro_join's.  Blocks. */
+int pfz_jaro_components(pfz_ctx *ctx, const pfz_strings *strings, int32_t scorer, double min_similarity, int32_t *out_label,
+                        int64_t *out_pairs, int64_t *out_components, int64_t *out_counters);
+
 /* ---- K9: all-pairs Levenshtein / OSA similarity + row arg-max -----------------
  * Replaces the hot loop of EditDistance._calculate_edit_distance (reference
  * polyfuzz/models/_distance.py:89-102) with the `scorer` argument (_distance.py:32) set to rapidfuzz's

@@ -96,6 +96,8 @@ SIGNATURES = {
     "pfz_jaro_argmax": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "pfz_jaro_argmax_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp]),
     "pfz_jaro_matrix_host": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_vp]),
+    "pfz_jaro_join": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_f64, c_i64, c_vp, c_vp, c_vp, P(c_i64), c_vp]),
+    "pfz_jaro_components": (ctypes.c_int, [c_vp, c_vp, c_i32, c_f64, c_vp, P(c_i64), P(c_i64), c_vp]),
     "pfz_lev_argmax": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "pfz_lev_argmax_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp]),
     "pfz_lev_topn": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp]),
@@ -1322,6 +1324,33 @@ def fuzz_topn(ctx, from_dev, to_dev, scorer, ntop, skip_idx=None, score_cutoff=0
     check(ctx.lib.pfz_fuzz_topn(ctx.h, from_dev.h, to_dev.h, FUZZ_SCORERS[scorer], _ptr(skip_idx), int(begin), int(end), int(ntop),
                                 float(score_cutoff), _ptr(idx), _ptr(score), _ptr(work)))
     return (idx, score, dict(zip(FUZZ_JOIN_COUNTERS, (int(w) for w in work)))) if counters else (idx, score)
+
+
+# ---- K20: the threshold join of K8's scorers and its components ----------------------------------------------------------
+
+JARO_JOIN_COUNTERS = ("pairs_in_window", "pairs_alive_after_sweep1", "pairs_scored", "steps")      # pfz_jaro_join's out_counters, in order
+
+
+def jaro_join(ctx, from_dev, to_dev, scorer, min_similarity, capacity=None, counters=False):
+    """K20: every pair whose `scorer` score (a name of JARO_SCORERS) -- jaro_matrix's float64, bit for bit -- is >= min_similarity
+    (float64 against float64: equal is a hit), as CSR over the from-rows: (row_ptr int64[n + 1], to-index int32[hits] ascending
+    within a row, score float64[hits]).  to_dev None (or from_dev itself): the self-join, every unordered pair once as (i, j),
+    i < j.  capacity and the ONE repeat as in lev_join; counters=True appends a dict of JARO_JOIN_COUNTERS (the last call's)."""
+    to_h = None if to_dev is None else to_dev.h
+    row_ptr, hits, _, work = _join_call(
+        from_dev.n, capacity, (np.int32, np.float64), JARO_JOIN_COUNTERS, counters,
+        lambda cap, ptr, hit, total, wk: ctx.lib.pfz_jaro_join(ctx.h, from_dev.h, to_h, JARO_SCORERS[scorer], float(min_similarity), cap, ptr,
+                                                               *hit, total, wk))
+    return (row_ptr,) + hits + ((work,) if counters else ())
+
+
+def jaro_components(ctx, dev, scorer, min_similarity, counters=False):
+    """K20: the connected components of "score >= min_similarity" over the list `dev` (the pairs of jaro_join's self-join, united
+    on the device, never stored) -- (label int32[n], pairs, components): label[i] is the smallest position in i's component,
+    pairs the number of hits (jaro_join's total), components the number of components, singletons included.  counters=True
+    appends a dict of JARO_JOIN_COUNTERS."""
+    return _components_call(dev.n, JARO_JOIN_COUNTERS, counters, lambda label, pairs, components, wk: ctx.lib.pfz_jaro_components(
+        ctx.h, dev.h, JARO_SCORERS[scorer], float(min_similarity), label, pairs, components, wk))
 
 
 # ---- K15: the sparse-cosine threshold join and its components --------------------------------------------------------

@@ -1,5 +1,6 @@
 // What the edit-distance kernels on K4's to-side plan have in common -- K8 (k8_jaro.hip), K9 (k9_levenshtein.hip), K10
-// (k10_pairs.hip), K11 (k11_join.hip), K12 (k12_components.hip), K13 (k13_indel_join.hip) -- each thing once:
+// (k10_pairs.hip), K11 (k11_join.hip), K12 (k12_components.hip), K13 (k13_indel_join.hip), K20 (k20_jaro_join.hip: the view, the
+// table, the ownership rule, the row classes and their launches) -- each thing once:
 //   the view      FromView (the from-strings and the plan's code unit -> symbol table) and EditView (+ the plan's packed groups),
 //                 which every argument block begins with, filled by from_view() / edit_view();
 //   the table     the symbol look-up, the LDS OR, and the set / clear of the workgroup's match table in its register form (one

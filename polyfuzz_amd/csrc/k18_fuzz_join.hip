@@ -37,6 +37,35 @@ __global__ __launch_bounds__(256) void k18_unpack(const uint64_t *__restrict__ k
     rows_fill(p > 0 ? (int64_t)fuzz_key_row(keys[p - 1]) : -1, (int64_t)fuzz_key_row(keys[p]), p, total, n_from, row_ptr);
 }
 
+// behind the walk of a join that appended through FuzzAppend (here and K20, k20_jaro_join.hip): pfz_internal.h has the contract
+int score_join_tail(pfz_ctx *ctx, const char *scope, const uint64_t *d_keys, const uint32_t *d_val, const double *d_score, int64_t total,
+                    int64_t n_from, int64_t *out_row_ptr, int32_t *out_idx, double *out_score)
+{
+    if (total == 0) {
+        for (int64_t r = 0; r <= n_from; ++r) out_row_ptr[r] = 0;
+        return PFZ_OK;
+    }
+    DevBuf d_skeys, d_svals, d_ptr, d_idx, d_out;
+    {
+        ProfScope ps(ctx, scope);
+        const size_t cap = (size_t)sort_codes_capacity(total);
+        PFZ_TRY(d_skeys.alloc(ctx, cap * sizeof(uint64_t)));
+        PFZ_TRY(d_svals.alloc(ctx, cap * sizeof(uint32_t)));
+        PFZ_TRY(sort_pairs_u64(ctx, d_keys, d_val, d_skeys.as<uint64_t>(), d_svals.as<uint32_t>(), total));
+        PFZ_TRY(d_ptr.alloc(ctx, (size_t)(n_from + 1) * sizeof(int64_t)));
+        PFZ_TRY(d_idx.alloc(ctx, (size_t)total * sizeof(int32_t)));
+        PFZ_TRY(d_out.alloc(ctx, (size_t)total * sizeof(double)));
+        hipLaunchKernelGGL(k18_unpack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, d_skeys.as<uint64_t>(),
+                           d_svals.as<uint32_t>(), d_score, total, n_from, d_ptr.as<int64_t>(), d_idx.as<int32_t>(), d_out.as<double>());
+        PFZ_HIP(hipGetLastError());
+    }
+    PFZ_TRY(copy_d2h(ctx, out_row_ptr, d_ptr.p, (size_t)(n_from + 1) * sizeof(int64_t)));
+    PFZ_TRY(copy_d2h(ctx, out_idx, d_idx.p, (size_t)total * sizeof(int32_t)));
+    PFZ_TRY(copy_d2h(ctx, out_score, d_out.p, (size_t)total * sizeof(double)));
+    PFZ_HIP(hipStreamSynchronize(ctx->stream));
+    return PFZ_OK;
+}
+
 static int fuzz_join_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, bool self, int32_t scorer, double cutoff,
                          int64_t capacity, int64_t *out_row_ptr, int32_t *out_idx, double *out_score, int64_t *out_total,
                          int64_t *out_counters)
@@ -78,30 +107,8 @@ static int fuzz_join_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *
     if (out_counters)
         for (int k = 0; k < 3; ++k) out_counters[k] = (int64_t)state[k + 1];
     if (total > capacity) return PFZ_OK;       // the caller's buffers stay as they are: it repeats the call with room for `total`
-    if (total == 0) {
-        for (int64_t r = 0; r <= n_from; ++r) out_row_ptr[r] = 0;
-        return PFZ_OK;
-    }
-    DevBuf d_skeys, d_svals, d_ptr, d_idx, d_out;
-    {
-        ProfScope ps(ctx, "k18_sort_unpack");
-        const size_t cap = (size_t)sort_codes_capacity(total);
-        PFZ_TRY(d_skeys.alloc(ctx, cap * sizeof(uint64_t)));
-        PFZ_TRY(d_svals.alloc(ctx, cap * sizeof(uint32_t)));
-        PFZ_TRY(sort_pairs_u64(ctx, d_keys.as<uint64_t>(), d_val.as<uint32_t>(), d_skeys.as<uint64_t>(), d_svals.as<uint32_t>(), total));
-        PFZ_TRY(d_ptr.alloc(ctx, (size_t)(n_from + 1) * sizeof(int64_t)));
-        PFZ_TRY(d_idx.alloc(ctx, (size_t)total * sizeof(int32_t)));
-        PFZ_TRY(d_out.alloc(ctx, (size_t)total * sizeof(double)));
-        hipLaunchKernelGGL(k18_unpack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, d_skeys.as<uint64_t>(),
-                           d_svals.as<uint32_t>(), d_score.as<double>(), total, n_from, d_ptr.as<int64_t>(), d_idx.as<int32_t>(),
-                           d_out.as<double>());
-        PFZ_HIP(hipGetLastError());
-    }
-    PFZ_TRY(copy_d2h(ctx, out_row_ptr, d_ptr.p, (size_t)(n_from + 1) * sizeof(int64_t)));
-    PFZ_TRY(copy_d2h(ctx, out_idx, d_idx.p, (size_t)total * sizeof(int32_t)));
-    PFZ_TRY(copy_d2h(ctx, out_score, d_out.p, (size_t)total * sizeof(double)));
-    PFZ_HIP(hipStreamSynchronize(ctx->stream));
-    return PFZ_OK;
+    return score_join_tail(ctx, "k18_sort_unpack", d_keys.as<uint64_t>(), d_val.as<uint32_t>(), d_score.as<double>(), total, n_from,
+                           out_row_ptr, out_idx, out_score);
 }
 
 static int fuzz_comp_run(pfz_ctx *ctx, const pfz_strings *F, int32_t scorer, double cutoff, int32_t *out_label, int64_t *out_pairs,

@@ -1,6 +1,7 @@
 // K8's per-pair logic: the greedy Jaro matching as bit operations on one 32- or 64-bit word per string, and the float64 score.
-// Plain integer C++ (and one float64 formula), shared by the HIP kernels (k8_jaro.hip) and a host program that checks it
-// against the definition on the CPU (tests/k8_core_host.cpp).
+// Plain integer C++ (and one float64 formula), shared by the HIP kernels (k8_jaro.hip; k20_jaro_join.hip, the threshold form, whose
+// bounds against a fixed t are at the end of this file) and the host programs that check it against the definition on the CPU
+// (tests/k8_core_host.cpp, tests/k20_core_host.cpp).
 //
 // The definition (jellyfish's jaro_similarity / jaro_winkler_similarity, default arguments, on code points):
 //   r = max(max(la, lb) / 2 - 1, 0);  the from-characters i in order take the first unflagged j in [i - r, i + r] with
@@ -98,6 +99,92 @@ K8_HD float jaro_bound(int m, float inv_la, float inv_lb, float last, int prefix
 {
     const float ub = ((float)m * inv_la + (float)m * inv_lb + last) * (1.0f / 3.0f);
     return winkler && ub > 0.7f - K8_BOUND_MARGIN ? ub + (float)prefix * 0.1f * (1.0f - ub) : ub;
+}
+
+// ---- against a fixed threshold t (K20, k20_jaro_join.hip) ---------------------------------------------------------------------
+// A pair is a hit iff jaro_score(...) >= t, float64 against float64, equal kept.  Everything below only DISMISSES pairs, and
+// only where that comparison is false: the float32 bound + K8_BOUND_MARGIN is >= the float64 score, and the threshold it is held
+// against is t rounded to float32 (a relative 6e-8, far inside the margin).  Each function grows (weakly) with m, with `last` and
+// with the prefix, whatever the roundings: every operation in it is a correctly rounded monotone one.
+// tests/k20_core_host.cpp walks all of it exhaustively against jaro_score.
+
+// can a pair with m matches reach t?  false only where its score is < t.  m = 0 scores 0.0, a hit iff t == 0 -- asked first, so
+// that the 0 * inf of an empty string never reaches a comparison
+K8_HD bool jaro_reaches(int m, float inv_la, float inv_lb, float last, int prefix, int winkler, float t)
+{
+    if (m <= 0) return t <= 0.0f;
+    return jaro_bound(m, inv_la, inv_lb, last, prefix, winkler) + K8_BOUND_MARGIN >= t;
+}
+
+K8_HD int jaro_min3(int a, int b, int c) { return a < b ? (a < c ? a : c) : (b < c ? b : c); }
+
+// the length bound: every character of the shorter string matched, none transposed, the longest prefix the lengths allow.  For one
+// la it rises with lb up to lb = la (where it is 1.0) and falls behind it: the admissible lb are one run around la.  The
+// reciprocals are IEEE divisions here, on the device too: the run K20's set-up launch finds is the one the host finds.
+K8_HD bool jaro_len_ok(int la, int lb, float t, int winkler)
+{
+    const int mn = la < lb ? la : lb;
+    if (mn <= 0) return t <= 0.0f;
+    return jaro_reaches(mn, 1.0f / (float)la, 1.0f / (float)lb, 1.0f, jaro_min3(4, la, lb), winkler, t);
+}
+
+// the run [*lo, *hi] of to-lengths lb <= lb_max a from-string of la characters can have a hit at (empty: *lo > *hi), by bisection
+// over jaro_len_ok on either side of la
+K8_HD void jaro_len_run(int la, int lb_max, float t, int winkler, int *lo, int *hi)
+{
+    if (t <= 0.0f) {
+        *lo = 0;
+        *hi = lb_max;
+        return;
+    }
+    if (la <= 0) {              // (an empty string scores 0.0 against everything)
+        *lo = 1;
+        *hi = 0;
+        return;
+    }
+    int a = 1, b = la;          // the smallest admissible lb: la itself is one
+    while (a < b) {
+        const int mid = a + (b - a) / 2;
+        if (jaro_len_ok(la, mid, t, winkler)) b = mid;
+        else a = mid + 1;
+    }
+    *lo = a;
+    a = la;                     // the largest: bisection over [la, lb_max]
+    b = lb_max > la ? lb_max : la;
+    while (a < b) {
+        const int mid = a + (b - a + 1) / 2;
+        if (jaro_len_ok(la, mid, t, winkler)) a = mid;
+        else b = mid - 1;
+    }
+    *hi = a;
+}
+
+// the fewest matches with which a pair of these lengths can still reach t (min(la, lb) + 1: with none): the bound with no
+// transposition and the longest prefix the lengths allow, evaluated around a guess from its real-number form
+K8_HD int jaro_m_need(int la, int lb, float inv_la, float inv_lb, float t, int winkler)
+{
+    const int mn = la < lb ? la : lb;
+    if (t <= 0.0f) return 0;
+    if (mn <= 0) return 1;
+    const int prefix = jaro_min3(4, la, lb);
+    // ub = (m (1/la + 1/lb) + 1) / 3 >= u, u the threshold below Winkler's step where the step can apply
+    float u = t;
+    if (winkler) {
+        const float v = (t - 0.1f * (float)prefix) / (1.0f - 0.1f * (float)prefix);
+        u = v > 0.7f ? v : (t < 0.7f ? t : 0.7f);
+    }
+    const float guess = (3.0f * u - 1.0f) / (inv_la + inv_lb);
+    int m = guess > 0.0f ? (guess < (float)mn ? (int)guess : mn) : 0;
+    while (m > 0 && jaro_reaches(m - 1, inv_la, inv_lb, 1.0f, prefix, winkler, t)) --m;
+    while (m <= mn && !jaro_reaches(m, inv_la, inv_lb, 1.0f, prefix, winkler, t)) ++m;
+    return m;
+}
+
+// mid-sweep: `flagged` matches so far, `remaining` to-characters still to come, each at most one more match
+K8_HD bool jaro_dead(int la, int flagged, int remaining, int m_need)
+{
+    const int most = flagged + remaining;
+    return (most < la ? most : la) < m_need;
 }
 
 }  // namespace pfz

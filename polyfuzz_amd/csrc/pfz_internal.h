@@ -404,4 +404,11 @@ int join_unpack(pfz_ctx *ctx, const uint64_t *d_skeys, int64_t total, int64_t n_
 int join_download(pfz_ctx *ctx, const DevBuf &d_ptr, const DevBuf &d_idx, const uint32_t *d_svals, int64_t total, int64_t n_from,
                   int64_t *out_row_ptr, int32_t *out_idx, float *out_sim);
 
+// The tail of the threshold joins that append (key = row << 32 | col, float64 score, position) triples (k18_sink.h FuzzAppend: K18,
+// K20): the keys sorted with the positions as payload, unpacked into CSR over n_from rows with the scores gathered through the
+// payload, and downloaded into the caller's host arrays; total == 0 zeroes the row pointers.  `scope` is the profiling scope of the
+// sort and the unpack.  Blocks (k18_fuzz_join.hip).
+int score_join_tail(pfz_ctx *ctx, const char *scope, const uint64_t *d_keys, const uint32_t *d_val, const double *d_score, int64_t total,
+                    int64_t n_from, int64_t *out_row_ptr, int32_t *out_idx, double *out_score);
+
 }  // namespace pfz

@@ -5,5 +5,6 @@ from ._distance import EditDistance
 from ._rapidfuzz import RapidFuzz
 from ._embeddings import Embeddings
 from ._blocked import BlockedEditDistance
+from ._jaro import JaroWinkler
 
-__all__ = ["BaseMatcher", "cosine_similarity", "TFIDF", "EditDistance", "RapidFuzz", "Embeddings", "BlockedEditDistance"]
+__all__ = ["BaseMatcher", "cosine_similarity", "TFIDF", "EditDistance", "RapidFuzz", "Embeddings", "BlockedEditDistance", "JaroWinkler"]
