@@ -476,6 +476,30 @@ int pfz_jaro_join(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strin
  * PFZ_OK, *out_pairs = *out_components = 0, nothing else is written.  Errors as pfz_jaro_join's.  Blocks. */
 int pfz_jaro_components(pfz_ctx *ctx, const pfz_strings *strings, int32_t scorer, double min_similarity, int32_t *out_label,
                         int64_t *out_pairs, int64_t *out_components, int64_t *out_counters);
+/* K21: the ntop best choices of every from-string of rows [from_begin, from_end) under Jaro (scorer = 0) or Jaro-Winkler
+ * (scorer = 1) -- rapidfuzz.process.extract(query, choices, scorer=JaroWinkler.similarity, limit=ntop, score_cutoff=c), where the
+ * reference's loop (_distance.py:89-102) keeps the one np.argmax.  Per row: the choices not left out (skip_idx: pfz_jaro_argmax's
+ * codes -- >= 0 one choice, <= -2 every choice up to -2 - code, -1 none) whose score -- exactly the float64 pfz_jaro_argmax /
+ * pfz_jaro_matrix_host compute for the pair -- is >= score_cutoff (a number in [0, 1]; equal is kept), in the order
+ * np.argsort(-scores, kind="stable")[:ntop]: score descending, equal scores by ascending to-index.  Column 0 at score_cutoff = 0
+ * is pfz_jaro_argmax's result.  out_idx / out_score: host buffers of (from_end - from_begin) * ntop entries, row-major; the slots
+ * beyond the choices a row has (ntop may exceed the to-list) carry -1 / 0.0.  An empty row range writes nothing; an empty
+ * to-list gives rows of -1 / 0.0; neither launches a kernel.
+ * out_counters: NULL, or uint64[4] of work counts -- [0] pairs whose matching sweep began (a real to-string in a group that was
+ * not skipped), [1] those alive after it, [2] those whose float64 score was computed, [3] to-characters the matching sweep
+ * walked for lanes still alive.  The counters depend on the order the waves run in; the result does not.
+ * Exact: the walk is pfz_jaro_join's with the floor moving -- a pair is skipped, abandoned or left unscored only where K8's
+ * float32 upper bound of its score plus the bound's margin is below the floor F = max(score_cutoff, the score of the ntop-th
+ * best choice a wave of the row's workgroup holds), so a tie with the ntop-th best is still scored and placed by its index
+ * (csrc/k8_core.h, csrc/k21_jaro_topn.hip, csrc/topn_wave.h).  From-strings of up to 64 characters against to-strings of up to 256
+ * run in registers, all other pairs (and alphabets whose match table exceeds 60 KiB) in a general -- slow -- kernel that scores
+ * every pair.
+ * Argument checks: a NULL handle or output, scorer outside {0, 1}, a row range outside the from-list, ntop < 1, a NaN
+ * score_cutoff or one outside [0, 1], skip_idx mixing both code forms: PFZ_ERR_INVALID.  ntop > 64 (one list entry per lane of
+ * a wave), K8's list limits: PFZ_ERR_UNSUPPORTED.  Blocks. */
+int pfz_jaro_topn(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strings *to_strings, int32_t scorer, const int32_t *skip_idx,
+                  int64_t from_begin, int64_t from_end, int32_t ntop, double score_cutoff, int32_t *out_idx, double *out_score,
+                  uint64_t *out_counters);
 
 /* ---- K9: all-pairs Levenshtein / OSA similarity + row arg-max -----------------
  * Replaces the hot loop of EditDistance._calculate_edit_distance (reference

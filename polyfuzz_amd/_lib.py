@@ -98,6 +98,7 @@ SIGNATURES = {
     "pfz_jaro_matrix_host": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_vp]),
     "pfz_jaro_join": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_f64, c_i64, c_vp, c_vp, c_vp, P(c_i64), c_vp]),
     "pfz_jaro_components": (ctypes.c_int, [c_vp, c_vp, c_i32, c_f64, c_vp, P(c_i64), P(c_i64), c_vp]),
+    "pfz_jaro_topn": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_i32, c_f64, c_vp, c_vp, c_vp]),
     "pfz_lev_argmax": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "pfz_lev_argmax_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp]),
     "pfz_lev_topn": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp]),
@@ -1351,6 +1352,29 @@ def jaro_components(ctx, dev, scorer, min_similarity, counters=False):
     appends a dict of JARO_JOIN_COUNTERS."""
     return _components_call(dev.n, JARO_JOIN_COUNTERS, counters, lambda label, pairs, components, wk: ctx.lib.pfz_jaro_components(
         ctx.h, dev.h, JARO_SCORERS[scorer], float(min_similarity), label, pairs, components, wk))
+
+
+# ---- K21: the n best choices under K8's scorers ----------------------------------------------------------------------------
+
+JARO_TOPN_COUNTERS = ("pairs_walked", "pairs_alive_after_sweep1", "pairs_scored", "steps")      # pfz_jaro_topn's out_counters, in order
+
+
+def jaro_topn(ctx, from_dev, to_dev, scorer, ntop, skip_idx=None, score_cutoff=0.0, begin=0, end=None, counters=False):
+    """K21: the ntop best choices of from-rows [begin, end) under the K8 scorer `scorer` (a name of JARO_SCORERS) --
+    rapidfuzz.process.extract(..., limit=ntop, score_cutoff=score_cutoff): (index int32[n, ntop], score float64[n, ntop]) in the
+    order (score descending, to-index ascending) over the choices not left out (skip_idx: jaro_argmax's codes) whose score --
+    jaro_matrix's float64 on the 0..1 scale, bit for bit -- is >= score_cutoff (equal is kept); -1 / 0.0 beyond the choices a row
+    has.  Column 0 at score_cutoff 0 is jaro_argmax's answer.  ntop <= 64 (PfzUnsupported beyond).  counters=True appends a dict
+    of JARO_TOPN_COUNTERS."""
+    end = from_dev.n if end is None else end
+    n = end - begin
+    idx = np.empty((n, max(int(ntop), 0)), np.int32)           # (ntop < 1 is the library's to refuse)
+    score = np.empty((n, max(int(ntop), 0)), np.float64)
+    skip_idx = _skip_array(skip_idx, from_dev.n)
+    work = np.zeros(len(JARO_TOPN_COUNTERS), np.uint64) if counters else None
+    check(ctx.lib.pfz_jaro_topn(ctx.h, from_dev.h, to_dev.h, JARO_SCORERS[scorer], _ptr(skip_idx), int(begin), int(end), int(ntop),
+                                float(score_cutoff), _ptr(idx), _ptr(score), _ptr(work)))
+    return (idx, score, dict(zip(JARO_TOPN_COUNTERS, (int(w) for w in work)))) if counters else (idx, score)
 
 
 # ---- K15: the sparse-cosine threshold join and its components --------------------------------------------------------

@@ -1,6 +1,6 @@
 // K8's per-pair logic: the greedy Jaro matching as bit operations on one 32- or 64-bit word per string, and the float64 score.
 // Plain integer C++ (and one float64 formula), shared by the HIP kernels (k8_jaro.hip; k20_jaro_join.hip, the threshold form, whose
-// bounds against a fixed t are at the end of this file) and the host programs that check it against the definition on the CPU
+// bounds against a fixed t are at the end of this file; k21_jaro_topn.hip, which holds them against a floor that rises) and the host programs that check it against the definition on the CPU
 // (tests/k8_core_host.cpp, tests/k20_core_host.cpp).
 //
 // The definition (jellyfish's jaro_similarity / jaro_winkler_similarity, default arguments, on code points):
@@ -101,7 +101,7 @@ K8_HD float jaro_bound(int m, float inv_la, float inv_lb, float last, int prefix
     return winkler && ub > 0.7f - K8_BOUND_MARGIN ? ub + (float)prefix * 0.1f * (1.0f - ub) : ub;
 }
 
-// ---- against a fixed threshold t (K20, k20_jaro_join.hip) ---------------------------------------------------------------------
+// ---- against a threshold t (K20, k20_jaro_join.hip: fixed; K21, k21_jaro_topn.hip: the row's floor)  ---------------------------
 // A pair is a hit iff jaro_score(...) >= t, float64 against float64, equal kept.  Everything below only DISMISSES pairs, and
 // only where that comparison is false: the float32 bound + K8_BOUND_MARGIN is >= the float64 score, and the threshold it is held
 // against is t rounded to float32 (a relative 6e-8, far inside the margin).  Each function grows (weakly) with m, with `last` and

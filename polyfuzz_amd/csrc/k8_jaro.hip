@@ -26,6 +26,7 @@
 // Bound: integer VALU + LDS look-ups, two sweeps per pair where K4 has one (measured beside K4).
 #include "edit_walk.h"
 #include "k8_core.h"
+#include "k8_launch.h"
 
 #include <algorithm>
 #include <limits.h>
@@ -258,31 +259,11 @@ static int jaro_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, in
     PFZ_TRY(indel_plan_get(ctx, T, &pl));
     const int64_t n_to = T->n;
 
-    // The register kernel's share, while the match table fits 60 KiB of LDS: from-strings of <= 32 characters against the
-    // groups whose to-strings all have <= 32 in 32-bit words; those from-strings against the groups of up to 256, and the
-    // from-strings of 33 .. 64 characters against all groups of up to 256, in 64-bit words (four for a to-string's flags).
-    // The groups are sorted by length: the first g32 / g256 of them qualify.
-    const bool lds_fits = lds_table_fits(pl);
-    const int32_t n_groups = (int32_t)pl->n_groups;
-    auto whole_groups_up_to = [&](int64_t len) {
-        int64_t n = 0;
-        for (int64_t j = 0; j < n_to; ++j) n += T->h_off[(size_t)j + 1] - T->h_off[(size_t)j] <= len;
-        return !lds_fits ? 0 : (n == n_to ? n_groups : (int32_t)(n / 64));
-    };
-    const int32_t g32 = whole_groups_up_to(32), g256 = whole_groups_up_to(256);
-    std::vector<int32_t> rows_reg, rows_64, rows_long;      // rows_reg: <= 32 characters first, then 33 .. 64
-    int64_t longest = 1;
-    for (int64_t i = begin; i < end; ++i) {
-        const int64_t la = F->h_off[(size_t)i + 1] - F->h_off[(size_t)i];
-        if (la <= 32 && g256 > 0) rows_reg.push_back((int32_t)i);
-        else if (la <= 64 && g256 > 0) rows_64.push_back((int32_t)i);
-        else {
-            rows_long.push_back((int32_t)i);
-            longest = std::max(longest, la);
-        }
-    }
-    const size_t n32 = rows_reg.size();
-    rows_reg.insert(rows_reg.end(), rows_64.begin(), rows_64.end());
+    // which rows the register kernels serve, against which groups, in how many parts: k8_launch.h
+    const JaroPlan plan = jaro_plan(ctx, F, T, pl, begin, end);
+    const std::vector<int32_t> &rows_reg = plan.rows_reg, &rows_long = plan.rows_long;
+    const int32_t n_groups = plan.n_groups, g256 = plan.g256;
+    const int64_t longest = plan.longest;
 
     DevBuf d_skip, d_oidx, d_oscore, d_matrix, d_rows_reg, d_rows_long, d_rec, d_scored;
     int skip_up_to = 0;
@@ -298,28 +279,9 @@ static int jaro_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, in
     if (!rows_reg.empty()) PFZ_TRY(d_rows_reg.upload(ctx, rows_reg));
     if (!rows_long.empty()) PFZ_TRY(d_rows_long.upload(ctx, rows_long));
 
-    // The register launches: (rows, to-groups, word).  Few from-strings: the to-groups of each are split over `parts`
-    // workgroups (K4's rule: >= 4 rounds of work units on the chip, each part at least one group per wave).  A row's
-    // launches leave their records side by side; the last slot is the general kernel's.
-    const int64_t max_grid = (int64_t)ctx->prop.multiProcessorCount * 8;
-    struct RegLaunch { size_t row0, n_rows; int32_t g_begin, g_end; bool wide; int32_t parts, slot0; };
-    RegLaunch reg[3] = {{0, n32, 0, g32, false, 1, 0}, {0, n32, g32, g256, true, 1, 0}, {n32, rows_reg.size() - n32, 0, g256, true, 1, 0}};
-    for (RegLaunch &L : reg) {
-        if (L.n_rows == 0 || L.g_begin >= L.g_end) {
-            L.parts = 0;
-            continue;
-        }
-        const int64_t want = (4 * max_grid + (int64_t)L.n_rows - 1) / (int64_t)L.n_rows, cap = std::max<int32_t>(1, (L.g_end - L.g_begin) / 4);
-        L.parts = (int32_t)std::max<int64_t>(1, std::min(want, cap));
-    }
-    reg[1].slot0 = reg[0].parts;
-    // the other from-strings have the general kernel alone: their to-groups are split by the same rule
-    int32_t parts_long = 1;
-    if (!rows_long.empty()) {
-        const int64_t n = (int64_t)rows_long.size(), want = (4 * max_grid + n - 1) / n, cap = std::max<int32_t>(1, n_groups / 4);
-        parts_long = (int32_t)std::max<int64_t>(1, std::min(want, cap));
-    }
-    const int32_t n_slots = std::max(std::max(reg[0].parts + reg[1].parts, reg[2].parts) + 1, parts_long);
+    // A row's launches leave their records side by side; the last slot is the general kernel's.
+    const int64_t max_grid = plan.max_grid;
+    const int32_t parts_long = plan.parts_long, n_slots = plan.n_slots;
     const size_t rec_bytes = (size_t)n_rows * (size_t)n_slots * sizeof(BestRec);
     PFZ_TRY(d_rec.alloc(ctx, rec_bytes));
     PFZ_HIP(hipMemsetAsync(d_rec.p, 0xff, rec_bytes, ctx->stream));      // idx = -1: no candidate
@@ -343,7 +305,7 @@ static int jaro_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, in
 
     {
         ProfScope ps_all(ctx, "k8_jaro");
-        for (const RegLaunch &L : reg) {
+        for (const JaroRegLaunch &L : plan.reg) {
             if (L.parts == 0) continue;
             A.rows = d_rows_reg.as<int32_t>() + L.row0;
             A.n_rows = (int32_t)L.n_rows;

@@ -1,4 +1,4 @@
-// Exact per-row top-n of the all-pairs edit-distance kernels (K4 ratio, K9 Levenshtein / OSA): the `ntop` best choices of a
+// Exact per-row top-n of the all-pairs edit-distance kernels (K4 ratio, K9 Levenshtein / OSA, K19 the per-pair scorers, K21 Jaro): the `ntop` best choices of a
 // from-string in the order (float64 score descending, original to-index ascending) -- np.argsort(-scores, kind="stable")[:ntop]
 // on the scores the reference computes (polyfuzz/models/_distance.py:89-102); entry 0 is the arg-max kernels' first maximum.
 //

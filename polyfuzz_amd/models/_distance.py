@@ -112,8 +112,8 @@ def _device_scorer(scorer) -> str:
     return name if name in _DEVICE_SCORERS else ""
 
 
-# the scorers whose kernels have a top-n form (K4 on one fixed string per list element, K9); Jaro (K8) and the per-pair scorers
-# (K7) prune around a single best and keep their arg-max only
+# the scorers whose kernels have a top-n form here (K4 on one fixed string per list element, K9); Jaro (K8) and the per-pair scorers
+# (K7) prune around a single best and keep their arg-max only -- their top-n forms are JaroWinkler.match(top_n=) (K21) and RapidFuzz.top_n (K19)
 _TOP_N_SCORERS = ("ratio", "QRatio", "token_sort_ratio", "levenshtein", "osa", "indel")
 _TOP_N_MAX = 64                 # one list entry per lane of a wave (csrc/topn_wave.h)
 _JOIN_SCORERS = ("levenshtein", "osa", "indel")      # the scorers with a threshold kernel (K11; "indel": K13)
@@ -205,7 +205,7 @@ class EditDistance(BaseMatcher):
     ONE minimum and maximum over all Similarity columns.  top_n is clipped to the number of choices every row has (the
     reference's clip, _utils.py:55-56); more than 64 after clipping raises _lib.PfzUnsupported; the Jaro scorers and the
     per-pair scorers (K7) raise NotImplementedError from `match` -- their kernels keep a single best (for the per-pair scorers the
-    top-n form is RapidFuzz.top_n, K19).  An int >= 1, else
+    top-n form is RapidFuzz.top_n, K19; for the Jaro scorers JaroWinkler.match(top_n=), K21).  An int >= 1, else
     ValueError; kept through pickling.
 
     join (method, "levenshtein", "osa" and "indel"): every pair at least `min_similarity` similar instead of each string's best --
@@ -373,7 +373,9 @@ class EditDistance(BaseMatcher):
         self.last_counts = {"pairs": pairs, "components": components}
         return label
 
-    def _best(self, from_list, to_list, reuse_to=False, top_n=None):
+    def _best(self, from_list, to_list, reuse_to=False, top_n=None, choices=_top_n_choices):
+        """the enqueued best-choice pass (top_n None) or `choices(...)`'s top_n best (its arguments: _top_n_choices's), and the
+        names the indices stand for; the self-match's skip codes, the resident to-list and its reuse are decided here, once"""
         ctx = _lib.Context.default()
         self_match = to_list is None
         skip = None
@@ -405,7 +407,7 @@ class EditDistance(BaseMatcher):
                 to_dev = upload_for(ctx, name, names)
             self._to_dev, self._to_names = to_dev, snap
         if top_n is not None:
-            return _top_n_choices(ctx, name, from_list, names, skip, self_match, to_dev, top_n), names
+            return choices(ctx, name, from_list, names, skip, self_match, to_dev, top_n), names
         return best_choice_async(ctx, name, from_list, names, skip, self_match, to_dev=to_dev), names
 
     # a matcher is pickled by joblib (reference _distance.py:77, polyfuzz.py:429-457): device handles stay behind

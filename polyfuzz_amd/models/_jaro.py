@@ -1,13 +1,13 @@
 """JaroWinkler -- jellyfish's Jaro / Jaro-Winkler similarity with all three questions answered on the device: the best match
-(`match`: K8, through EditDistance), every pair at or above a score (`join`: K20) and the clusters of that relation
-(`components`: K20).
+(`match`: K8, through EditDistance), the n best choices (`match(top_n=, min_similarity=)`: K21), every pair at or above a score
+(`join`: K20) and the clusters of that relation (`components`: K20).
 
 "Jaro-Winkler >= 0.9" is the textbook rule of record linkage, and the scorer of the reference's custom-model tutorial
 (docs/tutorial/models/models.md:46-58).  `EditDistance(scorer="jaro_winkler")` keeps refusing `join`, `components` and
-`top_n > 1`; the threshold forms live here, as RapidFuzz.top_n lives beside an EditDistance that refuses it.
+`top_n > 1`; the threshold forms and the top-n live here, as RapidFuzz.top_n lives beside an EditDistance that refuses it.
 
 Scores are K8's float64 on the scorer's own 0..1 scale, on code points, with jellyfish's default arguments (no
-long_tolerance); `join` reports the very bits `match` would (csrc/k8_core.h jaro_score).
+long_tolerance); `join` and the top-n report the very bits `match` would (csrc/k8_core.h jaro_score).
 """
 import time
 from typing import List
@@ -18,7 +18,8 @@ import pandas as pd
 from .. import _lib
 from ._base import BaseMatcher
 from ._distance import EditDistance
-from ._utils import gather_column
+from ._distance import _TOP_N_MAX
+from ._utils import gather_column, object_column
 
 
 class JaroWinkler(BaseMatcher):
@@ -31,11 +32,12 @@ class JaroWinkler(BaseMatcher):
         normalize: `match` only, as EditDistance's (the reference's min-max rescaling of the Similarity column)
 
     match:      the best to-string of every from-string -- EditDistance(scorer="jaro_winkler" / "jaro").match, that matcher's
-                frame and code path (K8).
+                frame and code path (K8); with the keywords top_n / min_similarity the n best choices at or above a score
+                (K21), rapidfuzz.process.extract(..., limit=top_n, score_cutoff=min_similarity).  The count is a keyword of the
+                call: the matcher has no attribute of that name.
     join:       every pair with score >= min_similarity, exact (K20).
     components: the connected components of the self-join's graph (K20); polyfuzz_amd.linkage.connected_components(strings,
                 JaroWinkler(), 0.9) turns them into single_linkage's three dicts.
-    There is no top_n.
     """
     def __init__(self, winkler: bool = True, model_id: str = None, normalize: bool = True):
         super().__init__(model_id)
@@ -45,11 +47,54 @@ class JaroWinkler(BaseMatcher):
         self._scorer_name = "jaro_winkler" if self.winkler else "jaro"
         self._best = EditDistance(scorer=self._scorer_name, model_id=model_id, normalize=normalize)
 
-    def match(self, from_list: List[str], to_list: List[str] = None, **kwargs) -> pd.DataFrame:
-        """ The best match of every from-string: EditDistance(scorer=...).match, delegated """
+    def match(self, from_list: List[str], to_list: List[str] = None, top_n: int = 1, min_similarity: float = 0.0, **kwargs) -> pd.DataFrame:
+        """ top_n == 1 and min_similarity == 0.0 (the defaults): the best match of every from-string,
+        EditDistance(scorer=...).match, delegated with `kwargs` as they are.
+
+        Otherwise (K21) the frame From, To, Similarity, To_2, Similarity_2, ... of EditDistance.top_n: per from-string its top_n
+        best choices in the order np.argsort(-scores, kind="stable") gives -- float64 score descending, equal scores in list
+        order --, exact, the scores K8's float64, unrounded.  top_n is clipped to the number of choices every row has (at least
+        1); more than 64 after clipping raises _lib.PfzUnsupported.  A cell whose choice is missing, or scores below
+        min_similarity (equal is kept), is None / 0.0.  At min_similarity == 0.0 the first pair of columns is the top_n = 1
+        frame before normalisation.
+
+        `normalize`: with min_similarity == 0.0 as EditDistance's top_n -- ONE minimum and maximum over all Similarity columns;
+        with a cutoff it is NOT applied, by `join`'s rule: a rescaled score no longer means the threshold.
+
+        to_list None: the self-match -- a from-string's own first occurrence is left out and nothing else, as EditDistance
+        does.  re_train=False re-uses the resident to-list by EditDistance's rule; an empty set of choices raises what
+        EditDistance raises.  top_n: an int >= 1, min_similarity: a number in [0, 1] (ValueError otherwise, before any device
+        call). """
+        if isinstance(top_n, bool) or not isinstance(top_n, (int, np.integer)) or top_n < 1:
+            raise ValueError(f"top_n must be an int >= 1, not {top_n!r}")
+        cutoff = _lib.check_min_similarity(min_similarity)
         self._best.normalize = self.normalize
-        matches = self._best.match(from_list, to_list, **kwargs)
-        self.last_timings = getattr(self._best, "last_timings", None)
+        if top_n == 1 and cutoff == 0.0:
+            matches = self._best.match(from_list, to_list, **kwargs)
+            self.last_timings = getattr(self._best, "last_timings", None)
+            return matches
+        t0 = time.perf_counter()
+        # every row has len(to_list) choices, or one less in a self-match (EditDistance._match_top_n's clip)
+        ntop = max(1, min(int(top_n), (len(from_list) - 1) if to_list is None else len(to_list)))
+        if ntop > _TOP_N_MAX:
+            raise _lib.PfzUnsupported(-4, f"JaroWinkler.match: top_n = {ntop} exceeds the limit of {_TOP_N_MAX} best choices per from-string")
+
+        def choices(ctx, name, from_list, names, skip, self_match, to_dev, ntop):
+            f_dev = _lib.DeviceStrings.upload(ctx, from_list)
+            return _lib.jaro_topn(ctx, f_dev, f_dev if self_match else to_dev, name, ntop, skip, score_cutoff=cutoff)
+        (idx, score), names = self._best._best(from_list, to_list, reuse_to=kwargs.get("re_train", True) is False, top_n=ntop, choices=choices)
+        t1 = time.perf_counter()
+        data = {"From": object_column(from_list)}
+        for r in range(ntop):      # (the kernel has applied the cutoff: a choice below it is no entry, index -1 -> None, score 0.0)
+            data["To" if r == 0 else f"To_{r + 1}"] = gather_column(names, np.ascontiguousarray(idx[:, r]))
+            data["Similarity" if r == 0 else f"Similarity_{r + 1}"] = score[:, r].copy()
+        matches = pd.DataFrame(data, copy=False)
+        if self.normalize and cutoff == 0.0 and score.size:      # EditDistance._match_top_n's: one minimum and one maximum
+            lo, hi = score.min(), score.max()
+            for r in range(ntop):
+                c = "Similarity" if r == 0 else f"Similarity_{r + 1}"
+                matches[c] = (matches[c] - lo) / (hi - lo)
+        self.last_timings = {"device": (t1 - t0) * 1e3, "frame": (time.perf_counter() - t1) * 1e3}
         return matches
 
     def join(self,
