@@ -115,7 +115,9 @@ int pfz_prof_reset(pfz_ctx *ctx);
  * K16: `k16_keys_sort` (keys, sort and row pointers), `k16_pairs_join` (the scoring launches of a call, either sink),
  * `k16_pairs_join_general` (its general-kernel launch), `k16_compact` (the join's scan and compaction).
  * K17 (the key entries): K16's scopes -- `k16_keys_sort` then holds the row pointers alone --, `k17_items` (the work items: count,
- * scan, fill); pfz_cossim_join_dev: `k15_join` once per launch, `k15_sort`. */
+ * scan, fill); pfz_cossim_join_dev: `k15_join` once per launch, `k15_sort`.
+ * K22: `k22_search` (the 16-bit tile kernel, both runs of a repeated search), `k22_rescore` (the candidates scored on the fp32
+ * vectors; for the components with forest and labels), `k22_sort_unpack`. */
 int pfz_prof_get(pfz_ctx *ctx, const char *name, double *total_ms, int64_t *launches);
 
 /* ---- CSR matrices --------------------------------------------------------
@@ -904,6 +906,55 @@ int pfz_dense_join(pfz_ctx *ctx, const pfz_dense *from_vectors, const pfz_dense 
  * out_components is PFZ_ERR_INVALID.  Profiling scope: `k14_components` (forest, tile kernel and labels).  Blocks. */
 int pfz_dense_components(pfz_ctx *ctx, const pfz_dense *vectors, double min_similarity, int32_t *out_label,
                          int64_t *out_pairs, int64_t *out_components, int64_t *out_counters);
+
+/* ---- K22: K14's two entries searched on the 16-bit matrix cores, scored exactly --
+ * The same question -- every pair (from i, to j) whose cosine is >= min_similarity -- answered in two stages: a search on float16
+ * / bfloat16 copies of the vectors (K5's 16-bit tile program with K14's end) finds candidates, and every candidate is scored on
+ * the fp32 vectors.  The score of a pair is the one pfz_dense_rescore_topn computes for it, bit for bit: f_from[i] * f_to[j] *
+ * sum_k x_i[k] x_j[k], summed in float64 in one fixed order per pair and rounded to fp32 once; it is symmetric in its two rows, so
+ * a self-join pair has one score.  The comparison is (double)score >= min_similarity: equal is a hit.
+ * The search copy: pfz_dense_derive16 makes it on the device from an fp32 handle uploaded with normalize = 1 (PFZ_ERR_INVALID
+ * otherwise) -- value k of a row is round16(x[k] * inv32), the fp32 product with the row's 1 / ||row|| rounded to nearest even to
+ * `dtype` (PFZ_DENSE_F16 or PFZ_DENSE_BF16): every value lies in [-1, 1], which float16 needs; the copy has its own 1 / ||row||;
+ * the matrix is uploaded once.  The handle is an ordinary 16-bit operand (pfz_dense_topn takes it; pfz_dense_free frees it).
+ * The margin: a pair at or above min_similarity is a candidate because the search compares the 16-bit score with ts32 = the
+ * largest float32 <= min_similarity - eps, where, with u = 2^-8 for bfloat16, u = 2^-11 for float16 and ld the copy's padded width
+ * (a multiple of 64),
+ *     eps = 2 asin(u + 2^-24 + sqrt(ld) 2^-25) + (ld + 8) 2^-23
+ * (pfz_dense_search_margin, a pure host function: no device is touched).  The first term is derived: a rounding of relative size
+ * u turns a vector by at most asin(u), the cosine is 1-Lipschitz in the angle, 2^-24 is the fp32 pre-scaling and sqrt(ld) 2^-25
+ * float16's subnormals.  The second term rests on an assumption about the matrix core -- that an fp32 accumulation of exact 16-bit
+ * products loses at most one ulp of the running sum per product (the two row factors and the final rounding add the rest); it is
+ * held by measurement (tests/test_dense_join16_gpu.py), not proved.
+ * The candidate buffer is the library's, not the caller's: cand_capacity keys of 8 bytes (0: the library chooses, four per
+ * from-row and at least 4096).  When the search counts more candidates than the buffer holds, a buffer of the exact count is made
+ * and the search runs once more: two runs at most.  Device memory beyond the operands is O(candidates), for the components too.
+ * Output, order, self-join rule, *out_total and the capacity rule are K14's on the final hits: *out_total is always the exact
+ * number of hits; when it exceeds `capacity` the call still returns PFZ_OK, has written NONE of the three output arrays and is
+ * to be repeated with capacity >= *out_total; out_idx ascending within a row; never (i, i); the same call gives the same bytes
+ * every time.  to16 == NULL, or from16 itself: the self-join (to32 NULL or from32 itself then).
+ * out_counters: NULL, or int64[3] -- [0] the 256 x 256 tiles executed, [1] the 64 x 64 wave corners that held a candidate (both
+ * add up over the two runs of a repeated search), [2] the candidates.
+ * from32 == NULL (to32 NULL too): the plain 16-bit join, for a corpus that exists only in 16 bits -- margin 0, the search keeps its
+ * scores and there is no second stage: the score of a pair is the float32 pfz_dense_topn computes on the 16-bit handles, bit for
+ * bit (in a self-join that of (i, j), i < j), compared as K14 compares; cand_capacity is ignored and [2] is the number of hits.
+ * PFZ_ERR_INVALID: a 16-bit handle that is not PFZ_DENSE_F16 / PFZ_DENSE_BF16 with normalize = 1, two 16-bit handles of different
+ * types or widths, an exact handle that is not PFZ_DENSE_F32 with normalize = 1, unequal shapes between a 16-bit handle and its
+ * exact handle, a self-join with a second exact handle or two lists without the to-side's, a NaN min_similarity or one outside [0, 1], capacity or
+ * cand_capacity < 0.  Limits (PFZ_ERR_UNSUPPORTED beyond): at most 2^31 tiles in one call, fewer than 2^31 rows per list; a call
+ * of 2^23 workgroups or more is several launches.  Profiling scopes: `k22_search`, `k22_rescore`, `k22_sort_unpack`.  Blocks. */
+int pfz_dense_derive16(pfz_ctx *ctx, const pfz_dense *exact, int32_t dtype, pfz_dense **out);
+int pfz_dense_search_margin(int32_t dtype, int64_t ld, double *out_eps);
+int pfz_dense_join16(pfz_ctx *ctx, const pfz_dense *from16, const pfz_dense *to16, const pfz_dense *from32, const pfz_dense *to32,
+                     double min_similarity, int64_t capacity, int64_t cand_capacity, int64_t *out_row_ptr, int32_t *out_idx,
+                     float *out_sim, int64_t *out_total, int64_t *out_counters);
+/* The connected components of "exact score >= min_similarity" over ONE list: the pairs of pfz_dense_join16(ctx, v16, NULL, v32,
+ * NULL, min_similarity, ...), but no hit is stored -- the lane that scores one unites the two positions in the union-find of
+ * csrc/k12_core.h.  Labels, *out_pairs and *out_components as pfz_dense_components; out_counters and cand_capacity as above.
+ * Unlike K14's O(n), device memory beyond the operands is O(candidates): the candidate keys are stored.  Both handles are
+ * required.  Profiling scopes: `k22_search`, `k22_rescore` (forest, scoring and labels).  Blocks. */
+int pfz_dense_components16(pfz_ctx *ctx, const pfz_dense *v16, const pfz_dense *v32, double min_similarity, int64_t cand_capacity,
+                           int32_t *out_label, int64_t *out_pairs, int64_t *out_components, int64_t *out_counters);
 
 /* ---- K15: all pairs at or above a sparse cosine, and their components -----------
  * The threshold form of K3, what de-duplication asks of the reference's TF-IDF matcher: every pair (from-row i, to-row j) whose

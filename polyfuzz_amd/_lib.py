@@ -139,6 +139,10 @@ SIGNATURES = {
     "pfz_dense_rescore_topn_mixed": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_f32, c_vp]),
     "pfz_dense_join": (ctypes.c_int, [c_vp, c_vp, c_vp, c_f64, c_i64, c_vp, c_vp, c_vp, P(c_i64), c_vp]),
     "pfz_dense_components": (ctypes.c_int, [c_vp, c_vp, c_f64, c_vp, P(c_i64), P(c_i64), c_vp]),
+    "pfz_dense_derive16": (ctypes.c_int, [c_vp, c_vp, c_i32, P(c_vp)]),
+    "pfz_dense_search_margin": (ctypes.c_int, [c_i32, c_i64, P(c_f64)]),
+    "pfz_dense_join16": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_f64, c_i64, c_i64, c_vp, c_vp, c_vp, P(c_i64), c_vp]),
+    "pfz_dense_components16": (ctypes.c_int, [c_vp, c_vp, c_vp, c_f64, c_i64, c_vp, P(c_i64), P(c_i64), c_vp]),
     "pfz_cossim_join": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_f64, c_i64, c_vp, c_vp, c_vp, P(c_i64), c_vp]),
     "pfz_cossim_components": (ctypes.c_int, [c_vp, c_vp, c_vp, c_f64, c_vp, P(c_i64), P(c_i64), c_vp]),
     "pfz_pr_curve_host": (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp]),
@@ -1189,6 +1193,19 @@ class DeviceDense(_Handle):
         scores by about 1e-3 (float16) or 1e-2 (bfloat16) relative per element, which is why this is opt-in."""
         return cls.upload_as(ctx, vec, check_compute_dtype(compute_dtype), normalize)
 
+    def derive16(self, dtype):
+        """The search copy of an fp32 handle uploaded with normalize=True, made on the device (K22): row values
+        round16(x[k] * (1 / ||row||)), to nearest even, as "float16" or "bfloat16" -- every value in [-1, 1].  The vectors are
+        uploaded once; the copy is a 16-bit operand like any other."""
+        if dtype not in ("float16", "bfloat16"):
+            raise ValueError(f"the search types are 'float16' and 'bfloat16', got {dtype!r}")
+        _dense_join_operand(self, "the vectors")
+        h = c_vp()
+        check(self.ctx.lib.pfz_dense_derive16(self.ctx.h, self.h, DENSE_DTYPES[dtype], ctypes.byref(h)))
+        m = type(self)(self.ctx, h)
+        m.n, m.dim, m.normalize, m.dtype = self.n, self.dim, True, dtype
+        return m
+
     @classmethod
     def upload_bits(cls, ctx, vec, normalize=True):
         """1-bit rows (K5's Hamming tile program).  An np.uint8 array [n, B] is "ubinary": d = 8 B bits in np.packbits order,
@@ -1278,6 +1295,68 @@ def dense_components(ctx, dev, min_similarity, counters=False):
     _dense_join_operand(dev, "the vectors")
     return _components_call(dev.n, DENSE_JOIN_COUNTERS, counters, lambda label, pairs, components, wk: ctx.lib.pfz_dense_components(
         ctx.h, dev.h, float(min_similarity), label, pairs, components, wk))
+
+
+# ---- K22: the same two entries searched on the 16-bit matrix cores, scored exactly on the fp32 vectors -------------------
+
+DENSE_JOIN16_COUNTERS = ("tiles", "hit_corners", "candidates")      # pfz_dense_join16's out_counters, in order
+
+
+def dense_search_margin(dtype, ld):
+    """eps of K22's search for `dtype` ("float16" / "bfloat16") and the padded width ld: how far the float32 score of two search
+    copies may lie below the exact cosine -- 2 asin(u + 2^-24 + sqrt(ld) 2^-25) + (ld + 8) 2^-23, u = 2^-11 / 2^-8 (the header
+    derives the first term and names the assumption behind the second).  The library's own host function: no device is touched."""
+    if dtype not in ("float16", "bfloat16"):
+        raise ValueError(f"the search types are 'float16' and 'bfloat16', got {dtype!r}")
+    eps = c_f64(0.0)
+    check(load().pfz_dense_search_margin(DENSE_DTYPES[dtype], int(ld), ctypes.byref(eps)))
+    return eps.value
+
+
+def dense_search_threshold32(t, eps):
+    """The largest float32 <= t - eps: what K22's search compares the 16-bit scores with.  Pure numpy."""
+    d = np.float64(t) - np.float64(eps)
+    r = np.float32(d)                              # (to nearest: at most one step above d)
+    return np.nextafter(r, np.float32(-np.inf)) if np.float64(r) > d else r
+
+
+def _search16_operand(dev, what):
+    if dev.dtype not in ("float16", "bfloat16") or not dev.normalize:
+        raise ValueError(f"{what} are {dev.dtype} vectors uploaded with normalize={dev.normalize}: the 16-bit search takes "
+                         "float16 / bfloat16 operands made with normalize=True (DeviceDense.derive16)")
+
+
+def dense_join16(ctx, from16, to16, from_exact, to_exact, min_similarity, capacity=None, counters=False, cand_capacity=None):
+    """K22: dense_join's result -- (row_ptr, to-index, similarity float32, counts) -- found on the 16-bit matrix cores.  from16 /
+    to16: the search copies (DeviceDense.derive16) of the fp32 handles from_exact / to_exact; to16 and to_exact None: the
+    self-join.  Every pair whose exact score -- dense_rescore's float32: a float64 sum rounded once -- is >= min_similarity;
+    similarity is that score.  cand_capacity: the candidate keys the library's buffer has room for (None: it chooses); a search
+    that finds more is repeated once with room for all.  capacity as dense_join, on the final hits.  counts: {"pairs": hits,
+    "candidates": ...}, with counters=True all of DENSE_JOIN16_COUNTERS (the tiles and corners of both searches when it was
+    repeated).  from_exact None: the plain 16-bit join -- the similarity is dense_topn's float32 on the 16-bit handles, bit for
+    bit, and there is no second stage."""
+    _search16_operand(from16, "the from-vectors")
+    if to16 is not None:
+        _search16_operand(to16, "the to-vectors")
+    for dev, what in ((from_exact, "the exact from-vectors"), (to_exact, "the exact to-vectors")):
+        if dev is not None:
+            _dense_join_operand(dev, what)
+    h = [None if d is None else d.h for d in (to16, from_exact, to_exact)]
+    row_ptr, hits, n, work = _join_call(
+        from16.n, capacity, (np.int32, np.float32), DENSE_JOIN16_COUNTERS, True,
+        lambda cap, ptr, hit, total, wk: ctx.lib.pfz_dense_join16(ctx.h, from16.h, h[0], h[1], h[2], float(min_similarity), cap,
+                                                                  int(cand_capacity or 0), ptr, *hit, total, wk))
+    return (row_ptr,) + hits + ({"pairs": n, **(work if counters else {"candidates": work["candidates"]})},)
+
+
+def dense_components16(ctx, dev16, dev_exact, min_similarity, counters=False, cand_capacity=None):
+    """K22: dense_components' result -- (label int32[n], pairs, components) -- over the pairs of dense_join16's self-join: the
+    candidates of the 16-bit search, scored exactly and united where they hit; none is stored, but the candidate keys are:
+    device memory is O(candidates).  counters=True appends a dict of DENSE_JOIN16_COUNTERS."""
+    _search16_operand(dev16, "the vectors")
+    _dense_join_operand(dev_exact, "the exact vectors")
+    return _components_call(dev16.n, DENSE_JOIN16_COUNTERS, counters, lambda label, pairs, components, wk: ctx.lib.pfz_dense_components16(
+        ctx.h, dev16.h, dev_exact.h, float(min_similarity), int(cand_capacity or 0), label, pairs, components, wk))
 
 
 # ---- K18: the threshold join of K7's scorers and its components ---------------------------------------------------------

@@ -27,70 +27,19 @@
 // of one L2).  Two lists: the blocks column by column.  Self-join: the blocks (bi <= bj) of the upper triangle, numbered
 // g = bj (bj + 1) / 2 + bi and decoded in the kernel; of a diagonal block's 64 workgroups the 28 below the diagonal leave at once,
 // as do those of tiles beyond the edge.  A deal of 2^24 workgroups or more goes out as several launches (k14_launch).
-#include "k5_core.h"
-#include "k11_core.h"
-#include "k12_core.h"
-
-#include <algorithm>
-#include <cmath>
-#include <limits.h>
+// The argument block, the deal, the corner's end and the launches are in k14_core.h: K22 (k22_dense_join16.hip) puts the same end
+// behind the 16-bit main loop.
+#include "k14_core.h"
 
 namespace pfz {
 
-struct DenseJoinArgs {
-    const void *A, *B;                 // [n_a][d], [n_b][d] float32 (a self-join: the same matrix)
-    const float *inv_a, *inv_b;        // 1 / ||row||
-    int64_t n_a, n_b, d;               // d: the padded width, a multiple of 32
-    int32_t tiles_m, tiles_n;
-    int32_t self;
-    int32_t wg_base;                   // the number, in the call's 1-D deal, of this launch's first workgroup (k14_launch)
-    float t32;
-    unsigned long long *state;         // [0] hits, [1] tiles executed, [2] 64 x 64 wave corners that held a hit
-    uint64_t *keys;                    // join: [capacity] row << 32 | col, in the order the waves got there ...
-    float *vals;                       // ... and the scores beside them
-    unsigned long long capacity;
-    int32_t *parent;                   // components: [n_a] the forest (k12_core.h)
-};
-
-// the tile of this workgroup; false: there is none (beyond the edge, or below the diagonal of a self-join)
-__device__ inline bool k14_tile(const DenseJoinArgs &P, int *tm, int *tn)
-{
-    const int w = P.wg_base + (int)blockIdx.x, xcd = w & 7, idx = w >> 3, pos = idx & 63;      // (wg_base is a multiple of 8: the XCD is blockIdx's)
-    const int g = (idx >> 6) * 8 + xcd;
-    int bi, bj;
-    if (P.self) {
-        bj = (int)((sqrtf(8.f * (float)g + 1.f) - 1.f) * 0.5f);      // (a guess: float32 is a few blocks off at most)
-        while ((int64_t)bj * (bj + 1) / 2 > g) --bj;
-        while ((int64_t)(bj + 1) * (bj + 2) / 2 <= g) ++bj;
-        bi = g - (int)((int64_t)bj * (bj + 1) / 2);
-    }
-    else {
-        const int bm = (P.tiles_m + 7) >> 3;
-        bi = g % bm;
-        bj = g / bm;
-    }
-    *tm = bi * 8 + (pos & 7);
-    *tn = bj * 8 + (pos >> 3);
-    return *tm < P.tiles_m && *tn < P.tiles_n && (!P.self || *tn >= *tm);
-}
-
-// inclusive prefix sum over the lanes of a wave
-__device__ inline int wave_scan_i32(int v, int lane)
-{
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
-
-template <bool kComp>
+// One workgroup's tile: the fp32 main loop, then the end of the wave's 64 x 64 corner (dense_corner_end of k14_core.h).
+template <DenseSink kSink>
 __device__ __forceinline__ void k14_body(const DenseJoinArgs &P)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int tm, tn;
-    if (!k14_tile(P, &tm, &tn)) return;
+    if (!k14_tile<8, 8>(P, &tm, &tn)) return;
     if (tid == 0) atomicAdd(P.state + 1, 1ull);
     const int64_t row0 = (int64_t)tm * kTile, col0 = (int64_t)tn * kTile;
     const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
@@ -105,71 +54,13 @@ __device__ __forceinline__ void k14_body(const DenseJoinArgs &P)
 
     k5_tile_loop(P.A, P.B, row0, col0, P.n_a, P.n_b, P.d, tid, lane, wm, wn, acc);
 
-    // Accumulator r of lane l = row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31 of its 32 x 32 (tile_epilogue of K5).  Element
-    // q = 32 i + 16 j + r of the lane is (row_of(q), col_of(q)).
-    const int64_t rbase = row0 + wm + 4 * (lane >> 5), cbase = col0 + wn + (lane & 31);
-    const bool self = P.self != 0;
-    float sb[2];
-    bool col_ok[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        col_ok[j] = cbase + 32 * j < P.n_b;
-        sb[j] = col_ok[j] ? P.inv_b[cbase + 32 * j] : 0.f;
-    }
-    // The corner in two halves of 32 rows (the accumulator pairs i = 0, 1): the half's 32 scores of the lane, its hits as a mask
-    // (bit 16 j + r), and -- only where some lane of the wave has one -- ONE atomic for all of them (K11's KeyAppend, with a
-    // prefix sum in place of the ballot's popcount: a lane may hold several).
-    bool corner_hit = false;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        float v[2][16];
-        uint32_t mask = 0;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int64_t row = rbase + i * 32 + (r & 3) + 8 * (r >> 2);
-            const bool ok = row < P.n_a;
-            const float f = ok ? P.inv_a[row] : 0.f;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                v[j][r] = acc[i][j][r] * f * sb[j];
-                const bool hit = ok && col_ok[j] && v[j][r] >= P.t32 && (!self || cbase + 32 * j > row);
-                mask |= (uint32_t)hit << (16 * j + r);
-            }
-        }
-        if (!__any(mask != 0)) continue;
-        corner_hit = true;
-        const int mine = __popc(mask), upto = wave_scan_i32(mine, lane), all = __shfl(upto, 63, 64);
-        unsigned long long base = 0;
-        if (lane == 0) base = atomicAdd(P.state, (unsigned long long)all);
-        if (kComp) {
-            while (mask) {
-                const int q = __builtin_ctz(mask), r = q & 15;
-                mask &= mask - 1;
-                uf_unite<UfDeviceOps>(P.parent, (int32_t)(rbase + i * 32 + (r & 3) + 8 * (r >> 2)), (int32_t)(cbase + 32 * (q >> 4)));
-            }
-            continue;
-        }
-        base = __shfl(base, 0, 64);
-        unsigned long long pos = base + (unsigned long long)(upto - mine);
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-                if ((mask >> (16 * j + r)) & 1) {
-                    if (pos < P.capacity) {
-                        P.keys[pos] = (uint64_t)(rbase + i * 32 + (r & 3) + 8 * (r >> 2)) << 32 | (uint64_t)(cbase + 32 * j);
-                        P.vals[pos] = v[j][r];
-                    }
-                    ++pos;
-                }
-    }
-    if (corner_hit && lane == 0) atomicAdd(P.state + 2, 1ull);
+    dense_corner_end<kSink>(acc, row0 + wm + 4 * (lane >> 5), col0 + wn + (lane & 31), P, lane);
 }
 
-__global__ __launch_bounds__(256, 2) void k14_join_kernel(DenseJoinArgs P) { k14_body<false>(P); }
+__global__ __launch_bounds__(256, 2) void k14_join_kernel(DenseJoinArgs P) { k14_body<kSinkJoin>(P); }
 
 // (a self-join always: the components of ONE list)
-__global__ __launch_bounds__(256, 2) void k14_comp_kernel(DenseJoinArgs P) { k14_body<true>(P); }
+__global__ __launch_bounds__(256, 2) void k14_comp_kernel(DenseJoinArgs P) { k14_body<kSinkUnite>(P); }
 
 // the sorted keys -> CSR: hit p of the row-major order and its share of the row pointers (k11_core.h rows_fill; the scores are
 // already in place beside the keys)
@@ -224,46 +115,6 @@ int join_download(pfz_ctx *ctx, const DevBuf &d_ptr, const DevBuf &d_idx, const 
     return PFZ_OK;
 }
 
-// the smallest float32 >= t (t in [0, 1])
-static float threshold32(double t)
-{
-    float f = (float)t;
-    if ((double)f < t) f = nextafterf(f, INFINITY);
-    return f;
-}
-
-// the grid of a call and its argument block's tile counts; PFZ_ERR_UNSUPPORTED beyond 2^31 tiles
-static int dense_join_grid(const char *who, DenseJoinArgs *P, int64_t *grid)
-{
-    const int64_t tm = (P->n_a + kTile - 1) / kTile, tn = (P->n_b + kTile - 1) / kTile;
-    const int64_t bm = (tm + 7) / 8, bn = (tn + 7) / 8;
-    const int64_t tiles = P->self ? tm * (tm + 1) / 2 : tm * tn, blocks = P->self ? bm * (bm + 1) / 2 : bm * bn;
-    *grid = (blocks + 7) / 8 * 8 * 64;
-    if (tiles > ((int64_t)1 << 31) || *grid > (int64_t)INT_MAX) {
-        set_error("%s: %lld x %lld rows are %lld tiles of %d x %d, more than the 2^31 one call launches", who, (long long)P->n_a,
-                  (long long)P->n_b, (long long)tiles, kTile, kTile);
-        return PFZ_ERR_UNSUPPORTED;
-    }
-    P->tiles_m = (int32_t)tm;
-    P->tiles_n = (int32_t)tn;
-    return PFZ_OK;
-}
-
-// One launch takes fewer than 2^32 threads (hipErrorInvalidConfiguration beyond), 2^24 workgroups of 256, which a self-join of
-// 740 000 rows exceeds.  So the call's deal of `grid` workgroups is cut into launches of at most kLaunchMax, whole 8-block rounds
-// each; they follow one another on the context's stream and share the argument block but for wg_base.
-constexpr int64_t kLaunchMax = ((int64_t)1 << 24) - 8 * 64;
-
-static int k14_launch(pfz_ctx *ctx, void (*kernel)(DenseJoinArgs), DenseJoinArgs P, int64_t grid)
-{
-    for (int64_t base = 0; base < grid; base += kLaunchMax) {
-        P.wg_base = (int32_t)base;
-        hipLaunchKernelGGL(kernel, dim3((unsigned)std::min(kLaunchMax, grid - base)), dim3(256), 0, ctx->stream, P);
-        PFZ_HIP(hipGetLastError());
-    }
-    return PFZ_OK;
-}
-
 static int dense_join_operand(const char *who, const char *side, const pfz_dense *m)
 {
     PFZ_REQUIRE(m->dtype == PFZ_DENSE_F32, "%s: the %s are %s; the threshold kernels take fp32 operands only (pfz_dense_upload)", who, side,
@@ -299,7 +150,7 @@ static int dense_join_run(pfz_ctx *ctx, const pfz_dense *F, const pfz_dense *T, 
     P.t32 = threshold32(t);
     P.capacity = (unsigned long long)capacity;
     int64_t grid;
-    PFZ_TRY(dense_join_grid("pfz_dense_join", &P, &grid));
+    PFZ_TRY(dense_join_grid("pfz_dense_join", &P, kTile, 8, 8, &grid));
 
     DevBuf d_keys, d_vals, d_state;
     PFZ_TRY(d_keys.alloc(ctx, (size_t)capacity * sizeof(uint64_t)));
@@ -312,7 +163,7 @@ static int dense_join_run(pfz_ctx *ctx, const pfz_dense *F, const pfz_dense *T, 
     unsigned long long state[3];
     {
         ProfScope ps(ctx, "k14_join");
-        PFZ_TRY(k14_launch(ctx, k14_join_kernel, P, grid));
+        PFZ_TRY(k14_launch(ctx, k14_join_kernel, P, grid, 256, 8 * 64));
         PFZ_TRY(copy_d2h(ctx, state, d_state.p, sizeof(state)));      // (waits for the kernel)
     }
     const int64_t total = (int64_t)state[0];
@@ -342,7 +193,7 @@ static int dense_comp_run(pfz_ctx *ctx, const pfz_dense *V, double t, int32_t *o
     P.self = 1;
     P.t32 = threshold32(t);
     int64_t grid;
-    PFZ_TRY(dense_join_grid("pfz_dense_components", &P, &grid));
+    PFZ_TRY(dense_join_grid("pfz_dense_components", &P, kTile, 8, 8, &grid));
 
     ForestRun forest;
     DevBuf d_state;
@@ -354,7 +205,7 @@ static int dense_comp_run(pfz_ctx *ctx, const pfz_dense *V, double t, int32_t *o
     {
         ProfScope ps(ctx, "k14_components");
         PFZ_TRY(forest.begin(ctx));
-        PFZ_TRY(k14_launch(ctx, k14_comp_kernel, P, grid));
+        PFZ_TRY(k14_launch(ctx, k14_comp_kernel, P, grid, 256, 8 * 64));
         PFZ_TRY(forest.flatten(ctx, P.state + 3));
     }
     unsigned long long state[4];

@@ -180,66 +180,6 @@ __global__ __launch_bounds__(256, 2) void k5_gemm_panel_pipe(const void *__restr
     tile_epilogue(acc, inv_a, inv_b, a0, a1, n_b, S, ld, M, ldm, row0, col0, wm, wn, lane);
 }
 
-// ---- 16-bit operands (float16 / bfloat16 embeddings) ----------------------------------------------------------------
-// The vectors are stored as their 16 bits; what differs between the two types is how a value widens and rounds and which
-// MFMA multiplies it.  The product of two such values is exact in fp32 and the MFMA sums in fp32: against the 16-bit
-// vectors as given the scores are as good as the fp32 kernel's.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x16 __attribute__((ext_vector_type(16)));
-
-// An operand trait: the stored value (store_t, kBytes) and how it widens; for the tile program (lp_gemm_tile) also the
-// accumulator type and the MFMA that takes one 16-byte fragment of each operand.  f32 has the fp32 tile program of its own.
-struct f32 {
-    typedef float store_t;
-    static constexpr int kBytes = 4;
-    __device__ static inline float widen(float v) { return v; }
-};
-struct f16 {
-    typedef uint16_t store_t;
-    typedef f32x16 acc_t;
-    static constexpr int kBytes = 2;
-    __device__ static inline float widen(uint16_t b) { return (float)__builtin_bit_cast(_Float16, b); }
-    __device__ static inline uint16_t narrow(float x) { return __builtin_bit_cast(uint16_t, (_Float16)x); }   // round to nearest even
-    __device__ static inline f32x16 mfma(const u32x4 &a, const u32x4 &b, const f32x16 &c)
-    {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    }
-};
-struct bf16 {
-    typedef uint16_t store_t;
-    typedef f32x16 acc_t;
-    static constexpr int kBytes = 2;
-    __device__ static inline float widen(uint16_t b) { return __uint_as_float((uint32_t)b << 16); }
-    __device__ static inline uint16_t narrow(float x)
-    {
-        const uint32_t u = __float_as_uint(x);
-        if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);      // NaN stays NaN
-        return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);                       // round to nearest even
-    }
-    __device__ static inline f32x16 mfma(const u32x4 &a, const u32x4 &b, const f32x16 &c)
-    {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    }
-};
-// int8: a fragment is 16 consecutive values of a row, one MFMA covers k = 32.  Which k of the 32 a lane's 16 values stand for
-// does not matter here: A and B are read with the same assignment, so every step sums the same 32 products, and integer
-// addition has no order (tests/test_dense8_gpu.py holds the dot products bit for bit).
-struct i8 {
-    typedef int8_t store_t;
-    typedef i32x16 acc_t;
-    static constexpr int kBytes = 1;
-    __device__ static inline float widen(int8_t q) { return (float)q; }
-    __device__ static inline i32x16 mfma(const u32x4 &a, const u32x4 &b, const i32x16 &c)
-    {
-        return __builtin_amdgcn_mfma_i32_32x32x32_i8(__builtin_bit_cast(i32x4, a), __builtin_bit_cast(i32x4, b), c, 0, 0, 0);
-    }
-};
-
-constexpr int kTile16 = 256; // workgroup tile of the 16-bit (and 8-bit) tile program
-constexpr int kChunkBytes = 128;   // bytes of a row a tile program stages per step: 32 floats, 64 16-bit or 128 int8 values
-
 // The norm of the values as stored: the cosine is that of the vectors the GEMM multiplies.  The sum is float64 (for int8
 // exact: integer squares, at most 2^14 ld), zero rows stay zero (sklearn normalize).  normalize == 0: raw dot products are
 // wanted and every factor is 1 -- unless keep_scale: an int8 row quantised from float32 keeps the scale k5_quantize8 left
@@ -266,31 +206,28 @@ __global__ __launch_bounds__(256) void k5_inv_norms(const void *__restrict__ x, 
     if (lane == 0) inv[row] = ss > 0.0 ? (float)(1.0 / sqrt(ss)) : 0.f;
 }
 
-// fp32 [n][dim] -> T [n][ld], round to nearest even, the columns beyond dim zero (16-bit compute asked for float32 input)
+// fp32 [n][src_ld] -> T [n][ld], round to nearest even, the columns beyond dim zero (16-bit compute asked for float32 input).
+// scale: NULL, or a factor per row that is applied first (one fp32 product, rounded to nearest even): with the row's 1 / ||row||
+// every value lies in [-1, 1] before it is rounded (pfz_dense_derive16, the search copy of K22).
 template <typename T>
-__global__ __launch_bounds__(256) void k5_round16(const float *__restrict__ src, int64_t n, int64_t dim, int64_t ld,
-                                                   uint16_t *__restrict__ dst)
+__global__ __launch_bounds__(256) void k5_round16(const float *__restrict__ src, int64_t n, int64_t dim, int64_t src_ld, int64_t ld,
+                                                   const float *__restrict__ scale, uint16_t *__restrict__ dst)
 {
     const int64_t total = n * ld;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t row = i / ld, col = i - row * ld;
-        dst[i] = col < dim ? T::narrow(src[row * dim + col]) : (uint16_t)0;
+        float v = 0.f;
+        if (col < dim) {
+            v = src[row * src_ld + col];
+            if (scale) v = __fmul_rn(v, scale[row]);
+        }
+        dst[i] = col < dim ? T::narrow(v) : (uint16_t)0;
     }
 }
 
-// The tile program for 16-bit and 8-bit operands: v_mfma_f32_32x32x16_f16 / _bf16 / v_mfma_i32_32x32x32_i8.  Lane
-// (r = l & 31, h = l >> 5) holds 16 consecutive bytes of row r of A and the same of B -- for 16-bit values
-// A[row r][k = 8 h .. 8 h + 7]: both matrices are row-major [n][d] and the product is A . B^T, so every
-// fragment is one ds_read_b128, no transposed read.  A k-chunk is 128 B of a row (64 16-bit values, 128 int8 values):
-// what 32 floats are, so the staging (8 lanes x 16 B per row), the LDS image (rows of 144 B: ds_write_b128 and
-// ds_read_b128 conflict-free, see the fp32 program) and the software pipeline (chunk c + 2 into registers, chunk c + 1 into
-// the other LDS buffer, one barrier per chunk, clamped edge rows) are those of k5_gemm_panel_pipe.  What changes is the MFMA
-// count -- a fragment feeds ONE instruction instead of four -- and with it the balance: at 128 x 128 tiles with 64 x 64 per
-// wave, the MFMAs, the LDS (one ds_read_b128 per MFMA) and the CU's 64 B / clk of global loads each need the same 1024 cycles
-// per chunk and CU, and the program ran at 0.23 of the MFMA peak (measured).  So the tile is 256 x 256:
-// 8 waves of 128 x 64 (eight accumulators), 6 fragment reads per 8 MFMAs, half the LDS stores and global bytes per flop:
-// 0.28 - 0.29.  147 456 B of LDS and 512 threads: ONE workgroup per CU, two waves per SIMD.  The epilogue sees a wave's
-// 128 x 64 as the halves wm = 0, 64 of a 128 x 128 tile.  d: the row pitch in values, a multiple of the k-chunk.
+// The tile program for 16-bit and 8-bit operands: the workgroup -> tile deal, the main loop of k5_core.h (k5_tile_loop16, which
+// K22's threshold search runs too: 256 x 256 tiles, 8 waves of 128 x 64), then the common end, which sees a wave's 128 x 64 as the
+// halves wm = 0, 64 of a 128 x 128 tile.  d: the row pitch in values, a multiple of the k-chunk.
 template <typename T>
 __device__ __forceinline__ void lp_gemm_tile(const void *__restrict__ A, const void *__restrict__ B,
                                              const float *__restrict__ inv_a, const float *__restrict__ inv_b,
@@ -298,9 +235,6 @@ __device__ __forceinline__ void lp_gemm_tile(const void *__restrict__ A, const v
                                              float *__restrict__ S, int64_t ld, int tiles_m, int tiles_n,
                                              float *__restrict__ M, int64_t ldm)
 {
-    constexpr int CB = kChunkBytes, LD = 144, NP = 4;       // LD: LDS row pitch in bytes
-    __shared__ __attribute__((aligned(16))) unsigned char As[2][kTile16 * LD];
-    __shared__ __attribute__((aligned(16))) unsigned char Bs[2][kTile16 * LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // workgroup -> tile: consecutive workgroup ids go round-robin over the 8 XCDs; the 32 workgroups an XCD runs at a time (one
     // per CU) get one block of 8 x 4 tiles: 8 A + 4 B tiles (4.7 MB at d = 768 16-bit values) feed 32 tile products out of
@@ -325,74 +259,8 @@ __device__ __forceinline__ void lp_gemm_tile(const void *__restrict__ A, const v
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[h][i][j][r] = 0;
 
-    const int lr = tid >> 3, lb = (tid & 7) * 16;         // staging: 8 threads per tile row, 64 rows per pass
-    const int64_t pitch = d * T::kBytes;                  // bytes per operand row
-    const __amdgpu_buffer_rsrc_t resA =
-        __builtin_amdgcn_make_buffer_rsrc((void *)((const unsigned char *)A + row0 * pitch), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t resB =
-        __builtin_amdgcn_make_buffer_rsrc((void *)((const unsigned char *)B + col0 * pitch), 0, 0x7fffffff, 0x00020000);
-    uint32_t offA[NP], offB[NP];
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {        // rows beyond the edge are clamped to the last row (their products are not stored)
-        offA[p] = (uint32_t)((min(row0 + lr + p * 64, a1 - 1) - row0) * pitch + lb);
-        offB[p] = (uint32_t)((min(col0 + lr + p * 64, n_b - 1) - col0) * pitch + lb);
-    }
-    u32x4 ra[NP], rb[NP];
-    auto load = [&](int p, int kb) {      // kb: byte offset of the chunk in a row
-        ra[p] = __builtin_amdgcn_raw_buffer_load_b128(resA, offA[p], kb, 0);
-        rb[p] = __builtin_amdgcn_raw_buffer_load_b128(resB, offB[p], kb, 0);
-    };
-    auto stage = [&](int p, int buf) {
-        *(u32x4 *)(As[buf] + (lr + p * 64) * LD + lb) = ra[p];
-        *(u32x4 *)(Bs[buf] + (lr + p * 64) * LD + lb) = rb[p];
-    };
-#pragma unroll
-    for (int p = 0; p < NP; ++p) load(p, 0);
-#pragma unroll
-    for (int p = 0; p < NP; ++p) stage(p, 0);
-    const int dk = (int)pitch;
-#pragma unroll
-    for (int p = 0; p < NP; ++p) load(p, min(CB, dk - CB));
-    __syncthreads();
+    k5_tile_loop16<T>(A, B, row0, col0, a1, n_b, d, tid, lane, vr, vc, wn, acc);
 
-    const int frag_off = (lane & 31) * LD + 16 * (lane >> 5);
-    int cur = 0;
-    for (int k0 = 0; k0 < dk; k0 += CB) {
-        const int k2 = min(k0 + 2 * CB, dk - CB);      // (the last two chunks re-fetch the last one: no branches in the loop)
-        const unsigned char *ap = As[cur] + vr * 128 * LD + frag_off, *bp = Bs[cur] + (vc * 128 + wn) * LD + frag_off;
-        auto frag = [&](int s, u32x4 (&a)[4], u32x4 (&b)[2]) {      // MFMA step s: bytes 32 s + 16 h .. + 15 of the chunk
-#pragma unroll
-            for (int i = 0; i < 4; ++i) a[i] = *(const u32x4 *)(ap + i * 32 * LD + 32 * s);
-#pragma unroll
-            for (int j = 0; j < 2; ++j) b[j] = *(const u32x4 *)(bp + j * 32 * LD + 32 * s);
-        };
-        auto mfma4 = [&](const u32x4 (&a)[4], const u32x4 (&b)[2], int h) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[h][i][j] = T::mfma(a[2 * h + i], b[j], acc[h][i][j]);
-        };
-        // one operand pair per four MFMAs: items 0..3 store chunk c + 1 (in registers since the previous chunk) to the other
-        // LDS buffer, items 4..7 fetch chunk c + 2 into the registers just freed
-        auto item = [&](int it) {
-            if (it < 4) stage(it, cur ^ 1);
-            else load(it - 4, k2);
-        };
-        u32x4 fa[2][4], fb[2][2];
-        frag(0, fa[0], fb[0]);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            if (s + 1 < 4) frag(s + 1, fa[(s + 1) & 1], fb[(s + 1) & 1]);      // fragments are read one step (8 MFMAs) ahead
-            __builtin_amdgcn_sched_barrier(0);
-            mfma4(fa[s & 1], fb[s & 1], 0);
-            item(2 * s);
-            __builtin_amdgcn_sched_barrier(0);
-            mfma4(fa[s & 1], fb[s & 1], 1);
-            item(2 * s + 1);
-        }
-        __syncthreads();
-        cur ^= 1;
-    }
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         if constexpr (T::kBytes == 1) {
@@ -791,7 +659,6 @@ __global__ __launch_bounds__(256) void k5_rescore_topn(const float *__restrict__
     __shared__ __attribute__((aligned(16))) uint64_t keys[kRescoreMax];
     __shared__ __attribute__((aligned(16))) float xs[kRowInLds ? kRescoreLds : 4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int64_t row = blockIdx.x; row < n_a; row += gridDim.x) {
         const float *xa = A + row * ld;
         if (kRowInLds) {
@@ -804,29 +671,7 @@ __global__ __launch_bounds__(256) void k5_rescore_topn(const float *__restrict__
             const int32_t j = __builtin_amdgcn_readfirstlane(c[slot]);
             uint64_t key = 0ull;
             if (j >= 0 && j < n_b) {
-                const float *xb = B + (int64_t)j * ld;
-                double acc = 0.0;
-                for (int64_t k0 = 0; k0 < ld; k0 += 1024) {      // four 1 KiB loads of the to-row in flight per wave
-                    float4 a[4], b[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int64_t k = k0 + u * 256 + lane * 4;
-                        const bool in = k < ld;
-                        b[u] = in ? *(const float4 *)(xb + k) : zero;
-                        if (kRowInLds) a[u] = in ? *(const float4 *)(xs + k) : zero;
-                        else a[u] = in ? *(const float4 *)(xa + k) : zero;
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        acc = fma((double)a[u].x, (double)b[u].x, acc);
-                        acc = fma((double)a[u].y, (double)b[u].y, acc);
-                        acc = fma((double)a[u].z, (double)b[u].z, acc);
-                        acc = fma((double)a[u].w, (double)b[u].w, acc);
-                    }
-                }
-#pragma unroll
-                for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
-                const float s = (float)(fa * (double)inv_b[j] * acc);
+                const float s = k5_pair_score(kRowInLds ? xs : xa, B + (int64_t)j * ld, ld, fa, (double)inv_b[j], lane);
                 if (s > lower_bound) key = ((uint64_t)__float_as_uint(s) << 32) | (uint32_t)(~(uint32_t)j);
             }
             if (lane == 0) keys[slot] = key;
@@ -1109,7 +954,7 @@ static int dense_create(pfz_ctx *ctx, const char *who, const void *vec, int64_t 
             else {
                 const int64_t blocks = std::min<int64_t>((n * ld + 255) / 256, 65536);
                 hipLaunchKernelGGL(dtype == PFZ_DENSE_F16 ? k5_round16<f16> : k5_round16<bf16>, dim3((unsigned)blocks), dim3(256), 0,
-                                   ctx->stream, (const float *)tmp.p, n, dim, ld, (uint16_t *)m->x);
+                                   ctx->stream, (const float *)tmp.p, n, dim, dim, ld, (const float *)nullptr, (uint16_t *)m->x);
             }
             PFZ_HIP(hipGetLastError());
         }
@@ -1176,6 +1021,38 @@ int pfz_dense_upload8(pfz_ctx *ctx, const void *vec, int64_t n, int64_t dim, int
 int pfz_dense_upload1(pfz_ctx *ctx, const void *vec, int64_t n, int64_t dim_bits, int32_t normalize, int32_t source, pfz_dense **out)
 {
     return dense_create(ctx, "pfz_dense_upload1", vec, n, dim_bits, normalize, PFZ_DENSE_B1, source, out);
+}
+
+int pfz_dense_derive16(pfz_ctx *ctx, const pfz_dense *exact, int32_t dtype, pfz_dense **out)
+{
+    PFZ_REQUIRE(ctx && exact && out, "pfz_dense_derive16: NULL argument");
+    PFZ_REQUIRE(dtype == PFZ_DENSE_F16 || dtype == PFZ_DENSE_BF16, "pfz_dense_derive16: dtype %d is neither PFZ_DENSE_F16 nor PFZ_DENSE_BF16",
+                dtype);
+    PFZ_REQUIRE(exact->dtype == PFZ_DENSE_F32 && exact->normalize,
+                "pfz_dense_derive16: the vectors are %s, uploaded with normalize = %d; the search copy is derived from fp32 vectors "
+                "uploaded with normalize = 1 (pfz_dense_upload)", dense_dtype_name(exact->dtype), exact->normalize);
+    PFZ_HIP(hipSetDevice(ctx->device));
+    Owner<pfz_dense, pfz_dense_free> m(new pfz_dense());
+    const int64_t n = exact->n, chunk = kChunkBytes / f16::kBytes;
+    m->ctx = ctx;
+    m->n = n;
+    m->dim = exact->dim;
+    m->dtype = dtype;
+    m->normalize = 1;
+    const int64_t ld = m->ld = (exact->dim + chunk - 1) / chunk * chunk;
+    PFZ_TRY(pool_alloc(ctx, &m->x, (size_t)(n > 0 ? n : 1) * (size_t)ld * (size_t)f16::kBytes));
+    PFZ_TRY(pool_alloc(ctx, &m->inv, (size_t)(n > 0 ? n : 1) * sizeof(float)));
+    if (n > 0) {
+        const int64_t blocks = std::min<int64_t>((n * ld + 255) / 256, 65536);
+        hipLaunchKernelGGL(dtype == PFZ_DENSE_F16 ? k5_round16<f16> : k5_round16<bf16>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream,
+                           (const float *)exact->x, n, exact->dim, exact->ld, ld, (const float *)exact->inv, (uint16_t *)m->x);
+        PFZ_HIP(hipGetLastError());
+        hipLaunchKernelGGL(dtype == PFZ_DENSE_F16 ? k5_inv_norms<f16> : k5_inv_norms<bf16>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0,
+                           ctx->stream, (const void *)m->x, n, ld, m->inv, 1, 0);
+        PFZ_HIP(hipGetLastError());
+    }
+    *out = m.release();
+    return PFZ_OK;
 }
 
 int pfz_dense_dtype(const pfz_dense *m, int32_t *dtype)

@@ -98,8 +98,21 @@ class Embeddings(BaseMatcher):
                    to-side of the rescoring is resident like the coarse one and re-made when `rescore_to` or the to-side
                    changes.
 
+        search_dtype: None (default: `join` and `components` run K14, the fp32 tile kernel) or "bfloat16" / "float16":
+                   `m = Embeddings(...); m.search_dtype = "bfloat16"`.  `join` and `components` then upload the fp32 vectors once,
+                   derive a 16-bit search copy on the device (every row scaled to unit length, then rounded to nearest even),
+                   find candidates on the 16-bit matrix cores and score every candidate on the fp32 vectors (K22).  A threshold
+                   makes that exact, which a top-n is not: rounding moves a cosine by at most a known margin (0.0079 for
+                   bfloat16, 0.0011 for float16 at width 768; _lib.dense_search_margin), the search runs that far below
+                   min_similarity, and the exact score decides -- every pair at or above the threshold is found, and there is no
+                   multiplier to choose.  Similarity is the exact score of `rescore_multiplier`'s second stage: a float64 sum
+                   rounded to float32 once, symmetric in the two rows; it may differ from K14's fp32-summed score in the last
+                   bits, so a pair within float32 rounding of the threshold can fall on the other side.  `match` raises ValueError
+                   while it is set.  Anything else raises ValueError when assigned; kept through pickling.
+
     Beside `match` (each string's best): `join` -- every pair whose cosine is at least a threshold -- and `components` -- the
-    near-duplicate clusters of one list -- on fp32 vectors (K14); see the two methods.
+    near-duplicate clusters of one list -- on fp32 vectors (K14), or searched in 16 bits and scored in fp32 (K22, `search_dtype`);
+    see the two methods.
     """
     def __init__(self,
                  embedding_method: Optional[Callable[[List[str]], np.ndarray]] = None,
@@ -127,6 +140,7 @@ class Embeddings(BaseMatcher):
         self._binary = None
         self._rescore_to = None
         self._dev_to_exact_form = None  # what _dev_to_exact holds: "float32", or the checked rescore_to it was made for
+        self._search_dtype = None
 
     @property
     def compute_dtype(self) -> Optional[str]:
@@ -170,6 +184,16 @@ class Embeddings(BaseMatcher):
         _lib.check_rescore_to(value)
         self._rescore_to = value
 
+    @property
+    def search_dtype(self) -> Optional[str]:
+        return self._search_dtype
+
+    @search_dtype.setter
+    def search_dtype(self, value: Optional[str]):
+        if value is not None and value not in ("bfloat16", "float16"):
+            raise ValueError(f"search_dtype must be None, 'bfloat16' or 'float16', got {value!r}")
+        self._search_dtype = value
+
     def match(self,
               from_list: List[str],
               to_list: List[str] = None,
@@ -178,6 +202,10 @@ class Embeddings(BaseMatcher):
               re_train: bool = True) -> pd.DataFrame:
         """ Matches the two lists of strings to each other and returns the best mapping
         (reference _embeddings.py:87-135) """
+        if self.search_dtype is not None:
+            raise ValueError(f"search_dtype={self.search_dtype!r} is the 16-bit search of join and components, where a threshold "
+                             "makes it exact; match's own two-stage route is compute_dtype + rescore_multiplier (leave "
+                             "search_dtype at None)")
         if not isinstance(embeddings_from, np.ndarray):
             embeddings_from = self._embed(from_list)
         explicit_to = isinstance(embeddings_to, np.ndarray)     # the caller's own to-side always wins (_embeddings.py:117-133)
@@ -311,7 +339,11 @@ class Embeddings(BaseMatcher):
         embedding_method embeds the lists.  min_similarity: a number in [0, 1] (ValueError otherwise).  `precision`, `binary`,
         a 16-bit `compute_dtype`, `rescore_multiplier` and `rescore_to` must be unset (ValueError): the threshold kernels take
         fp32 operands only.  The frame has the columns single_linkage reads; for the clusters of the self-join's graph see
-        `components`, which never builds the frame.  Sets last_timings and last_counts = {"pairs": hits}. """
+        `components`, which never builds the frame.  Sets last_timings and last_counts = {"pairs": hits}.
+
+        With `search_dtype` set the pairs are found by K22 instead -- a 16-bit search below the threshold by the rounding margin,
+        every candidate scored exactly on the fp32 vectors: the same frame, order and self-join rule; Similarity is the float64-summed
+        score, and last_counts has "candidates" (what the search handed to the scoring) beside "pairs". """
         self._threshold_operands_only("join", min_similarity)
         if to_list is None and isinstance(embeddings_to, np.ndarray):
             raise ValueError("embeddings_to is given without a to_list: the self-join has one list and one matrix, embeddings_from")
@@ -323,7 +355,12 @@ class Embeddings(BaseMatcher):
         ctx = _lib.Context.default()
         f_dev = _lib.DeviceDense.upload(ctx, vec_from, True)
         t_dev = None if vec_to is None else _lib.DeviceDense.upload(ctx, vec_to, True)
-        row_ptr, idx, sim, counts = _lib.dense_join(ctx, f_dev, t_dev, float(min_similarity))
+        if self.search_dtype is None:
+            row_ptr, idx, sim, counts = _lib.dense_join(ctx, f_dev, t_dev, float(min_similarity))
+        else:
+            row_ptr, idx, sim, counts = _lib.dense_join16(ctx, f_dev.derive16(self.search_dtype),
+                                                          None if t_dev is None else t_dev.derive16(self.search_dtype), f_dev, t_dev,
+                                                          float(min_similarity))
         t1 = time.perf_counter()
         names = from_list if to_list is None else to_list
         frm = np.repeat(np.arange(len(from_list), dtype=np.int32), np.diff(row_ptr))
@@ -344,14 +381,24 @@ class Embeddings(BaseMatcher):
         single_linkage returns.
 
         embeddings: ready-made row vectors, else the embedding_method embeds the list.  Refusals as `join`.  Sets last_timings
-        and last_counts = {"pairs": hits, "components": components}. """
+        and last_counts = {"pairs": hits, "components": components}.
+
+        With `search_dtype` set (K22) the candidates of the 16-bit search are stored before they are scored: device memory beyond
+        the vectors is O(candidates) then, and last_counts has "candidates" too. """
         self._threshold_operands_only("components", min_similarity)
         vec = self._vectors(strings, embeddings, "embeddings")
         t0 = time.perf_counter()
         ctx = _lib.Context.default()
-        label, pairs, components = _lib.dense_components(ctx, _lib.DeviceDense.upload(ctx, vec, True), float(min_similarity))
+        dev = _lib.DeviceDense.upload(ctx, vec, True)
+        if self.search_dtype is None:
+            label, pairs, components = _lib.dense_components(ctx, dev, float(min_similarity))
+            counts = {"pairs": pairs, "components": components}
+        else:
+            label, pairs, components, work = _lib.dense_components16(ctx, dev.derive16(self.search_dtype), dev, float(min_similarity),
+                                                                     counters=True)
+            counts = {"pairs": pairs, "components": components, "candidates": work["candidates"]}
         self.last_timings = {"device": (time.perf_counter() - t0) * 1e3, "frame": 0.0}
-        self.last_counts = {"pairs": pairs, "components": components}
+        self.last_counts = counts
         return label
 
     # a matcher is pickled by joblib (reference polyfuzz.py:429-457): the device copy stays behind
@@ -366,6 +413,7 @@ class Embeddings(BaseMatcher):
         self.__dict__.setdefault("_binary", None)
         self.__dict__.setdefault("_rescore_to", None)
         self.__dict__.setdefault("_dev_to_exact_form", None)
+        self.__dict__.setdefault("_search_dtype", None)
         self._dev_to = None
         self._dev_to_exact = None
 
