@@ -956,6 +956,35 @@ int pfz_dense_join16(pfz_ctx *ctx, const pfz_dense *from16, const pfz_dense *to1
 int pfz_dense_components16(pfz_ctx *ctx, const pfz_dense *v16, const pfz_dense *v32, double min_similarity, int64_t cand_capacity,
                            int32_t *out_label, int64_t *out_pairs, int64_t *out_components, int64_t *out_counters);
 
+/* ---- K23: all pairs of binary codes within a Hamming distance, and their components --
+ * The threshold form of the 1-bit operator: every pair (from i, to j) of PFZ_DENSE_B1 rows (pfz_dense_upload1) of equal dim_bits
+ * that differ in h <= max_distance bits -- SimHash near-duplicates, perceptual hashes, de-duplication of a corpus kept as
+ * "ubinary" embeddings.  The tiles are k5_hamming_panel's (128 x 128, XOR / popcount on the vector ALU); the comparison is made
+ * on the integer counts in registers, so no score panel is written, nothing is divided and the result is exact.  The entries
+ * threshold h itself and do not read the handles' `normalize`.
+ * to_codes == NULL or == from_codes: the self-join -- only the tiles on or above the diagonal run, and the result holds every pair
+ * i < j once (row i, column j), never (i, i); equal codes at different positions are pairs with h = 0.
+ * Output, order, determinism, capacity, *out_total and the repeat protocol are pfz_dense_join's, with out_dist[p] = the pair's h in
+ * place of a score; out_counters: NULL, or int64[2] -- [0] the 128 x 128 tiles executed, [1] the waves (32 rows x 128 columns) that
+ * held a hit (the others left without touching memory).  An empty list on either side: PFZ_OK, *out_total = 0, out_row_ptr all
+ * zero.  PFZ_ERR_INVALID: an operand of another type (the message names it), unequal widths, max_distance outside [0, dim_bits],
+ * capacity < 0; PFZ_ERR_UNSUPPORTED: 2^31 rows or more in a list, more than 2^31 tiles in one call.  Profiling scopes: `k23_join`
+ * (the tile kernel), `k23_sort_unpack`.  Blocks. */
+int pfz_hamming_join(pfz_ctx *ctx, const pfz_dense *from_codes, const pfz_dense *to_codes, int64_t max_distance, int64_t capacity,
+                     int64_t *out_row_ptr, int32_t *out_idx, int32_t *out_dist, int64_t *out_total, int64_t *out_counters);
+/* The connected components of "h <= max_distance" over ONE list: the pairs of pfz_hamming_join(ctx, codes, NULL, max_distance,
+ * ...), found by the same tiles and united in the union-find of csrc/k12_core.h; none is stored.  Labels, *out_pairs,
+ * *out_components, the empty list and the NULL rules as pfz_dense_components; operands, limits and errors as pfz_hamming_join;
+ * out_counters as above.  Profiling scope: `k23_components` (forest, tile kernel and labels).  Blocks. */
+int pfz_hamming_components(pfz_ctx *ctx, const pfz_dense *codes, int64_t max_distance, int32_t *out_label, int64_t *out_pairs,
+                           int64_t *out_components, int64_t *out_counters);
+/* The distance that stands for a similarity: *out_max_distance = the largest h in [0, dim_bits] for which the score
+ * pfz_dense_topn reports for normalised 1-bit operands, (double)(float(dim_bits - 2 h) / float(dim_bits)), is >= min_similarity
+ * (compared as pfz_dense_join compares: float64, equal is kept); -1 if no h passes.  Found by evaluating that rule, not by a
+ * closed form.  A pure host function: no device is touched.  PFZ_ERR_INVALID: dim_bits outside [1, 2^24), a NaN min_similarity
+ * or one outside [0, 1]. */
+int pfz_hamming_max_distance(int64_t dim_bits, double min_similarity, int64_t *out_max_distance);
+
 /* ---- K15: all pairs at or above a sparse cosine, and their components -----------
  * The threshold form of K3, what de-duplication asks of the reference's TF-IDF matcher: every pair (from-row i, to-row j) whose
  * cosine is >= min_similarity, however many partners a row has -- no top_n to guess, no n x top_n table.  to_index is the

@@ -141,6 +141,9 @@ SIGNATURES = {
     "pfz_dense_components": (ctypes.c_int, [c_vp, c_vp, c_f64, c_vp, P(c_i64), P(c_i64), c_vp]),
     "pfz_dense_derive16": (ctypes.c_int, [c_vp, c_vp, c_i32, P(c_vp)]),
     "pfz_dense_search_margin": (ctypes.c_int, [c_i32, c_i64, P(c_f64)]),
+    "pfz_hamming_join": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, P(c_i64), c_vp]),
+    "pfz_hamming_components": (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp, P(c_i64), P(c_i64), c_vp]),
+    "pfz_hamming_max_distance": (ctypes.c_int, [c_i64, c_f64, P(c_i64)]),
     "pfz_dense_join16": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_f64, c_i64, c_i64, c_vp, c_vp, c_vp, P(c_i64), c_vp]),
     "pfz_dense_components16": (ctypes.c_int, [c_vp, c_vp, c_vp, c_f64, c_i64, c_vp, P(c_i64), P(c_i64), c_vp]),
     "pfz_cossim_join": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_f64, c_i64, c_vp, c_vp, c_vp, P(c_i64), c_vp]),
@@ -1295,6 +1298,61 @@ def dense_components(ctx, dev, min_similarity, counters=False):
     _dense_join_operand(dev, "the vectors")
     return _components_call(dev.n, DENSE_JOIN_COUNTERS, counters, lambda label, pairs, components, wk: ctx.lib.pfz_dense_components(
         ctx.h, dev.h, float(min_similarity), label, pairs, components, wk))
+
+
+# ---- K23: all pairs of binary codes within a Hamming distance, and their components ------------------------------------
+
+HAMMING_JOIN_COUNTERS = ("tiles", "hit_waves")      # pfz_hamming_join's out_counters, in order
+
+
+def _hamming_join_operand(dev, what):
+    if dev.dtype != BINARY:
+        raise ValueError(f"{what} are {dev.dtype} vectors: the Hamming threshold kernels take binary operands only "
+                         "(DeviceDense.upload_bits)")
+
+
+def hamming_max_distance(dim_bits, min_similarity):
+    """The largest h in [0, dim_bits] for which the score of two codes that differ in h bits --
+    float32(dim_bits - 2 h) / float32(dim_bits), what dense_topn reports for normalised bit handles -- is >= min_similarity as
+    float64 (equal is kept); -1 if there is none.  The library evaluates the rule itself (no closed form).  Its own host
+    function: no device is touched.  dim_bits in [1, 2**24), min_similarity a number in [0, 1]: ValueError otherwise."""
+    if isinstance(dim_bits, bool) or not isinstance(dim_bits, (int, np.integer)) or not 1 <= int(dim_bits) < 1 << 24:
+        raise ValueError(f"dim_bits must be an integer in [1, 2**24), not {dim_bits!r}")
+    h = c_i64(0)
+    check(load().pfz_hamming_max_distance(int(dim_bits), check_min_similarity(min_similarity), ctypes.byref(h)))
+    return h.value
+
+
+def hamming_similarity(dist, dim_bits):
+    """The float32 scores of Hamming distances at dim_bits bits: (float32(d) - 2 dist) / float32(d), one IEEE division -- the bits
+    of k5_hamming_panel's scores (d < 2**24: numerator and denominator are exact).  Pure numpy."""
+    d = np.float32(dim_bits)
+    return ((d - np.float32(2) * np.asarray(dist).astype(np.float32)) / d).astype(np.float32)
+
+
+def hamming_join(ctx, from_dev, to_dev, max_distance, capacity=None, counters=False):
+    """K23: every pair of rows of two bit handles of equal width that differ in at most max_distance bits, as CSR over the
+    from-rows: (row_ptr int64[n + 1], to-index int32[hits] ascending within a row, distance int32[hits], counts).  to_dev None
+    (or from_dev itself): the self-join, every unordered pair once as (i, j), i < j, only the tiles on or above the diagonal
+    computed.  Exact: the comparison is made on the integer bit counts.  capacity and the ONE repeat as dense_join.  counts:
+    {"pairs": hits}, with counters=True also HAMMING_JOIN_COUNTERS (the last call's)."""
+    _hamming_join_operand(from_dev, "the from-codes")
+    if to_dev is not None:
+        _hamming_join_operand(to_dev, "the to-codes")
+    to_h = None if to_dev is None else to_dev.h
+    row_ptr, hits, n, work = _join_call(
+        from_dev.n, capacity, (np.int32, np.int32), HAMMING_JOIN_COUNTERS, counters,
+        lambda cap, ptr, hit, total, wk: ctx.lib.pfz_hamming_join(ctx.h, from_dev.h, to_h, int(max_distance), cap, ptr, *hit, total, wk))
+    return (row_ptr,) + hits + ({"pairs": n, **(work or {})},)
+
+
+def hamming_components(ctx, dev, max_distance, counters=False):
+    """K23: the connected components of "at most max_distance differing bits" over the rows of the bit handle `dev` (the pairs of
+    hamming_join's self-join, united on the device, never stored) -- (label int32[n], pairs, components) as dense_components.
+    counters=True appends a dict of HAMMING_JOIN_COUNTERS."""
+    _hamming_join_operand(dev, "the codes")
+    return _components_call(dev.n, HAMMING_JOIN_COUNTERS, counters, lambda label, pairs, components, wk: ctx.lib.pfz_hamming_components(
+        ctx.h, dev.h, int(max_distance), label, pairs, components, wk))
 
 
 # ---- K22: the same two entries searched on the 16-bit matrix cores, scored exactly on the fp32 vectors -------------------

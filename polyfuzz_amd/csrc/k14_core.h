@@ -21,9 +21,10 @@ struct DenseJoinArgs {
     int32_t self;
     int32_t wg_base;                   // the number, in the call's 1-D deal, of this launch's first workgroup (k14_launch)
     float t32;
-    unsigned long long *state;         // [0] hits, [1] tiles executed, [2] 64 x 64 wave corners that held a hit
+    int32_t hmax;                      // K23 (k23_core.h) only: a pair is a hit iff its Hamming distance is <= hmax; A, B: packed bits, d: bytes a row
+    unsigned long long *state;         // [0] hits, [1] tiles executed, [2] 64 x 64 wave corners that held a hit (K23: the same three, a line apart, k23_core.h)
     uint64_t *keys;                    // join: [capacity] row << 32 | col, in the order the waves got there ...
-    float *vals;                       // ... and the scores beside them (kSinkKeys: NULL, no score is kept)
+    float *vals;                       // ... and the scores beside them (kSinkKeys: NULL, no score is kept; K23: the int32 distances)
     unsigned long long capacity;
     int32_t *parent;                   // components: [n_a] the forest (k12_core.h)
 };

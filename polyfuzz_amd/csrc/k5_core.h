@@ -1,7 +1,8 @@
 // What the dense kernels share: the operand handle; the fp32 tile program's main loop -- k5_gemm_panel_pipe (k5_dense.hip)
 // and the threshold kernels of K14 (k14_dense_join.hip) run the same loop and differ in what they do with the accumulators --;
 // the operand traits and the main loop of the 16-bit / 8-bit tile program -- k5_gemm16_panel, k5_gemm8_panel and K22's threshold
-// search (k22_dense_join16.hip) --; and the exact float64-summed score of one pair of fp32 rows (k5_rescore_topn, K22's rescoring).
+// search (k22_dense_join16.hip) --; the XOR / popcount main loop of the 1-bit tile program -- k5_hamming_panel and K23's threshold
+// kernels (k23_hamming_join.hip) --; and the exact float64-summed score of one pair of fp32 rows (k5_rescore_topn, K22's rescoring).
 #pragma once
 
 #include "pfz_internal.h"
@@ -291,6 +292,63 @@ __device__ __forceinline__ void k5_tile_loop16(const void *__restrict__ A, const
         }
         __syncthreads();
         cur ^= 1;
+    }
+}
+
+// The main loop of the tile program for two 1-bit operands, on the vector ALU (there is no matrix instruction for XOR /
+// popcount): k5_hamming_panel (k5_dense.hip) and the threshold kernels of K23 (k23_hamming_join.hip) run it and differ in what
+// they do with the counts.  A workgroup of 256 threads owns a 128 x 128 tile.  Both row sets are staged in LDS as 32-bit words,
+// a chunk of 128 B of every row at a time (a whole row at dim <= 1024), rows of 36 words (ds_write_b128 / ds_read_b128, see the
+// fp32 program); rows beyond the edge (a1, n_b) are clamped to the last row (the caller does not use their counts).  Thread
+// (tx = tid & 31, ty = tid >> 5) has the differing bits of row row0 + ty + 8 i and column col0 + tx + 32 j ADDED to h[i][j] (the
+// caller clears h, as k5_tile_loop's callers clear acc: cleared in here, k5_hamming_panel took 185 registers instead of 122): per 16
+// bytes of k it reads four B pieces, and for each of its 16 rows one A piece (two addresses per wave: a broadcast) that meets
+// all four -- 20 LDS reads for 256 XORs and 256 v_bcnt_u32_b32, which add the bit count into the running count.  The words of a
+// row are XORed in whatever order they lie in: both sides lie the same way.  pitch: bytes per operand row, whole 16-byte pieces.
+// All 256 threads of the workgroup call it (it has barriers); 36 864 B of LDS.
+__device__ __forceinline__ void k5_hamming_loop(const void *__restrict__ A, const void *__restrict__ B, int64_t row0, int64_t col0,
+                                                int64_t a1, int64_t n_b, int64_t pitch, int tid, int tx, int ty, int (&h)[16][4])
+{
+    constexpr int LD = 36, NP = 4;                       // LDS row pitch in words; staging passes of 32 rows
+    __shared__ __attribute__((aligned(16))) uint32_t As[kTile * LD];
+    __shared__ __attribute__((aligned(16))) uint32_t Bs[kTile * LD];
+    const int lr = tid >> 3, lb = (tid & 7) * 16;         // staging: 8 threads per tile row, 32 rows per pass
+    const unsigned char *pa[NP], *pb[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {        // rows beyond the edge are clamped to the last row (their counts are not stored)
+        pa[p] = (const unsigned char *)A + min(row0 + lr + p * 32, a1 - 1) * pitch + lb;
+        pb[p] = (const unsigned char *)B + min(col0 + lr + p * 32, n_b - 1) * pitch + lb;
+    }
+    const u32x4 zero4 = {0u, 0u, 0u, 0u};
+    for (int64_t kb = 0; kb < pitch; kb += kChunkBytes) {
+        const bool in = kb + lb < pitch;                  // (a 16-byte piece is inside the row or beyond it: pitch is whole pieces)
+        u32x4 ra[NP], rb[NP];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            ra[p] = in ? *(const u32x4 *)(pa[p] + kb) : zero4;
+            rb[p] = in ? *(const u32x4 *)(pb[p] + kb) : zero4;
+        }
+        if (kb) __syncthreads();                          // the chunk before has been counted
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            *(u32x4 *)(As + (lr + p * 32) * LD + lb / 4) = ra[p];
+            *(u32x4 *)(Bs + (lr + p * 32) * LD + lb / 4) = rb[p];
+        }
+        __syncthreads();
+        const int pieces = (int)(min((int64_t)kChunkBytes, pitch - kb) / 16);
+        for (int q = 0; q < pieces; ++q) {
+            u32x4 b[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) b[j] = *(const u32x4 *)(Bs + (tx + 32 * j) * LD + 4 * q);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const u32x4 a = *(const u32x4 *)(As + (ty + 8 * i) * LD + 4 * q);
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    h[i][j] += __builtin_popcount(a.x ^ b[j].x) + __builtin_popcount(a.y ^ b[j].y) +
+                               __builtin_popcount(a.z ^ b[j].z) + __builtin_popcount(a.w ^ b[j].w);
+            }
+        }
     }
 }
 

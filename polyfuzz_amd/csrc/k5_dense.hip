@@ -356,14 +356,9 @@ __global__ __launch_bounds__(256) void k5_pack_signs(const float *__restrict__ s
 // What k5_hamming_panel gets in the tile programs' `d` argument: the bit count, and bit 32 set for the normalised score.
 __host__ __device__ inline int64_t b1_arg(int64_t dim_bits, int32_t normalize) { return dim_bits | ((int64_t)(normalize ? 1 : 0) << 32); }
 
-// The tile program of two 1-bit operands: there is no matrix instruction for XOR / popcount, so this one runs on the vector
-// ALU.  A workgroup of 256 threads owns a 128 x 128 tile.  Both row sets are staged in LDS as 32-bit words, a chunk of 128 B
-// of every row at a time (a whole row at dim <= 1024), rows of 36 words (ds_write_b128 / ds_read_b128, see the fp32 program);
-// edge rows are clamped to the last row (their counts are not stored).  Thread (tx = tid & 31, ty = tid >> 5) keeps the 16 x 4
-// counts of rows ty + 8 i and columns tx + 32 j: per 16 bytes of k it reads four B pieces, and for each of its 16 rows one A
-// piece (two addresses per wave: a broadcast) that meets all four -- 20 LDS reads for 256 XORs and 256 v_bcnt_u32_b32, which
-// add the bit count into the running count.  The words of a row are XORed in whatever order they lie in: both sides lie the
-// same way.  The epilogue turns a count into the score (see above; columns beyond n_b score 0, as in tile_epilogue), stores
+// The tile program of two 1-bit operands: k5_hamming_loop of k5_core.h (the vector ALU's XOR / popcount loop over a 128 x 128
+// tile; thread (tx = tid & 31, ty = tid >> 5) gets the 16 x 4 counts of rows ty + 8 i and columns tx + 32 j), then this end.  The
+// epilogue turns a count into the score (see above; columns beyond n_b score 0, as in tile_epilogue), stores
 // it -- lanes 0..31 of a store cover one 128-B line of a row -- and leaves the block maxima M[row][col / 64] through the same
 // halving exchange as the matrix programs: slot q = 2 i + (j >> 1) of lane (tx, .) is the maximum of row ty + 8 i over the
 // thread's two columns of that 64-column block.
@@ -373,9 +368,6 @@ __global__ __launch_bounds__(256, 2) void k5_hamming_panel(const void *__restric
                                                             float *__restrict__ S, int64_t ld, int tiles_m, int tiles_n,
                                                             float *__restrict__ M, int64_t ldm)
 {
-    constexpr int LD = 36, NP = 4;                       // LDS row pitch in words; staging passes of 32 rows
-    __shared__ __attribute__((aligned(16))) uint32_t As[kTile * LD];
-    __shared__ __attribute__((aligned(16))) uint32_t Bs[kTile * LD];
     const int tid = threadIdx.x, lane = tid & 63;
     // workgroup -> tile: as k5_gemm_panel_pipe (8 x 8 tile blocks dealt round-robin to the XCDs)
     const int w = blockIdx.x, xcd = w & 7, idx = w >> 3, pos = idx & 63;
@@ -394,45 +386,7 @@ __global__ __launch_bounds__(256, 2) void k5_hamming_panel(const void *__restric
     for (int i = 0; i < 16; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) h[i][j] = 0;
-
-    const int lr = tid >> 3, lb = (tid & 7) * 16;         // staging: 8 threads per tile row, 32 rows per pass
-    const unsigned char *pa[NP], *pb[NP];
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {        // rows beyond the edge are clamped to the last row (their counts are not stored)
-        pa[p] = (const unsigned char *)A + min(row0 + lr + p * 32, a1 - 1) * pitch + lb;
-        pb[p] = (const unsigned char *)B + min(col0 + lr + p * 32, n_b - 1) * pitch + lb;
-    }
-    const u32x4 zero4 = {0u, 0u, 0u, 0u};
-    for (int64_t kb = 0; kb < pitch; kb += kChunkBytes) {
-        const bool in = kb + lb < pitch;                  // (a 16-byte piece is inside the row or beyond it: pitch is whole pieces)
-        u32x4 ra[NP], rb[NP];
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            ra[p] = in ? *(const u32x4 *)(pa[p] + kb) : zero4;
-            rb[p] = in ? *(const u32x4 *)(pb[p] + kb) : zero4;
-        }
-        if (kb) __syncthreads();                          // the chunk before has been counted
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            *(u32x4 *)(As + (lr + p * 32) * LD + lb / 4) = ra[p];
-            *(u32x4 *)(Bs + (lr + p * 32) * LD + lb / 4) = rb[p];
-        }
-        __syncthreads();
-        const int pieces = (int)(min((int64_t)kChunkBytes, pitch - kb) / 16);
-        for (int q = 0; q < pieces; ++q) {
-            u32x4 b[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) b[j] = *(const u32x4 *)(Bs + (tx + 32 * j) * LD + 4 * q);
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const u32x4 a = *(const u32x4 *)(As + (ty + 8 * i) * LD + 4 * q);
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    h[i][j] += __builtin_popcount(a.x ^ b[j].x) + __builtin_popcount(a.y ^ b[j].y) +
-                               __builtin_popcount(a.z ^ b[j].z) + __builtin_popcount(a.w ^ b[j].w);
-            }
-        }
-    }
+    k5_hamming_loop(A, B, row0, col0, a1, n_b, pitch, tid, tx, ty, h);
 
     const float fd = (float)bits;
     bool col_ok[4];

@@ -149,7 +149,9 @@ def connected_components(strings: List[str], model,
     set (K17) takes the pairs of the TF-IDF threshold join at that cosine for its candidates instead: equal strings that have an
     n-gram then share a component however many copies the list holds.  Or a RapidFuzz under one of K7's seven scorers (K18; WRatio
     by default): the components of "score >= min_similarity * 100" -- equal strings share one whenever they have a token; under
-    WRatio, min_similarity <= 0.855 links everything that shares a word with a string 1.5 times its length or more."""
+    WRatio, min_similarity <= 0.855 links everything that shares a word with a string 1.5 times its length or more.  Or a Hamming
+    model (K23): `embeddings` are the strings' binary codes, required, and the components are those of "at most h differing bits"
+    for the largest h whose score float32(d - 2 h) / float32(d) reaches min_similarity."""
     strings = list(strings)
     extra = {} if embeddings is None else {"embeddings": embeddings}
     return dicts_from_labels(strings, model.components(strings, min_similarity, **extra))

@@ -6,5 +6,6 @@ from ._rapidfuzz import RapidFuzz
 from ._embeddings import Embeddings
 from ._blocked import BlockedEditDistance
 from ._jaro import JaroWinkler
+from ._hamming import Hamming
 
-__all__ = ["BaseMatcher", "cosine_similarity", "TFIDF", "EditDistance", "RapidFuzz", "Embeddings", "BlockedEditDistance", "JaroWinkler"]
+__all__ = ["BaseMatcher", "cosine_similarity", "TFIDF", "EditDistance", "RapidFuzz", "Embeddings", "BlockedEditDistance", "JaroWinkler", "Hamming"]
