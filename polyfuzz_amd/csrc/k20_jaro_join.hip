@@ -12,11 +12,9 @@
 //   the window   for one la the admissible to-lengths are one run around la (k8_core.h jaro_len_run), found once per call for every
 //                la by the set-up launch; a row's groups are two binary searches over the plan with that run.  A row whose window
 //                is empty never builds its table.
-//   sweep 1      K8's, with the abandon rule once per packed dword: a lane whose matches so far plus the to-characters still to
-//                come (or la) are below its pair's m_need is dead; the wave leaves the sweep when no live lane has characters left.
-//                Behind it the bound again with the pair's own prefix.
-//   sweep 2      for the wave only if a live lane has two matches, left when no live lane has a flagged from-position left; then
-//                the bound with t, then the float64 score and the comparison.
+//   in a group   k8_sweep.h's jaro_pair_above against (float)t, shared with K21: sweep 1 with the abandon rule once per packed
+//                dword and the wave-uniform exit, the bound with the pair's own prefix, sweep 2 only if a live lane has two matches,
+//                the bound with t, the float64 score; then the comparison with t.
 //   Every lane of a wave that enters a group reaches the sink -- padding lanes, lanes not owned and dead lanes with hit = false --
 //   and every exit from a group is wave-uniform.
 // Register kernels: from-strings of <= 32 characters against the groups of <= 32 in 32-bit words; those against the groups of up to
@@ -31,8 +29,8 @@
 // launches over them and the general kernel's buffers are edit_walk.h's.
 #include "edit_walk.h"
 #include "k18_sink.h"
-#include "k8_core.h"
-#include "pair_score.h"
+#include "k8_launch.h"
+#include "k8_sweep.h"
 
 #include <algorithm>
 #include <cmath>
@@ -40,21 +38,11 @@
 
 namespace pfz {
 
-struct JaroJoinArgs : EditView {
-    const int32_t *rows;       // from-rows of this launch
-    int32_t n_rows;
-    int32_t n_to;
-    int32_t g_begin, g_end;    // the to-groups of this launch
+struct JaroJoinArgs : JaroWalkArgs {      // (counters: the pairs are those inside the length window)
     const int32_t *len_run;    // [longest from-string + 1][2] the admissible to-lengths [lo, hi] of a from-string of la characters
-    const void *t_chars;       // the raw to-list, which the general kernel reads (pair_score.h)
-    int32_t t_width;
-    const int64_t *t_off;
     double t;
     float t32;                 // t rounded to float32, what the bounds are held against
-    int32_t winkler;
     int32_t self;
-    unsigned long long *counters;   // optional [4]: pairs inside the length window, pairs alive after sweep 1, pairs scored in
-                                    // float64, sweep-1 to-characters of live lanes
 };
 
 // the set-up launch: the run of every from-length and, where a forest is wanted, every position its own root
@@ -97,31 +85,18 @@ __device__ inline void jaro_window(const JaroJoinArgs &A, bool self, int la, int
     *hi_out = lo;
 }
 
-__device__ inline void jaro_join_count(unsigned long long *counters, unsigned long long w, unsigned long long a, unsigned long long s,
-                                       unsigned long long c)
-{
-    if (!counters) return;
-    wave_count(counters + 0, w);
-    wave_count(counters + 1, a);
-    wave_count(counters + 2, s);
-    wave_count(counters + 3, c);
-}
-
-// WORD: uint32_t (from-strings of <= 32 characters) or uint64_t (<= 64); NB: to-strings of up to NB words' characters (K8's flag
-// registers, walked stretch by stretch with compile-time indices)
+// WORD, IDB, NB: jaro_pair_above's (k8_sweep.h)
 template <typename WORD, int IDB, int NB, typename SINK>
 __global__ __launch_bounds__(256) void k20_join_kernel(JaroJoinArgs A, SINK sink)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     WORD *pm = (WORD *)smem_raw;
-    constexpr int PER = 32 / IDB;  // symbols per dword
-    constexpr int SPW = (int)sizeof(WORD) * 8 / PER;      // dwords per stretch
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool self = A.self != 0;
 
     pm_reg_zero(A, pm, tid, 256);
 
-    unsigned long long n_win = 0, n_alive = 0, n_scored = 0, n_steps = 0;
+    JaroWork work;
     for (int r = blockIdx.x; r < A.n_rows; r += gridDim.x) {
         const int row = A.rows[r];
         const int64_t a0 = A.a_off[row];
@@ -139,65 +114,14 @@ __global__ __launch_bounds__(256) void k20_join_kernel(JaroJoinArgs A, SINK sink
             const int lb = A.b_len[slot];
             bool alive = join_owned(self, row, la, orig, lb) && lb >= len_lo && lb <= len_hi;
             if (!__any(alive)) continue;
-            n_win += alive;
-            const float inv_lb = __builtin_amdgcn_rcpf((float)lb);
-            const int need = jaro_m_need(la, lb, inv_la, inv_lb, A.t32, A.winkler);
-            const int steps = __builtin_amdgcn_readfirstlane(A.g_steps[g]);
-            const uint32_t *gp = A.b_packed + A.g_off[g] + lane;
-            JaroFlags<WORD> s;
-            WORD fb[NB];
-            jaro_begin(s, jaro_range(la, lb));
-            bool go = true;                               // wave-uniform: a live lane has to-characters left
-#pragma unroll
-            for (int k = 0; k < NB; ++k) {
-                s.fb = 0;
-                for (int t = k * SPW; go && t < min(steps, (k + 1) * SPW); ++t) {
-                    const uint32_t pk = gp[(int64_t)t * 64];
-#pragma unroll
-                    for (int q = 0; q < PER; ++q)
-                        jaro_match<WORD>(s, pm[__builtin_amdgcn_ubfe(pk, q * IDB, IDB)], t * PER + q, (t - k * SPW) * PER + q);
-                    const int done = (t + 1) * PER;       // to-characters behind this lane (its own: min(done, lb))
-                    if (alive && done < lb && jaro_dead(la, __popcll((uint64_t)s.fa), lb - done, need)) {
-                        alive = false;
-                        n_steps += done;
-                    }
-                    go = __any(alive && done < lb);
-                }
-                fb[k] = s.fb;
-            }
-            n_steps += alive ? lb : 0;
-            const int m = __popcll((uint64_t)s.fa);
-            const int prefix = jaro_prefix(s.pre);
-            // the bound from m alone, with the pair's own prefix
-            alive = alive && jaro_reaches(m, inv_la, inv_lb, 1.0f, prefix, A.winkler, A.t32);
-            n_alive += alive;
-            int half_t = 0;
-            // (one flagged pair cannot be out of order; the sweep runs for the wave if a single live lane wants it)
-            if (__any(alive && m >= 2)) {
-                go = true;                                // wave-uniform: a live lane has a flagged from-position left
-#pragma unroll
-                for (int k = 0; k < NB; ++k) {
-                    s.fb = fb[k];
-                    for (int t = k * SPW; go && t < min(steps, (k + 1) * SPW); ++t) {
-                        const uint32_t pk = gp[(int64_t)t * 64];
-#pragma unroll
-                        for (int q = 0; q < PER; ++q)
-                            half_t += jaro_transpose<WORD>(s, pm[__builtin_amdgcn_ubfe(pk, q * IDB, IDB)], (t - k * SPW) * PER + q);
-                        go = __any(alive && s.fa != 0);
-                    }
-                }
-            }
-            // the bound again, with t (m = 0: asked before the division's result is)
-            const float last = (float)(m - half_t / 2) * __builtin_amdgcn_rcpf((float)m);
-            alive = alive && jaro_reaches(m, inv_la, inv_lb, last, prefix, A.winkler, A.t32);
-            n_scored += alive;
-            const double sc = alive ? jaro_score(m, half_t, la, lb, prefix, A.winkler) : 0.0;
+            work.pairs += alive;
+            const double sc = jaro_pair_above<WORD, IDB, NB>(A, pm, g, la, lb, inv_la, A.t32, A.winkler, alive, work);
             sink(alive && sc >= A.t, self ? min(row, orig) : row, self ? max(row, orig) : orig, sc);
         }
         __syncthreads();                                  // every wave is done with the match table
         pm_reg_clear(pm, my_sym);
     }
-    jaro_join_count(A.counters, n_win, n_alive, n_scored, n_steps);
+    jaro_work_flush(A.counters, work);
 }
 
 // The general case: any lengths, any alphabet.  The match table of the workgroup's from-string (WA words per symbol) and every
@@ -209,17 +133,8 @@ __global__ __launch_bounds__(256) void k20_join_general_kernel(JaroJoinArgs A, S
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const bool self = A.self != 0;
-    uint64_t *pm = pm_all + (int64_t)blockIdx.x * A.n_sym1 * WA;      // zero on entry, zero again after every row
-    uint64_t *fa = fa_all + ((int64_t)blockIdx.x * 4 + wave) * WA * 64 + lane;      // fa[w * 64]: this lane's word w
-    uint64_t *fb = fb_all + ((int64_t)blockIdx.x * 4 + wave) * WS * 64 + lane;
-    PairView P;
-    static_cast<FromView &>(P) = A;
-    P.b_chars = A.t_chars;
-    P.b_width = A.t_width;
-    P.b_off = A.t_off;
-    P.n_to = A.n_to;
-    P.scorer = A.winkler ? PAIR_JARO_WINKLER : PAIR_JARO;
-    unsigned long long n_win = 0, n_steps = 0;
+    const JaroGeneral G = jaro_general_begin(A, WA, WS, pm_all, fa_all, fb_all);
+    JaroWork work;
     for (int r = blockIdx.x; r < A.n_rows; r += gridDim.x) {
         const int row = A.rows[r];
         const int64_t a0 = A.a_off[row];
@@ -229,23 +144,24 @@ __global__ __launch_bounds__(256) void k20_join_general_kernel(JaroJoinArgs A, S
         int g_lo, g_hi;
         jaro_window(A, self, la, len_lo, len_hi, &g_lo, &g_hi);
         if (g_lo >= g_hi) continue;
-        pm_global_set(A, pm, WA, a0, la, tid, 256);
+        pm_global_set(A, G.pm, WA, a0, la, tid, 256);
         for (int g = g_lo + wave; g < g_hi; g += 4) {
             const int slot = g * 64 + lane;
             const int orig = A.b_orig[slot];
             const int lb = A.b_len[slot];
             const bool alive = join_owned(self, row, la, orig, lb) && lb >= len_lo && lb <= len_hi;
             if (!__any(alive)) continue;
-            n_win += alive;
-            n_steps += alive ? lb : 0;
+            work.pairs += alive;
+            work.steps += alive ? lb : 0;
             double sc = 0.0;
-            if (alive) sc = pair_score_general(P, pm, fa, fb, nullptr, WA, W, la, A.t_off[orig], lb);
+            if (alive) sc = pair_score_general(G.P, G.pm, G.fa, G.fb, nullptr, WA, W, la, A.t_off[orig], lb);
             sink(alive && sc >= A.t, self ? min(row, orig) : row, self ? max(row, orig) : orig, sc);
         }
         __syncthreads();                                              // every wave is done with the match table
-        pm_global_clear(A, pm, WA, a0, la, tid, 256);
+        pm_global_clear(A, G.pm, WA, a0, la, tid, 256);
     }
-    jaro_join_count(A.counters, n_win, n_win, n_win, n_steps);
+    work.alive = work.scored = work.pairs;          // scored to the end, every one
+    jaro_work_flush(A.counters, work);
 }
 
 // The launches of a call on the context's stream: the register kernels over the row classes and their groups (walk_launch), the
@@ -254,19 +170,12 @@ template <typename SINK>
 static int jaro_join_launch(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, const pfz_indel_plan *pl, JaroJoinArgs &A, const SINK &sink,
                             const char *entry, const char *what, const char *scope_general)
 {
-    const int64_t n_to = T->n;
-    const bool lds_fits = lds_table_fits(pl);
-    const RowClasses rc = classify_rows(F, 0, F->n, lds_fits);
+    const RowClasses rc = classify_rows(F, 0, F->n, lds_table_fits(pl));      // (a table beyond LDS: every row is the general kernel's)
     DevBuf d_rows[3];
     PFZ_TRY(rows_upload(ctx, rc, d_rows));
     // the groups are sorted by length: the first g32 / g256 of them hold to-strings of <= 32 / <= 256 characters only
     const int32_t n_groups = (int32_t)pl->n_groups;
-    auto whole_groups_up_to = [&](int64_t len) {
-        int64_t n = 0;
-        for (int64_t j = 0; j < n_to; ++j) n += T->h_off[(size_t)j + 1] - T->h_off[(size_t)j] <= len;
-        return n == n_to ? n_groups : (int32_t)(n / 64);
-    };
-    const int32_t g32 = whole_groups_up_to(32), g256 = whole_groups_up_to(256);
+    const int32_t g32 = whole_groups_up_to(T, pl, 32), g256 = whole_groups_up_to(T, pl, 256);
     const int32_t WS = (int32_t)std::max<int64_t>(1, (T->max_len + 63) / 64);
 
     auto reg_launch = [&](auto word, auto nb, dim3 grid, int32_t g_begin, int32_t g_end) {
@@ -321,10 +230,7 @@ static int jaro_join_launch(pfz_ctx *ctx, const pfz_strings *F, const pfz_string
 static int jaro_join_begin(pfz_ctx *ctx, const char *entry, const pfz_strings *F, const pfz_strings *T, bool self, int32_t scorer, double t,
                            const pfz_indel_plan **pl, DevBuf *d_run, ForestRun *forest, JaroJoinArgs *A)
 {
-    if (T->n >= INT_MAX - 64 || F->n >= INT_MAX || T->max_len >= INT_MAX / 2 || F->max_len >= INT_MAX / 2) {
-        set_error("%s: list or string too long", entry);
-        return PFZ_ERR_UNSUPPORTED;
-    }
+    PFZ_TRY(jaro_check_limits(entry, F, T));
     PFZ_TRY(indel_plan_get(ctx, T, pl));
     if (forest) PFZ_TRY(forest->alloc(ctx, F->n));
     const int32_t n_len = (int32_t)F->max_len + 1;
@@ -425,7 +331,7 @@ static int jaro_comp_run(pfz_ctx *ctx, const pfz_strings *F, int32_t scorer, dou
 
 static int check_jaro_threshold(const char *who, int32_t scorer, double t)
 {
-    PFZ_REQUIRE(scorer == 0 || scorer == 1, "%s: scorer %d is neither 0 (Jaro) nor 1 (Jaro-Winkler)", who, scorer);
+    PFZ_TRY(jaro_check_scorer(who, scorer));
     PFZ_REQUIRE(!std::isnan(t) && t >= 0.0 && t <= 1.0, "%s: min_similarity %g is not a number in [0, 1]", who, t);
     return PFZ_OK;
 }

@@ -17,10 +17,11 @@
 //                (float)F) is the length bound.  A group none of whose choices still in passes it is skipped; a direction ends at
 //                the first group all of whose real strings fail and lie on the far side of |a| -- the admissible lengths are one
 //                run around la (k8_core.h), and the run only shrinks as F rises.
-//   in a group   K20's sweep against (float)F: jaro_m_need per pair, jaro_dead once per packed dword with the wave-uniform early
-//                exit, jaro_reaches with the pair's own prefix, sweep 2 only if a live lane has two matches, jaro_reaches with t,
-//                jaro_score; then score >= score_cutoff, then topn_insert.  Padding lanes, left-out lanes and dead lanes are
-//                predicates: all 64 lanes reach topn_insert, and every exit from a group is wave-uniform.
+//   in a group   k8_sweep.h's jaro_pair_above against (float)F, the function K20 calls with its t: jaro_m_need per pair, jaro_dead
+//                once per packed dword with the wave-uniform early exit, jaro_reaches with the pair's own prefix, sweep 2 only if a
+//                live lane has two matches, jaro_reaches with t, jaro_score; then score >= score_cutoff, then topn_insert.  Padding
+//                lanes, left-out lanes and dead lanes are predicates: all 64 lanes reach topn_insert, and every exit from a group
+//                is wave-uniform.
 // K8's shortcut "same (m, t, |b|, prefix) as the best: skip" is NOT here: an equal score at a later index belongs in a top-n.
 // Everything else -- longer from-strings, the groups beyond 256 characters for every from-string, an alphabet whose table exceeds
 // 60 KiB -- takes the general kernel: pair_score.h's general Jaro, every pair not left out scored to the end, no floor.
@@ -38,10 +39,8 @@
 // alone) share a list buffer: row r of the class owns n_lists lists of ntop keys, n_lists = 4 waves x the parts of every launch
 // that IS made for the class, launch after launch; wave w of part p of a launch writes list list0 + 4 p + w.  A launch that is not
 // made contributes no lists, so the merge of a class reads nothing that was not written: there is no memset.
-#include "edit_walk.h"
-#include "k8_core.h"
 #include "k8_launch.h"
-#include "pair_score.h"
+#include "k8_sweep.h"
 #include "topn_wave.h"
 
 #include <algorithm>
@@ -50,40 +49,19 @@
 
 namespace pfz {
 
-struct JaroTopnArgs : EditView {
-    const int32_t *rows;       // from-rows of this launch, in their class's order
-    int32_t n_rows;
-    int32_t n_to;
-    int32_t g_begin, g_end;    // the to-groups of this launch
+struct JaroTopnArgs : JaroWalkArgs {      // (rows: in their class's order; counters: the pairs are the real strings of the groups walked)
     const int32_t *skip_idx;   // [n_from] or NULL (decoded: pfz_internal.h decode_skip_codes)
     int32_t skip_up_to;
-    int32_t winkler;
     int32_t parts;             // the to-groups of a from-string are split over `parts` workgroups, each with a floor of its own
     int32_t ntop;
     int32_t n_lists, list0;    // wave w of part p of row r (its place in `rows`) leaves its list in
     TopnKey *lists;            // lists[((int64_t)r * n_lists + list0 + 4 * p + w) * ntop]
     double cutoff;
-    const void *t_chars;       // the raw to-list, which the general kernel reads (pair_score.h)
-    int32_t t_width;
-    const int64_t *t_off;
-    unsigned long long *counters;   // optional [4]: pairs whose sweep 1 began, pairs alive after it, pairs scored in float64, sweep-1
-                                    // to-characters of live lanes
 };
 
 constexpr int K21_LDS_HEAD = 16;     // the floor word in front of the match table (which stays 16-byte aligned)
 
-__device__ inline void jaro_topn_count(unsigned long long *counters, unsigned long long w, unsigned long long a, unsigned long long s,
-                                       unsigned long long c)
-{
-    if (!counters) return;
-    wave_count(counters + 0, w);
-    wave_count(counters + 1, a);
-    wave_count(counters + 2, s);
-    wave_count(counters + 3, c);
-}
-
-// WORD: uint32_t (from-strings of <= 32 characters) or uint64_t (<= 64); NB: to-strings of up to NB words' characters (K8's flag
-// registers, walked stretch by stretch with compile-time indices)
+// WORD, IDB, NB: jaro_pair_above's (k8_sweep.h)
 template <typename WORD, int IDB, int NB>
 __global__ __launch_bounds__(256) void k21_topn_kernel(JaroTopnArgs A)
 {
@@ -91,13 +69,12 @@ __global__ __launch_bounds__(256) void k21_topn_kernel(JaroTopnArgs A)
     unsigned long long *wg_floor = (unsigned long long *)smem_raw;
     WORD *pm = (WORD *)(smem_raw + K21_LDS_HEAD);
     constexpr int PER = 32 / IDB;  // symbols per dword
-    constexpr int SPW = (int)sizeof(WORD) * 8 / PER;      // dwords per stretch
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
     pm_reg_zero(A, pm, tid, 256);
 
     const int parts = A.parts;
-    unsigned long long n_walk = 0, n_alive = 0, n_scored = 0, n_steps = 0;
+    JaroWork work;
     for (int u = blockIdx.x; u < A.n_rows * parts; u += gridDim.x) {
         const int r = u / parts, part = u - r * parts;
         const int row = A.rows[r];
@@ -148,59 +125,8 @@ __global__ __launch_bounds__(256) void k21_topn_kernel(JaroTopnArgs A)
                 }
                 continue;
             }
-            n_walk += real;
-            const float inv_lb = __builtin_amdgcn_rcpf((float)lb);
-            const int need = jaro_m_need(la, lb, inv_la, inv_lb, f32, A.winkler);
-            const int steps = __builtin_amdgcn_readfirstlane(A.g_steps[g]);
-            const uint32_t *gp = A.b_packed + A.g_off[g] + lane;
-            JaroFlags<WORD> s;
-            WORD fb[NB];
-            jaro_begin(s, jaro_range(la, lb));
-            bool go = true;                               // wave-uniform: a live lane has to-characters left
-#pragma unroll
-            for (int k = 0; k < NB; ++k) {
-                s.fb = 0;
-                for (int t = k * SPW; go && t < min(steps, (k + 1) * SPW); ++t) {
-                    const uint32_t pk = gp[(int64_t)t * 64];
-#pragma unroll
-                    for (int q = 0; q < PER; ++q)
-                        jaro_match<WORD>(s, pm[__builtin_amdgcn_ubfe(pk, q * IDB, IDB)], t * PER + q, (t - k * SPW) * PER + q);
-                    const int done = (t + 1) * PER;       // to-characters behind this lane (its own: min(done, lb))
-                    if (alive && done < lb && jaro_dead(la, __popcll((uint64_t)s.fa), lb - done, need)) {
-                        alive = false;
-                        n_steps += done;
-                    }
-                    go = __any(alive && done < lb);
-                }
-                fb[k] = s.fb;
-            }
-            n_steps += alive ? lb : 0;
-            const int m = __popcll((uint64_t)s.fa);
-            const int prefix = jaro_prefix(s.pre);
-            // the bound from m alone, with the pair's own prefix (m = 0: asked before any 0 * inf reaches a comparison)
-            alive = alive && jaro_reaches(m, inv_la, inv_lb, 1.0f, prefix, A.winkler, f32);
-            n_alive += alive;
-            int half_t = 0;
-            // (one flagged pair cannot be out of order; the sweep runs for the wave if a single live lane wants it)
-            if (__any(alive && m >= 2)) {
-                go = true;                                // wave-uniform: a live lane has a flagged from-position left
-#pragma unroll
-                for (int k = 0; k < NB; ++k) {
-                    s.fb = fb[k];
-                    for (int t = k * SPW; go && t < min(steps, (k + 1) * SPW); ++t) {
-                        const uint32_t pk = gp[(int64_t)t * 64];
-#pragma unroll
-                        for (int q = 0; q < PER; ++q)
-                            half_t += jaro_transpose<WORD>(s, pm[__builtin_amdgcn_ubfe(pk, q * IDB, IDB)], (t - k * SPW) * PER + q);
-                        go = __any(alive && s.fa != 0);
-                    }
-                }
-            }
-            // the bound again, with t
-            const float last = (float)(m - half_t / 2) * __builtin_amdgcn_rcpf((float)m);
-            alive = alive && jaro_reaches(m, inv_la, inv_lb, last, prefix, A.winkler, f32);
-            n_scored += alive;
-            const double sc = alive ? jaro_score(m, half_t, la, lb, prefix, A.winkler) : 0.0;
+            work.pairs += real;
+            const double sc = jaro_pair_above<WORD, IDB, NB>(A, pm, g, la, lb, inv_la, f32, A.winkler, alive, work);
             topn_insert(list, A.ntop, alive && sc >= A.cutoff, sc, orig);
             // a full list: A.ntop reportable choices at or above its last entry's score exist
             double last_score;
@@ -211,7 +137,7 @@ __global__ __launch_bounds__(256) void k21_topn_kernel(JaroTopnArgs A)
         __syncthreads();                                  // every wave is done with the match table and the floor
         pm_reg_clear(pm, my_sym);
     }
-    jaro_topn_count(A.counters, n_walk, n_alive, n_scored, n_steps);
+    jaro_work_flush(A.counters, work);
 }
 
 // The general case: any lengths, any alphabet.  The match table of the workgroup's from-string (WA words per symbol) and every
@@ -221,25 +147,16 @@ __global__ __launch_bounds__(256) void k21_topn_general_kernel(JaroTopnArgs A, i
                                                                 uint64_t *__restrict__ fa_all, uint64_t *__restrict__ fb_all)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    uint64_t *pm = pm_all + (int64_t)blockIdx.x * A.n_sym1 * WA;      // zero on entry, zero again after every row
-    uint64_t *fa = fa_all + ((int64_t)blockIdx.x * 4 + wave) * WA * 64 + lane;      // fa[w * 64]: this lane's word w
-    uint64_t *fb = fb_all + ((int64_t)blockIdx.x * 4 + wave) * WS * 64 + lane;
-    PairView P;
-    static_cast<FromView &>(P) = A;
-    P.b_chars = A.t_chars;
-    P.b_width = A.t_width;
-    P.b_off = A.t_off;
-    P.n_to = A.n_to;
-    P.scorer = A.winkler ? PAIR_JARO_WINKLER : PAIR_JARO;
+    const JaroGeneral G = jaro_general_begin(A, WA, WS, pm_all, fa_all, fb_all);
     const int parts = A.parts;
-    unsigned long long n_walk = 0, n_scored = 0, n_steps = 0;
+    JaroWork work;
     for (int u = blockIdx.x; u < A.n_rows * parts; u += gridDim.x) {
         const int r = u / parts, part = u - r * parts;
         const int row = A.rows[r];
         const int64_t a0 = A.a_off[row];
         const int la = (int)(A.a_off[row + 1] - a0);
         const int W = la > 0 ? (la + 63) / 64 : 1;                    // <= WA
-        pm_global_set(A, pm, WA, a0, la, tid, 256);
+        pm_global_set(A, G.pm, WA, a0, la, tid, 256);
         const int skip = A.skip_idx ? A.skip_idx[row] : -1;
         TopnList list = topn_empty();
         for (int g = A.g_begin + wave + 4 * part; g < A.g_end; g += 4 * parts) {
@@ -247,18 +164,19 @@ __global__ __launch_bounds__(256) void k21_topn_general_kernel(JaroTopnArgs A, i
             const int orig = A.b_orig[slot];
             const int lb = A.b_len[slot];
             const bool have = orig >= 0 && !choice_left_out(orig, skip, A.skip_up_to);
-            n_walk += orig >= 0;
-            n_scored += have;
-            n_steps += have ? lb : 0;
+            work.pairs += orig >= 0;
+            work.scored += have;
+            work.steps += have ? lb : 0;
             double sc = 0.0;
-            if (have) sc = pair_score_general(P, pm, fa, fb, nullptr, WA, W, la, A.t_off[orig], lb);
+            if (have) sc = pair_score_general(G.P, G.pm, G.fa, G.fb, nullptr, WA, W, la, A.t_off[orig], lb);
             topn_insert(list, A.ntop, have && sc >= A.cutoff, sc, orig);
         }
         topn_store(list, A.ntop, A.lists + (((int64_t)r * A.n_lists + A.list0 + 4 * part + wave)) * A.ntop);
         __syncthreads();                                              // every wave is done with the match table
-        pm_global_clear(A, pm, WA, a0, la, tid, 256);
+        pm_global_clear(A, G.pm, WA, a0, la, tid, 256);
     }
-    jaro_topn_count(A.counters, n_walk, n_scored, n_scored, n_steps);
+    work.alive = work.scored;          // scored to the end, every one not left out
+    jaro_work_flush(A.counters, work);
 }
 
 static int jaro_topn_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, int32_t scorer, const int32_t *skip_idx, int64_t begin,
@@ -280,10 +198,7 @@ static int jaro_topn_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *
         return PFZ_OK;
     }
     PFZ_HIP(hipSetDevice(ctx->device));
-    if (T->n >= INT_MAX - 64 || F->n >= INT_MAX || T->max_len >= INT_MAX / 2 || F->max_len >= INT_MAX / 2) {
-        set_error("pfz_jaro_topn: list or string too long");
-        return PFZ_ERR_UNSUPPORTED;
-    }
+    PFZ_TRY(jaro_check_limits("pfz_jaro_topn", F, T));
     const pfz_indel_plan *pl;
     PFZ_TRY(indel_plan_get(ctx, T, &pl));
     const JaroPlan plan = jaro_plan(ctx, F, T, pl, begin, end);      // K8's launches (k8_launch.h)
@@ -398,7 +313,7 @@ int pfz_jaro_topn(pfz_ctx *ctx, const pfz_strings *from_strings, const pfz_strin
                   uint64_t *out_counters)
 {
     PFZ_REQUIRE(ctx && from_strings && to_strings, "pfz_jaro_topn: NULL argument");
-    PFZ_REQUIRE(scorer == 0 || scorer == 1, "pfz_jaro_topn: scorer %d is neither 0 (Jaro) nor 1 (Jaro-Winkler)", scorer);
+    PFZ_TRY(jaro_check_scorer("pfz_jaro_topn", scorer));
     PFZ_REQUIRE(from_begin >= 0 && from_begin <= from_end && from_end <= from_strings->n, "pfz_jaro_topn: row range [%lld,%lld) outside [0,%lld)",
                 (long long)from_begin, (long long)from_end, (long long)from_strings->n);
     PFZ_REQUIRE(ntop >= 1, "pfz_jaro_topn: ntop %d < 1", ntop);

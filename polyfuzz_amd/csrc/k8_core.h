@@ -1,7 +1,8 @@
 // K8's per-pair logic: the greedy Jaro matching as bit operations on one 32- or 64-bit word per string, and the float64 score.
-// Plain integer C++ (and one float64 formula), shared by the HIP kernels (k8_jaro.hip; k20_jaro_join.hip, the threshold form, whose
-// bounds against a fixed t are at the end of this file; k21_jaro_topn.hip, which holds them against a floor that rises) and the host programs that check it against the definition on the CPU
-// (tests/k8_core_host.cpp, tests/k20_core_host.cpp).
+// Plain integer C++ (and one float64 formula), shared by the HIP kernels and the host programs that check it against the
+// definition on the CPU (tests/k8_core_host.cpp, tests/k20_core_host.cpp).  The kernels: k8_jaro.hip, the arg-max;
+// k20_jaro_join.hip, which holds the bounds at the end of this file against a fixed t, and k21_jaro_topn.hip, which holds them
+// against a floor that rises -- both through k8_sweep.h, the device code that walks one pair with these rules.
 //
 // The definition (jellyfish's jaro_similarity / jaro_winkler_similarity, default arguments, on code points):
 //   r = max(max(la, lb) / 2 - 1, 0);  the from-characters i in order take the first unflagged j in [i - r, i + r] with

@@ -23,6 +23,9 @@
 // 60 KiB -- takes the general kernel: flag words and match table in global memory, any length, slow.  Every launch
 // leaves (score, index) records per from-string; k8_merge picks the first maximum of a row over them.
 // The view of the plan, the match table's set / clear, the (score, index) best and its merge are edit_walk.h's, shared with K9 .. K12.
+// The two sweeps of the register kernel are written out here and not taken from k8_sweep.h (K20's and K21's): behind every shared
+// form tried, k8_jaro_kernel<uint64_t, 8, 4> took 97 registers where this text takes 95 -- 5 waves per SIMD become 4
+// (docs/JARO_SWEEP_MEASURED.md).  The plan of the launches and the checks of an entry are k8_launch.h's.
 // Bound: integer VALU + LDS look-ups, two sweeps per pair where K4 has one (measured beside K4).
 #include "edit_walk.h"
 #include "k8_core.h"
@@ -245,16 +248,13 @@ static int jaro_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, in
                     int64_t end, int32_t *out_idx, double *out_score, double *out_matrix, pfz_topn *out_dev = nullptr)
 {
     PFZ_REQUIRE(ctx && F && T, "pfz_jaro: NULL argument");
-    PFZ_REQUIRE(scorer == 0 || scorer == 1, "pfz_jaro: scorer %d is neither 0 (Jaro) nor 1 (Jaro-Winkler)", scorer);
+    PFZ_TRY(jaro_check_scorer("pfz_jaro", scorer));
     PFZ_REQUIRE(begin >= 0 && begin <= end && end <= F->n, "pfz_jaro: row range [%lld,%lld) outside [0,%lld)",
                 (long long)begin, (long long)end, (long long)F->n);
     const int64_t n_rows = end - begin;
     if (n_rows == 0) return PFZ_OK;
     PFZ_HIP(hipSetDevice(ctx->device));
-    if (T->n >= INT_MAX - 64 || F->n >= INT_MAX || T->max_len >= INT_MAX / 2 || F->max_len >= INT_MAX / 2) {
-        set_error("pfz_jaro: list or string too long");
-        return PFZ_ERR_UNSUPPORTED;
-    }
+    PFZ_TRY(jaro_check_limits("pfz_jaro", F, T));
     const pfz_indel_plan *pl;
     PFZ_TRY(indel_plan_get(ctx, T, &pl));
     const int64_t n_to = T->n;
@@ -315,10 +315,10 @@ static int jaro_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, in
             A.slot0 = L.slot0;
             const dim3 grid((unsigned)std::min<int64_t>((int64_t)A.n_rows * L.parts, max_grid));
             const size_t lds = (size_t)A.n_sym1 * (L.wide ? sizeof(uint64_t) : sizeof(uint32_t));
-            if (!L.wide && pl->idb == 8) hipLaunchKernelGGL((k8_jaro_kernel<uint32_t, 8, 1>), grid, dim3(256), lds, ctx->stream, A);
-            else if (!L.wide) hipLaunchKernelGGL((k8_jaro_kernel<uint32_t, 16, 1>), grid, dim3(256), lds, ctx->stream, A);
-            else if (pl->idb == 8) hipLaunchKernelGGL((k8_jaro_kernel<uint64_t, 8, 4>), grid, dim3(256), lds, ctx->stream, A);
-            else hipLaunchKernelGGL((k8_jaro_kernel<uint64_t, 16, 4>), grid, dim3(256), lds, ctx->stream, A);
+            dispatch_idb(pl->idb, [&](auto IDB) {
+                if (L.wide) hipLaunchKernelGGL((k8_jaro_kernel<uint64_t, decltype(IDB)::value, 4>), grid, dim3(256), lds, ctx->stream, A);
+                else hipLaunchKernelGGL((k8_jaro_kernel<uint32_t, decltype(IDB)::value, 1>), grid, dim3(256), lds, ctx->stream, A);
+            });
             PFZ_HIP(hipGetLastError());
         }
         // the general kernel: the from-strings of the register launches against the groups of longer to-strings, the other
@@ -339,12 +339,10 @@ static int jaro_run(pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, in
             ProfScope ps(ctx, "k8_jaro_general");
             GeneralBufs gb;      // (col[0]: the from-flags, col[1]: the to-flags)
             PFZ_TRY(general_bufs_alloc(ctx, &gb, grid, A.n_sym1, WA, {WA, WB, 0}, 256));
-            if (pl->idb == 8)
-                hipLaunchKernelGGL((k8_jaro_general_kernel<8>), dim3((unsigned)grid), dim3(256), 0, ctx->stream, A, WA, WB,
+            dispatch_idb(pl->idb, [&](auto IDB) {
+                hipLaunchKernelGGL((k8_jaro_general_kernel<decltype(IDB)::value>), dim3((unsigned)grid), dim3(256), 0, ctx->stream, A, WA, WB,
                                    gb.pm.as<uint64_t>(), gb.col[0].as<uint64_t>(), gb.col[1].as<uint64_t>());
-            else
-                hipLaunchKernelGGL((k8_jaro_general_kernel<16>), dim3((unsigned)grid), dim3(256), 0, ctx->stream, A, WA, WB,
-                                   gb.pm.as<uint64_t>(), gb.col[0].as<uint64_t>(), gb.col[1].as<uint64_t>());
+            });
             PFZ_HIP(hipGetLastError());
         }
         hipLaunchKernelGGL(k8_merge, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, ctx->stream, (const BestRec *)d_rec.p, n_slots,
@@ -390,8 +388,7 @@ int pfz_jaro_matrix_host(pfz_ctx *ctx, const pfz_strings *from_strings, const pf
 {
     PFZ_REQUIRE(out_matrix, "pfz_jaro_matrix_host: NULL output");
     if (to_strings && to_strings->n == 0) {
-        PFZ_REQUIRE(scorer == 0 || scorer == 1, "pfz_jaro: scorer %d is neither 0 (Jaro) nor 1 (Jaro-Winkler)", scorer);
-        return PFZ_OK;
+        return jaro_check_scorer("pfz_jaro", scorer);
     }
     return jaro_run(ctx, from_strings, to_strings, scorer, nullptr, from_begin, from_end, nullptr, nullptr, out_matrix);
 }

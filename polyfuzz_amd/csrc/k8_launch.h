@@ -1,6 +1,7 @@
 // The launches of an all-pairs Jaro call over K4's to-side plan, planned once for K8 (k8_jaro.hip: a best per row) and K21
 // (k21_jaro_topn.hip: a list per wave): which from-rows the register kernels serve and against which groups, into how many parts
-// a row's groups are split, and where a launch leaves what it found for its rows.  Host code only.
+// a row's groups are split, and where a launch leaves what it found for its rows; and what every Jaro entry -- K20's
+// (k20_jaro_join.hip) too -- checks before it plans.  Host code only.
 #pragma once
 
 #include "edit_walk.h"
@@ -32,6 +33,30 @@ struct JaroPlan {
     bool general_behind_reg() const { return !rows_reg.empty() && g256 < n_groups; }      // rows_reg against the groups beyond 256
 };
 
+// what every Jaro entry refuses before it plans: positions (padded to groups of 64) and lengths are 32-bit
+inline int jaro_check_limits(const char *entry, const pfz_strings *F, const pfz_strings *T)
+{
+    if (T->n >= INT_MAX - 64 || F->n >= INT_MAX || T->max_len >= INT_MAX / 2 || F->max_len >= INT_MAX / 2) {
+        set_error("%s: list or string too long", entry);
+        return PFZ_ERR_UNSUPPORTED;
+    }
+    return PFZ_OK;
+}
+
+inline int jaro_check_scorer(const char *entry, int32_t scorer)
+{
+    PFZ_REQUIRE(scorer == 0 || scorer == 1, "%s: scorer %d is neither 0 (Jaro) nor 1 (Jaro-Winkler)", entry, scorer);
+    return PFZ_OK;
+}
+
+// the groups are sorted by length: the first whole_groups_up_to(T, pl, len) of them hold to-strings of <= len characters only
+inline int32_t whole_groups_up_to(const pfz_strings *T, const pfz_indel_plan *pl, int64_t len)
+{
+    int64_t n = 0;
+    for (int64_t j = 0; j < T->n; ++j) n += T->h_off[(size_t)j + 1] - T->h_off[(size_t)j] <= len;
+    return n == T->n ? (int32_t)pl->n_groups : (int32_t)(n / 64);
+}
+
 // The register kernel's share, while the match table fits 60 KiB of LDS: from-strings of <= 32 characters against the groups whose
 // to-strings all have <= 32 in 32-bit words; those from-strings against the groups of up to 256, and the from-strings of 33 .. 64
 // characters against all groups of up to 256, in 64-bit words (four for a to-string's flags).  Few from-strings: the to-groups of
@@ -39,16 +64,10 @@ struct JaroPlan {
 inline JaroPlan jaro_plan(const pfz_ctx *ctx, const pfz_strings *F, const pfz_strings *T, const pfz_indel_plan *pl, int64_t begin, int64_t end)
 {
     JaroPlan P;
-    const int64_t n_to = T->n;
     const bool lds_fits = lds_table_fits(pl);
     P.n_groups = (int32_t)pl->n_groups;
-    auto whole_groups_up_to = [&](int64_t len) {
-        int64_t n = 0;
-        for (int64_t j = 0; j < n_to; ++j) n += T->h_off[(size_t)j + 1] - T->h_off[(size_t)j] <= len;
-        return !lds_fits ? 0 : (n == n_to ? P.n_groups : (int32_t)(n / 64));
-    };
-    P.g32 = whole_groups_up_to(32);
-    P.g256 = whole_groups_up_to(256);
+    P.g32 = lds_fits ? whole_groups_up_to(T, pl, 32) : 0;
+    P.g256 = lds_fits ? whole_groups_up_to(T, pl, 256) : 0;
     std::vector<int32_t> rows_64;
     P.longest = 1;
     for (int64_t i = begin; i < end; ++i) {

@@ -39,12 +39,18 @@ def _long_strings(alpha_name):
     return ["".join(rng.choice(list(alpha), size=n)) for n in (255, 256, 257, 300)]
 
 
-@pytest.fixture(scope="module", params=("ab", "wide"))
-def classes(request, oracle_mod):
-    fl, tl = _class_lists(request.param)
-    tl = tl + _long_strings(request.param)
+def class_lists(alpha_name):
+    """the lists of the `classes` fixture (tests/test_jaro_sweep_gpu.py records the work of K20 and K21 on them)"""
+    fl, tl = _class_lists(alpha_name)
+    tl = tl + _long_strings(alpha_name)
     # from-strings of <= 64 that share their start with a to-string beyond 256, and two long near-copies of such to-strings
     fl = fl + [tl[-1][:64], tl[-2][:40], tl[-1][1:], tl[-3][:-2]]
+    return fl, tl
+
+
+@pytest.fixture(scope="module", params=("ab", "wide"))
+def classes(request, oracle_mod):
+    fl, tl = class_lists(request.param)
     return request.param, fl, tl, {name: oracle_mod.jaro_matrix(fl, tl, name) for name in SCORERS}
 
 

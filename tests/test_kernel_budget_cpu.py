@@ -59,6 +59,28 @@ def test_k7_join_kernels_keep_their_register_classes(kernels):
     assert seen == 18 and sum(k.startswith("void pfz::k7_join_kernel<") for k in kernels) == 18
 
 
+def test_jaro_register_kernels_keep_their_register_classes(kernels):
+    """K20's and K21's register kernels share what a lane does with one pair (k8_sweep.h jaro_pair_above): one edit there moves all
+    twelve instances, and K8's four are the yardstick beside them.  Each must stay at or below the register allocation (VGPRs in
+    steps of 8; waves per SIMD = min(8, 512 // allocation)) it had with a copy of the sweep of its own -- no scratch, and K8's
+    widest instance, 95 of 96, is the one that is a register or two from a wave less."""
+    u32, u64 = "unsigned int", "unsigned long"
+    k20 = {(u32, 16): 64, (u32, 8): 64, (u64, 16): 72, (u64, 8): 80}       # both sinks: 52 / 50, 54 / 50, 71 / 66, 79 / 75
+    k21 = {(u32, 16): 72, (u32, 8): 72, (u64, 16): 80, (u64, 8): 88}       # 67, 67, 79, 87
+    k8 = {(u32, 16): 64, (u32, 8): 64, (u64, 16): 88, (u64, 8): 96}        # 62, 62, 81, 95
+    seen = {"k20_join_kernel": 0, "k21_topn_kernel": 0, "k8_jaro_kernel": 0}
+    for name, limits, tails in (("k20_join_kernel", k20, (", pfz::FuzzAppend", ", pfz::FuzzUnite")), ("k21_topn_kernel", k21, ("",)),
+                                ("k8_jaro_kernel", k8, ("",))):
+        for (word, idb), limit in limits.items():
+            for tail in tails:
+                k = _one(kernels, f"void pfz::{name}<{word}, {idb}, {1 if word == u32 else 4}{tail}>(")
+                assert k["vgpr"] <= limit and k["scratch"] == 0, (name, word, idb, tail, k)
+                seen[name] += 1
+    assert seen == {"k20_join_kernel": 8, "k21_topn_kernel": 4, "k8_jaro_kernel": 4}
+    for name, n in seen.items():          # (a new template parameter is a new instance: it gets a limit here first)
+        assert sum(k.startswith(f"void pfz::{name}<") for k in kernels) == n, name
+
+
 def test_k3_headline_kernel_keeps_18_workgroups_per_cu(kernels):
     """2048 accumulator columns + the 96-key candidate buffer: 8960 B; one more 256-B step is a workgroup per CU less."""
     k = _one(kernels, "void pfz::k3_cossim_topn_kernel<2048, 96, false>(")

@@ -1,6 +1,8 @@
 """Registers, LDS and scratch of every gfx950 kernel in the built library (the code objects' own metadata).
 usage: python tools/kernel_budget.py [libpolyfuzz_hip.so] [name filter]
        python tools/kernel_budget.py --digest [libpolyfuzz_hip.so]     one sha256 of the device code per translation unit
+       python tools/kernel_budget.py --digest [libpolyfuzz_hip.so] k8_jaro.hip     one sha256 per kernel of that unit, by name:
+                                                                       the same lines when only the kernels' order in the unit moved
 
 Why: round 3 found K7 and K3 sitting ON occupancy steps -- 256 B of LDS more cost K7 a workgroup per CU and 5 %, K3 4.4 %
 (DESIGN.md, K7 / "What comes next") -- and nothing but this metadata says when an edit crosses one.
@@ -78,6 +80,23 @@ def device_digests(lib):
     return out
 
 
+def kernel_digests(lib, unit_index):
+    """{kernel symbol: sha256 of its disassembly, addresses and encodings left out} of one translation unit: the order in which a
+    unit's templates are instantiated (host code decides it) moves its kernels and the unit's digest, not these"""
+    import hashlib
+    out, cur = {}, None
+    with tempfile.TemporaryDirectory() as d:
+        co = code_objects(lib, d)[unit_index]
+        dis = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", "--no-leading-addr", co], capture_output=True, text=True).stdout
+    for line in dis.splitlines():
+        m = re.match(r"^[0-9a-f]* ?<(\S+)>:$", line)
+        if m:
+            cur = out.setdefault(m.group(1), hashlib.sha256())
+        elif cur is not None:
+            cur.update(re.sub(r"//.*$", "", line).strip().encode() + b"\n")
+    return {k: h.hexdigest() for k, h in out.items()}
+
+
 def demangled(names):
     import shutil
     exe = shutil.which("c++filt")
@@ -95,6 +114,11 @@ if __name__ == "__main__":
     flt = [a for a in args if not a.endswith(".so")]
     if "--digest" in sys.argv[1:]:
         units = [os.path.basename(p) for p in _build.sources()]      # (link order)
+        if flt:
+            per_kernel = kernel_digests(lib, units.index(flt[0]))
+            for pretty, n in sorted(zip(demangled(list(per_kernel)), per_kernel)):
+                print(per_kernel[n], pretty[:110])
+            sys.exit(0)
         for k, h in enumerate(device_digests(lib)):
             print(h, units[k] if k < len(units) else f"unit{k}")
         sys.exit(0)
