@@ -985,6 +985,43 @@ int pfz_hamming_components(pfz_ctx *ctx, const pfz_dense *codes, int64_t max_dis
  * or one outside [0, 1]. */
 int pfz_hamming_max_distance(int64_t dim_bits, double min_similarity, int64_t *out_max_distance);
 
+/* ---- K24: the same two results through a block index, for small distances ---------
+ * K23 computes every pair.  For a small max_distance on short codes (64-bit SimHash fingerprints at 3) nearly all of that work is
+ * thrown away.  The block index is the exact filter (csrc/k24_core.h): cut the dim_bits bits into m = max_distance + 1 blocks,
+ * block b = bits [b dim_bits / m, (b + 1) dim_bits / m) in np.packbits order; two codes within max_distance agree completely on at
+ * least one block.  A block's KEY is its first min(width, 32) bits; a pair is a CANDIDATE in block b iff its two keys of block b
+ * are equal (self-join: column > row only), and a candidate is reported iff its full distance is <= max_distance and no earlier
+ * block has equal keys -- every pair exactly once, nothing approximate: the result is pfz_hamming_join's, bit for bit.
+ * The to-rows' m n_to sort keys (block << 56 | key << 24 | position) are sorted once; every (from-row, block) probe finds its run
+ * of partners by binary search; the runs are cut into work items of at most 64 partners (K17's deal) and a wave computes an
+ * item's distances, XOR / popcount over 16-byte pieces, leaving a pair as soon as it passes max_distance.
+ * A (dim_bits, max_distance) is INDEXABLE iff 1 <= m <= min(dim_bits, 256); a call also needs fewer than 2^24 rows in both lists,
+ * m n_to < 2^31 and m n_from < 2^31, and fewer than 2^31 work items.
+ * mode: PFZ_HAMMING_INDEX_BLOCKS -- the index runs, or the call returns PFZ_ERR_UNSUPPORTED and the message names the limit;
+ * PFZ_HAMMING_INDEX_AUTO -- the index runs iff the call is indexable and checks * R <= all pairs (n_from n_to, or n (n - 1) / 2
+ * for a self-join), R the measured constant pfz_hamming_index_plan reports; otherwise K23's tile program runs inside the same
+ * call.  The decision falls behind the sort and the searches, where `checks` is known.
+ * Everything else -- operands, the self-join, output, order, capacity, *out_total, the repeat protocol, the empty lists, the other
+ * errors -- is pfz_hamming_join's.  out_counters: NULL, or int64[5] -- [0] the blocks m, [1] the narrowest block's width in bits,
+ * [2] checks: the (pair, block) candidates, a function of the input alone, [3] the work items, [4] the route: 1 = the index, 0 =
+ * the tiles ([0] and [1] are 0 where (dim_bits, max_distance) is not indexable, [2] and [3] where the searches did not run).
+ * Profiling scopes: `k24_keys`, `k24_sort`, `k24_ranges` (searches and scan), `k24_probe`, `k24_sort_unpack`; on the tile route
+ * K23's.  Blocks. */
+#define PFZ_HAMMING_INDEX_BLOCKS 1
+#define PFZ_HAMMING_INDEX_AUTO 2
+int pfz_hamming_join_indexed(pfz_ctx *ctx, const pfz_dense *from_codes, const pfz_dense *to_codes, int64_t max_distance, int32_t mode,
+                             int64_t capacity, int64_t *out_row_ptr, int32_t *out_idx, int32_t *out_dist, int64_t *out_total,
+                             int64_t *out_counters);
+/* pfz_hamming_components through the same index: the hits are united in the union-find of csrc/k12_core.h where they are found;
+ * *out_pairs equals the join's total.  mode and out_counters as above; the rest as pfz_hamming_components.  Profiling scope of the
+ * forest, the probe kernel and the labels: `k24_components`.  Blocks. */
+int pfz_hamming_components_indexed(pfz_ctx *ctx, const pfz_dense *codes, int64_t max_distance, int32_t mode, int32_t *out_label,
+                                   int64_t *out_pairs, int64_t *out_components, int64_t *out_counters);
+/* The index of a width and a distance: out = int64[4] -- [0] the blocks m, [1] the narrowest and [2] the widest block in bits,
+ * [3] R.  A pure host function: no device is touched.  PFZ_ERR_UNSUPPORTED: not indexable (the message says why: more blocks than
+ * bits, more than 256 blocks); PFZ_ERR_INVALID: dim_bits outside [1, 2^24), max_distance outside [0, dim_bits], NULL. */
+int pfz_hamming_index_plan(int64_t dim_bits, int64_t max_distance, int64_t *out);
+
 /* ---- K15: all pairs at or above a sparse cosine, and their components -----------
  * The threshold form of K3, what de-duplication asks of the reference's TF-IDF matcher: every pair (from-row i, to-row j) whose
  * cosine is >= min_similarity, however many partners a row has -- no top_n to guess, no n x top_n table.  to_index is the

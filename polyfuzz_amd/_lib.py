@@ -144,6 +144,9 @@ SIGNATURES = {
     "pfz_hamming_join": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, P(c_i64), c_vp]),
     "pfz_hamming_components": (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp, P(c_i64), P(c_i64), c_vp]),
     "pfz_hamming_max_distance": (ctypes.c_int, [c_i64, c_f64, P(c_i64)]),
+    "pfz_hamming_join_indexed": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, P(c_i64), c_vp]),
+    "pfz_hamming_components_indexed": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i32, c_vp, P(c_i64), P(c_i64), c_vp]),
+    "pfz_hamming_index_plan": (ctypes.c_int, [c_i64, c_i64, c_vp]),
     "pfz_dense_join16": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_f64, c_i64, c_i64, c_vp, c_vp, c_vp, P(c_i64), c_vp]),
     "pfz_dense_components16": (ctypes.c_int, [c_vp, c_vp, c_vp, c_f64, c_i64, c_vp, P(c_i64), P(c_i64), c_vp]),
     "pfz_cossim_join": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_f64, c_i64, c_vp, c_vp, c_vp, P(c_i64), c_vp]),
@@ -1353,6 +1356,53 @@ def hamming_components(ctx, dev, max_distance, counters=False):
     _hamming_join_operand(dev, "the codes")
     return _components_call(dev.n, HAMMING_JOIN_COUNTERS, counters, lambda label, pairs, components, wk: ctx.lib.pfz_hamming_components(
         ctx.h, dev.h, int(max_distance), label, pairs, components, wk))
+
+
+# ---- K24: the same two results through a block index, for small distances ------------------------------------------------
+
+HAMMING_INDEX_COUNTERS = ("blocks", "min_block_bits", "checks", "items", "route")      # the indexed entries' out_counters, in order
+HAMMING_INDEX_BLOCKS, HAMMING_INDEX_AUTO = 1, 2      # PFZ_HAMMING_INDEX_*
+
+
+def hamming_index_plan(dim_bits, max_distance):
+    """The block index of codes of dim_bits bits at max_distance (csrc/k24_core.h): {"blocks": m = max_distance + 1,
+    "min_block_bits", "max_block_bits", "ratio": R, the measured cost of one indexed check in tile pairs (auto runs the index iff
+    checks * R <= all pairs)}.  The library's own host function: no device is touched.  ValueError: dim_bits outside [1, 2**24) or
+    max_distance outside [0, dim_bits]; PfzUnsupported: no index -- more blocks than bits, or more than 256 (the message says)."""
+    if isinstance(dim_bits, bool) or not isinstance(dim_bits, (int, np.integer)) or not 1 <= int(dim_bits) < 1 << 24:
+        raise ValueError(f"dim_bits must be an integer in [1, 2**24), not {dim_bits!r}")
+    if isinstance(max_distance, bool) or not isinstance(max_distance, (int, np.integer)) or not 0 <= int(max_distance) <= int(dim_bits):
+        raise ValueError(f"max_distance must be an integer in [0, {dim_bits}], not {max_distance!r}")
+    out = np.zeros(4, np.int64)
+    check(load().pfz_hamming_index_plan(int(dim_bits), int(max_distance), _ptr(out)))
+    return dict(zip(("blocks", "min_block_bits", "max_block_bits", "ratio"), out.tolist()))
+
+
+def hamming_join_indexed(ctx, from_dev, to_dev, max_distance, auto=False, capacity=None, counters=False):
+    """K24: hamming_join's result, bit for bit, through the block index -- only pairs that share the bits of one of
+    max_distance + 1 blocks have their distance computed.  auto=False: the index runs, or PfzUnsupported names the limit that
+    keeps it from running (hamming_index_plan; 2**24 rows); auto=True: the index runs iff it is cheaper by the library's measured
+    rule, otherwise K23's tiles run inside the call.  Returns what hamming_join returns; counts: {"pairs": hits}, with
+    counters=True also HAMMING_INDEX_COUNTERS (the last call's; "route": 1 = the index, 0 = the tiles)."""
+    _hamming_join_operand(from_dev, "the from-codes")
+    if to_dev is not None:
+        _hamming_join_operand(to_dev, "the to-codes")
+    to_h = None if to_dev is None else to_dev.h
+    mode = HAMMING_INDEX_AUTO if auto else HAMMING_INDEX_BLOCKS
+    row_ptr, hits, n, work = _join_call(
+        from_dev.n, capacity, (np.int32, np.int32), HAMMING_INDEX_COUNTERS, counters,
+        lambda cap, ptr, hit, total, wk: ctx.lib.pfz_hamming_join_indexed(ctx.h, from_dev.h, to_h, int(max_distance), mode, cap, ptr, *hit,
+                                                                          total, wk))
+    return (row_ptr,) + hits + ({"pairs": n, **(work or {})},)
+
+
+def hamming_components_indexed(ctx, dev, max_distance, auto=False, counters=False):
+    """K24: hamming_components' result through the block index -- (label int32[n], pairs, components); auto as
+    hamming_join_indexed.  counters=True appends a dict of HAMMING_INDEX_COUNTERS."""
+    _hamming_join_operand(dev, "the codes")
+    mode = HAMMING_INDEX_AUTO if auto else HAMMING_INDEX_BLOCKS
+    return _components_call(dev.n, HAMMING_INDEX_COUNTERS, counters, lambda label, pairs, components, wk:
+                            ctx.lib.pfz_hamming_components_indexed(ctx.h, dev.h, int(max_distance), mode, label, pairs, components, wk))
 
 
 # ---- K22: the same two entries searched on the 16-bit matrix cores, scored exactly on the fp32 vectors -------------------

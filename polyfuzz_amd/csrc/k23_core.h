@@ -94,4 +94,11 @@ inline int64_t hamming_cutoff(int64_t dim_bits, double t)
     return lo;
 }
 
+// The two runs behind pfz_hamming_join / pfz_hamming_components (k23_hamming_join.hip), arguments checked by the caller: K24's
+// entries hand a call over to them when its block index does not pay (k24_hamming_index.hip).  out_counters: NULL, or int64[2].
+int hamming_join_run(pfz_ctx *ctx, const pfz_dense *F, const pfz_dense *T, bool self, int64_t hmax, int64_t capacity, int64_t *out_row_ptr,
+                     int32_t *out_idx, int32_t *out_dist, int64_t *out_total, int64_t *out_counters);
+int hamming_comp_run(pfz_ctx *ctx, const pfz_dense *V, int64_t hmax, int32_t *out_label, int64_t *out_pairs, int64_t *out_components,
+                     int64_t *out_counters);
+
 }  // namespace pfz

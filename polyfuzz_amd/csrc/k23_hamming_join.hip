@@ -63,8 +63,8 @@ static int hamming_join_args(const char *who, const pfz_dense *F, const pfz_dens
     return dense_join_grid(who, P, kTile, 8, 8, grid);
 }
 
-static int hamming_join_run(pfz_ctx *ctx, const pfz_dense *F, const pfz_dense *T, bool self, int64_t hmax, int64_t capacity,
-                            int64_t *out_row_ptr, int32_t *out_idx, int32_t *out_dist, int64_t *out_total, int64_t *out_counters)
+int hamming_join_run(pfz_ctx *ctx, const pfz_dense *F, const pfz_dense *T, bool self, int64_t hmax, int64_t capacity,
+                     int64_t *out_row_ptr, int32_t *out_idx, int32_t *out_dist, int64_t *out_total, int64_t *out_counters)
 {
     PFZ_HIP(hipSetDevice(ctx->device));
     *out_total = 0;
@@ -105,8 +105,8 @@ static int hamming_join_run(pfz_ctx *ctx, const pfz_dense *F, const pfz_dense *T
                             reinterpret_cast<float *>(out_dist));
 }
 
-static int hamming_comp_run(pfz_ctx *ctx, const pfz_dense *V, int64_t hmax, int32_t *out_label, int64_t *out_pairs, int64_t *out_components,
-                            int64_t *out_counters)
+int hamming_comp_run(pfz_ctx *ctx, const pfz_dense *V, int64_t hmax, int32_t *out_label, int64_t *out_pairs, int64_t *out_components,
+                     int64_t *out_counters)
 {
     PFZ_HIP(hipSetDevice(ctx->device));
     *out_pairs = *out_components = 0;

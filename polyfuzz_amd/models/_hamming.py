@@ -36,17 +36,47 @@ class Hamming(BaseMatcher):
 
     match:      each from-string's best (or top_n best) to-strings -- an internal Embeddings with binary = "ubinary", true cosine,
                 that matcher's frame and code path.
-    join:       every pair within a distance, exact (K23).
-    components: the connected components of the self-join's graph (K23); polyfuzz_amd.linkage.connected_components(strings,
+    join:       every pair within a distance, exact (K23; K24 with `index`).
+    components: the connected components of the self-join's graph (K23; K24 with `index`); polyfuzz_amd.linkage.connected_components(strings,
                 Hamming(), 0.9, embeddings=codes) turns them into single_linkage's three dicts.
 
     A threshold is either `max_distance`, the largest number of differing bits (an int in [0, d]), or `min_similarity`, a number
     in [0, 1] that is turned into the distance it stands for: the largest h whose score, as float64, is >= min_similarity
     (_lib.hamming_max_distance; equal is kept).  Exactly one of the two is given.
+
+    The attribute `index` chooses how `join` and `components` find their pairs; the results are the same, bit for bit.
+        None      (the default) K23: every pair's distance is computed, tile by tile.
+        "blocks"  K24's block index: the d bits are cut into max_distance + 1 blocks -- two codes within the distance agree
+                  completely on at least one -- and only codes that share a block's bits are compared.  For small distances on
+                  many codes (64-bit fingerprints at 3).  A (d, distance) without an index -- more than 256 blocks, or more
+                  blocks than bits -- is a ValueError before any device call.
+        "auto"    the index where the library's measured rule says it is cheaper (_lib.hamming_index_plan), K23's tiles otherwise.
+    On the two indexed routes last_counts also holds _lib.HAMMING_INDEX_COUNTERS ("route": 1 = the index ran, 0 = the tiles).
     """
+    INDEXES = (None, "blocks", "auto")
+
     def __init__(self, model_id: str = None):
         super().__init__(model_id)
         self.type = "Embeddings"
+        self.index = None
+
+    @property
+    def index(self):
+        return getattr(self, "_index", None)
+
+    @index.setter
+    def index(self, value):
+        if value is not None and not (isinstance(value, str) and value in self.INDEXES):
+            raise ValueError(f'index must be None, "blocks" or "auto", not {value!r}')
+        self._index = value
+
+    def _check_index(self, bits, hmax):
+        """index == "blocks": a ValueError that names the limit when (bits, hmax) has no block index (no device is touched)"""
+        if self.index == "blocks" and hmax >= 0:
+            try:
+                _lib.hamming_index_plan(bits, hmax)
+            except _lib.PfzUnsupported as e:
+                raise ValueError(f'index = "blocks": {e}; use index = "auto" or None') from None
 
     def match(self,
               from_list: List[str],
@@ -118,6 +148,7 @@ class Hamming(BaseMatcher):
             if bits_to != bits:
                 raise ValueError(f"Hamming distance needs two code arrays of equal width, got {bits} and {bits_to} bits" + _lib.BITS_WIDTH_HINT)
         hmax = self._cutoff(bits, min_similarity, max_distance)
+        self._check_index(bits, hmax)
         t0 = time.perf_counter()
         if hmax < 0:
             row_ptr, idx, dist, counts = np.zeros(len(from_list) + 1, np.int64), np.empty(0, np.int32), np.empty(0, np.int32), {"pairs": 0}
@@ -125,7 +156,10 @@ class Hamming(BaseMatcher):
             ctx = _lib.Context.default()
             f_dev = _lib.DeviceDense.upload_bits(ctx, vec_from)
             t_dev = None if vec_to is None else _lib.DeviceDense.upload_bits(ctx, vec_to)
-            row_ptr, idx, dist, counts = _lib.hamming_join(ctx, f_dev, t_dev, hmax)
+            if self.index is None:
+                row_ptr, idx, dist, counts = _lib.hamming_join(ctx, f_dev, t_dev, hmax)
+            else:
+                row_ptr, idx, dist, counts = _lib.hamming_join_indexed(ctx, f_dev, t_dev, hmax, auto=self.index == "auto", counters=True)
         t1 = time.perf_counter()
         names = from_list if to_list is None else to_list
         frm = np.repeat(np.arange(len(from_list), dtype=np.int32), np.diff(row_ptr))
@@ -151,12 +185,18 @@ class Hamming(BaseMatcher):
         Threshold and `embeddings` as `join`.  Sets last_timings and last_counts = {"pairs": hits, "components": components}. """
         vec, bits = self._codes(strings, embeddings, "embeddings")
         hmax = self._cutoff(bits, min_similarity, max_distance)
+        self._check_index(bits, hmax)
         t0 = time.perf_counter()
+        work = {}
         if hmax < 0 or len(strings) == 0:
             label, pairs, components = np.arange(len(strings), dtype=np.int32), 0, len(strings)
-        else:
+        elif self.index is None:
             ctx = _lib.Context.default()
             label, pairs, components = _lib.hamming_components(ctx, _lib.DeviceDense.upload_bits(ctx, vec), hmax)
+        else:
+            ctx = _lib.Context.default()
+            label, pairs, components, work = _lib.hamming_components_indexed(ctx, _lib.DeviceDense.upload_bits(ctx, vec), hmax,
+                                                                             auto=self.index == "auto", counters=True)
         self.last_timings = {"device": (time.perf_counter() - t0) * 1e3, "frame": 0.0}
-        self.last_counts = {"pairs": pairs, "components": components}
+        self.last_counts = {"pairs": pairs, "components": components, **work}
         return label
