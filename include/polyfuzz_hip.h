@@ -1022,6 +1022,26 @@ int pfz_hamming_components_indexed(pfz_ctx *ctx, const pfz_dense *codes, int64_t
  * bits, more than 256 blocks); PFZ_ERR_INVALID: dim_bits outside [1, 2^24), max_distance outside [0, dim_bits], NULL. */
 int pfz_hamming_index_plan(int64_t dim_bits, int64_t max_distance, int64_t *out);
 
+/* ---- K25: SimHash fingerprints of a string list, as a 1-bit operand ---------------
+ * The codes K23 / K24 join, made on the device from a resident list (csrc/k25_core.h is the rule).  Analyzer: TFIDF's -- `params` as
+ * pfz_tfidf_fit takes them: with clean (1-byte code units only) lower-case, keep [a-z0-9 ], collapse runs of ' ', strip; every window
+ * of n consecutive symbols for n in ngram_lo .. ngram_hi, every occurrence; with remove_space_ngrams the windows that hold a ' ' are
+ * dropped.  A symbol is the code point as uint32.  Hash, all mod 2^64: G = 0x9E3779B97F4A7C15; mix(z): z ^= z >> 30, z *=
+ * 0xBF58476D1CE4E5B9, z ^= z >> 27, z *= 0x94D049BB133111EB, z ^= z >> 31; g = mix(G), then g = mix(g ^ c) for the window's symbols in
+ * order; word 0 of the window's hash is g, word q >= 1 is mix(g + q G).  Vote V[64 q + b] = the sum over the windows of +1 where bit b
+ * (least significant = 0) of word q is set, else -1; fingerprint bit k = V[k] > 0 (a tie gives 0), in np.packbits order.  So the first
+ * 64 bits of a wider fingerprint are the 64-bit fingerprint.  A string without a window has an all-zero fingerprint and NO ROW in the
+ * handle: it is nobody's partner.
+ * *out_codes: a fresh PFZ_DENSE_B1 handle (pfz_dense_free) of the strings with a window, in list order, `bits` wide, normalize = 1,
+ * in pfz_dense_upload1's layout.  out_row: host [n], a string's row in the handle, -1 = no window.  out_windows: host [n] or NULL,
+ * the windows of every string.  out_bytes: host [n][bits / 8] or NULL, every string's fingerprint.
+ * n = 0, and a list in which no string has a window, give a handle of 0 rows.  PFZ_ERR_INVALID: a NULL argument, bits that are no
+ * multiple of 64 in [64, 1024], ngram_lo / ngram_hi that do not satisfy 1 <= lo <= hi <= 8, clean on 4-byte code units;
+ * PFZ_ERR_UNSUPPORTED: 2^31 strings or more.  No limit on a string's length.  Profiling scopes: `k25_fingerprint`, `k25_compact`.
+ * Blocks. */
+int pfz_simhash(pfz_ctx *ctx, const pfz_strings *strings, const pfz_tfidf_params *params, int32_t bits, pfz_dense **out_codes,
+                int32_t *out_row, int32_t *out_windows, uint8_t *out_bytes);
+
 /* ---- K15: all pairs at or above a sparse cosine, and their components -----------
  * The threshold form of K3, what de-duplication asks of the reference's TF-IDF matcher: every pair (from-row i, to-row j) whose
  * cosine is >= min_similarity, however many partners a row has -- no top_n to guess, no n x top_n table.  to_index is the

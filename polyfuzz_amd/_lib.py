@@ -147,6 +147,7 @@ SIGNATURES = {
     "pfz_hamming_join_indexed": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, P(c_i64), c_vp]),
     "pfz_hamming_components_indexed": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i32, c_vp, P(c_i64), P(c_i64), c_vp]),
     "pfz_hamming_index_plan": (ctypes.c_int, [c_i64, c_i64, c_vp]),
+    "pfz_simhash": (ctypes.c_int, [c_vp, c_vp, P(TfidfParams), c_i32, P(c_vp), c_vp, c_vp, c_vp]),
     "pfz_dense_join16": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_f64, c_i64, c_i64, c_vp, c_vp, c_vp, P(c_i64), c_vp]),
     "pfz_dense_components16": (ctypes.c_int, [c_vp, c_vp, c_vp, c_f64, c_i64, c_vp, P(c_i64), P(c_i64), c_vp]),
     "pfz_cossim_join": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_f64, c_i64, c_vp, c_vp, c_vp, P(c_i64), c_vp]),
@@ -1403,6 +1404,52 @@ def hamming_components_indexed(ctx, dev, max_distance, auto=False, counters=Fals
     mode = HAMMING_INDEX_AUTO if auto else HAMMING_INDEX_BLOCKS
     return _components_call(dev.n, HAMMING_INDEX_COUNTERS, counters, lambda label, pairs, components, wk:
                             ctx.lib.pfz_hamming_components_indexed(ctx.h, dev.h, int(max_distance), mode, label, pairs, components, wk))
+
+
+# ---- K25: SimHash fingerprints of a resident string list, as a bit handle -------------------------------------------------
+
+SIMHASH_MIN_BITS, SIMHASH_MAX_BITS, SIMHASH_MAX_GRAM = 64, 1024, 8      # kK25MinBits, kK25MaxBits, kK25MaxGram of csrc/k25_core.h
+
+
+def check_simhash_bits(bits):
+    """bits as an int: a multiple of 64 in [64, 1024] (ValueError otherwise)"""
+    if isinstance(bits, bool) or not isinstance(bits, (int, np.integer)) or not SIMHASH_MIN_BITS <= int(bits) <= SIMHASH_MAX_BITS \
+            or int(bits) % 64:
+        raise ValueError(f"bits must be a multiple of 64 in [{SIMHASH_MIN_BITS}, {SIMHASH_MAX_BITS}], not {bits!r}")
+    return int(bits)
+
+
+def check_simhash_grams(n_gram_range):
+    """(lo, hi) as ints with 1 <= lo <= hi <= 8 (ValueError otherwise)"""
+    try:
+        lo, hi = n_gram_range
+        ok = all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in (lo, hi)) and 1 <= lo <= hi <= SIMHASH_MAX_GRAM
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"n_gram_range must be (lo, hi) with 1 <= lo <= hi <= {SIMHASH_MAX_GRAM}, not {n_gram_range!r}")
+    return int(lo), int(hi)
+
+
+def simhash(ctx, dev_strings, params, bits, want_bytes=False):
+    """K25: the SimHash fingerprints of a resident string list (csrc/k25_core.h is the rule; `params` a TfidfParams: TFIDF's
+    analyzer) -> (DeviceDense, row, windows[, bytes]).  The handle holds the strings that have a window, in list order, as a bit
+    operand (dtype "binary", dim = bits, normalize=True: what DeviceDense.upload_bits makes of such rows) for hamming_join /
+    hamming_components / their indexed forms / dense_topn.  row int32[n]: a string's row in the handle, -1 = no window; windows
+    int32[n]; want_bytes: uint8[n, bits / 8], every string's fingerprint (zeros where it has no window), np.packbits order."""
+    bits = check_simhash_bits(bits)
+    check_simhash_grams((params.ngram_lo, params.ngram_hi))
+    if params.clean and dev_strings.char_width != 1:
+        raise ValueError("clean on 4-byte code units: strings with code points > 0xFF are cleaned on the host")
+    n = dev_strings.n
+    row, windows = np.empty(n, np.int32), np.empty(n, np.int32)
+    out = np.empty((n, bits // 8), np.uint8) if want_bytes else None
+    h = c_vp()
+    check(ctx.lib.pfz_simhash(ctx.h, dev_strings.h, ctypes.byref(params), bits, ctypes.byref(h), _ptr(row), _ptr(windows),
+                              None if out is None else _ptr(out)))
+    m = DeviceDense(ctx, h)
+    m.n, m.dim, m.normalize, m.dtype = int((row >= 0).sum()), bits, True, BINARY
+    return (m, row, windows, out) if want_bytes else (m, row, windows)
 
 
 # ---- K22: the same two entries searched on the 16-bit matrix cores, scored exactly on the fp32 vectors -------------------

@@ -151,7 +151,8 @@ def connected_components(strings: List[str], model,
     by default): the components of "score >= min_similarity * 100" -- equal strings share one whenever they have a token; under
     WRatio, min_similarity <= 0.855 links everything that shares a word with a string 1.5 times its length or more.  Or a Hamming
     model (K23): `embeddings` are the strings' binary codes, required, and the components are those of "at most h differing bits"
-    for the largest h whose score float32(d - 2 h) / float32(d) reaches min_similarity."""
+    for the largest h whose score float32(d - 2 h) / float32(d) reaches min_similarity.  Or a SimHash model (K25): the same components
+    over the fingerprints it makes of the strings itself; a string without an n-gram window is its own component."""
     strings = list(strings)
     extra = {} if embeddings is None else {"embeddings": embeddings}
     return dicts_from_labels(strings, model.components(strings, min_similarity, **extra))

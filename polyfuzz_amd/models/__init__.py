@@ -7,5 +7,6 @@ from ._embeddings import Embeddings
 from ._blocked import BlockedEditDistance
 from ._jaro import JaroWinkler
 from ._hamming import Hamming
+from ._simhash import SimHash
 
-__all__ = ["BaseMatcher", "cosine_similarity", "TFIDF", "EditDistance", "RapidFuzz", "Embeddings", "BlockedEditDistance", "JaroWinkler", "Hamming"]
+__all__ = ["BaseMatcher", "cosine_similarity", "TFIDF", "EditDistance", "RapidFuzz", "Embeddings", "BlockedEditDistance", "JaroWinkler", "Hamming", "SimHash"]

@@ -66,17 +66,11 @@ class Hamming(BaseMatcher):
 
     @index.setter
     def index(self, value):
-        if value is not None and not (isinstance(value, str) and value in self.INDEXES):
-            raise ValueError(f'index must be None, "blocks" or "auto", not {value!r}')
-        self._index = value
+        self._index = check_index(value)
 
     def _check_index(self, bits, hmax):
         """index == "blocks": a ValueError that names the limit when (bits, hmax) has no block index (no device is touched)"""
-        if self.index == "blocks" and hmax >= 0:
-            try:
-                _lib.hamming_index_plan(bits, hmax)
-            except _lib.PfzUnsupported as e:
-                raise ValueError(f'index = "blocks": {e}; use index = "auto" or None') from None
+        check_index_plan(self.index, bits, hmax)
 
     def match(self,
               from_list: List[str],
@@ -106,17 +100,7 @@ class Hamming(BaseMatcher):
     @staticmethod
     def _cutoff(bits, min_similarity, max_distance):
         """the one threshold of a call as a distance (-1: nothing passes); both or neither given, or one out of range: ValueError"""
-        if (min_similarity is None) == (max_distance is None):
-            raise ValueError("give exactly one of min_similarity and max_distance"
-                             + (" (both are set)" if min_similarity is not None else " (neither is set)"))
-        if max_distance is not None:
-            if isinstance(max_distance, bool) or not isinstance(max_distance, (int, np.integer)) or not 0 <= int(max_distance) <= bits:
-                raise ValueError(f"max_distance must be an int in [0, {bits}] (the codes' width in bits), not {max_distance!r}")
-            return int(max_distance)
-        t = _lib.check_min_similarity(min_similarity)
-        if not 1 <= bits < 1 << 24:
-            raise ValueError(f"the codes have {bits} bits: a similarity is defined for 1 to 2**24 - 1")
-        return _lib.hamming_max_distance(bits, t)
+        return cutoff(bits, min_similarity, max_distance)
 
     def join(self,
              from_list: List[str],
@@ -151,21 +135,15 @@ class Hamming(BaseMatcher):
         self._check_index(bits, hmax)
         t0 = time.perf_counter()
         if hmax < 0:
-            row_ptr, idx, dist, counts = np.zeros(len(from_list) + 1, np.int64), np.empty(0, np.int32), np.empty(0, np.int32), {"pairs": 0}
+            row_ptr, idx, dist, counts = empty_join(len(from_list))
         else:
             ctx = _lib.Context.default()
             f_dev = _lib.DeviceDense.upload_bits(ctx, vec_from)
             t_dev = None if vec_to is None else _lib.DeviceDense.upload_bits(ctx, vec_to)
-            if self.index is None:
-                row_ptr, idx, dist, counts = _lib.hamming_join(ctx, f_dev, t_dev, hmax)
-            else:
-                row_ptr, idx, dist, counts = _lib.hamming_join_indexed(ctx, f_dev, t_dev, hmax, auto=self.index == "auto", counters=True)
+            row_ptr, idx, dist, counts = join_handles(ctx, f_dev, t_dev, hmax, self.index)
         t1 = time.perf_counter()
-        names = from_list if to_list is None else to_list
         frm = np.repeat(np.arange(len(from_list), dtype=np.int32), np.diff(row_ptr))
-        sim = _lib.hamming_similarity(dist, max(bits, 1)).astype(np.float64)
-        matches = pd.DataFrame({"From": gather_column(from_list, frm), "To": gather_column(names, idx), "Similarity": sim,
-                                "Distance": dist}, copy=False)
+        matches = join_frame(from_list, from_list if to_list is None else to_list, frm, idx, dist, bits)
         self.last_timings = {"device": (t1 - t0) * 1e3, "frame": (time.perf_counter() - t1) * 1e3}
         self.last_counts = counts
         return matches
@@ -187,16 +165,70 @@ class Hamming(BaseMatcher):
         hmax = self._cutoff(bits, min_similarity, max_distance)
         self._check_index(bits, hmax)
         t0 = time.perf_counter()
-        work = {}
         if hmax < 0 or len(strings) == 0:
-            label, pairs, components = np.arange(len(strings), dtype=np.int32), 0, len(strings)
-        elif self.index is None:
-            ctx = _lib.Context.default()
-            label, pairs, components = _lib.hamming_components(ctx, _lib.DeviceDense.upload_bits(ctx, vec), hmax)
+            label, pairs, components, work = np.arange(len(strings), dtype=np.int32), 0, len(strings), {}
         else:
             ctx = _lib.Context.default()
-            label, pairs, components, work = _lib.hamming_components_indexed(ctx, _lib.DeviceDense.upload_bits(ctx, vec), hmax,
-                                                                             auto=self.index == "auto", counters=True)
+            label, pairs, components, work = components_handle(ctx, _lib.DeviceDense.upload_bits(ctx, vec), hmax, self.index)
         self.last_timings = {"device": (time.perf_counter() - t0) * 1e3, "frame": 0.0}
         self.last_counts = {"pairs": pairs, "components": components, **work}
         return label
+
+
+# ---- what join and components do behind their uploads, on handles (SimHash runs the same on the handles K25 makes) -----------------
+
+def empty_join(n_from):
+    """the result of a join in which nothing passes: (row_ptr, idx, dist, counts)"""
+    return np.zeros(n_from + 1, np.int64), np.empty(0, np.int32), np.empty(0, np.int32), {"pairs": 0}
+
+
+def join_handles(ctx, f_dev, t_dev, hmax, index):
+    """every pair of two bit handles (t_dev None: the self-join) within hmax >= 0 bits, by the route `index` names (Hamming.INDEXES)
+    -> (row_ptr, idx, dist, counts) as _lib.hamming_join"""
+    if index is None:
+        return _lib.hamming_join(ctx, f_dev, t_dev, hmax)
+    return _lib.hamming_join_indexed(ctx, f_dev, t_dev, hmax, auto=index == "auto", counters=True)
+
+
+def components_handle(ctx, dev, hmax, index):
+    """the components of one bit handle's self-join within hmax >= 0 bits -> (label, pairs, components, the indexed routes' counters)"""
+    if index is None:
+        return _lib.hamming_components(ctx, dev, hmax) + ({},)
+    return _lib.hamming_components_indexed(ctx, dev, hmax, auto=index == "auto", counters=True)
+
+
+def join_frame(from_list, names, frm, idx, dist, bits):
+    """the frame From, To, Similarity, Distance of the pairs (from_list[frm[p]], names[idx[p]]) at dist[p] of `bits` bits"""
+    sim = _lib.hamming_similarity(dist, max(bits, 1)).astype(np.float64)
+    return pd.DataFrame({"From": gather_column(from_list, frm), "To": gather_column(names, idx), "Similarity": sim, "Distance": dist},
+                        copy=False)
+
+
+def check_index(value):
+    if value is not None and not (isinstance(value, str) and value in Hamming.INDEXES):
+        raise ValueError(f'index must be None, "blocks" or "auto", not {value!r}')
+    return value
+
+
+def check_index_plan(index, bits, hmax):
+    """index == "blocks": a ValueError that names the limit when (bits, hmax) has no block index (no device is touched)"""
+    if index == "blocks" and hmax >= 0:
+        try:
+            _lib.hamming_index_plan(bits, hmax)
+        except _lib.PfzUnsupported as e:
+            raise ValueError(f'index = "blocks": {e}; use index = "auto" or None') from None
+
+
+def cutoff(bits, min_similarity, max_distance):
+    """the one threshold of a call as a distance (-1: nothing passes); both or neither given, or one out of range: ValueError"""
+    if (min_similarity is None) == (max_distance is None):
+        raise ValueError("give exactly one of min_similarity and max_distance"
+                         + (" (both are set)" if min_similarity is not None else " (neither is set)"))
+    if max_distance is not None:
+        if isinstance(max_distance, bool) or not isinstance(max_distance, (int, np.integer)) or not 0 <= int(max_distance) <= bits:
+            raise ValueError(f"max_distance must be an int in [0, {bits}] (the codes' width in bits), not {max_distance!r}")
+        return int(max_distance)
+    t = _lib.check_min_similarity(min_similarity)
+    if not 1 <= bits < 1 << 24:
+        raise ValueError(f"the codes have {bits} bits: a similarity is defined for 1 to 2**24 - 1")
+    return _lib.hamming_max_distance(bits, t)

@@ -73,6 +73,22 @@ _RANGE_FILL = os.environ.get("PFZ_RANGE_FILL", "1") != "0"      # (A/B knob: 0 =
 _FROM_IN_PACK = os.environ.get("PFZ_FROM_IN_PACK", "1") != "0"      # (A/B knob of tools/match_wall_probe.py; the frames are the same)
 
 
+def upload_strings(strings, clean_string, objects=None):
+    """A string list as the analyzer's kernels take it (TFIDF's K1 / K2, SimHash's K25) -> _lib.DeviceStrings.  1-byte lists go up
+    as they are and are cleaned on the device; a list with code points > 0xFF is cleaned here first when clean_string is set.
+    objects: see _lib.pack_strings (the From column, filled in the packer's walk over the strings)"""
+    ctx = _lib.Context.default()
+    direct = _lib.DeviceStrings.upload_direct(ctx, strings, objects) if len(strings) >= 1024 and _DIRECT_PACK else None
+    if direct is not None:          # (1-byte strings packed straight into the pinned staging buffer)
+        return direct
+    packed = _lib.pack_strings(strings, objects)
+    if clean_string and packed[2] != 1:
+        # code points > 0xFF: clean on the host (str.lower() can map into ASCII); cleaning is idempotent,
+        # so the device's clean pass leaves these untouched
+        packed = _lib.pack_strings([_clean_string(s) for s in strings])
+    return _lib.DeviceStrings.upload_packed(ctx, *packed)
+
+
 class HipTfidfVectorizer:
     """What `TFIDF.vectorizer` holds after a fit: the device-resident vocabulary +
     idf, with the read-only parts of sklearn's TfidfVectorizer surface
@@ -354,16 +370,7 @@ class TFIDF(BaseMatcher):
 
     def _upload(self, strings, objects=None):
         """objects: see _lib.pack_strings (the From column, filled in the packer's walk over the strings)"""
-        ctx = _lib.Context.default()
-        direct = _lib.DeviceStrings.upload_direct(ctx, strings, objects) if len(strings) >= 1024 and _DIRECT_PACK else None
-        if direct is not None:          # (1-byte strings packed straight into the pinned staging buffer)
-            return direct
-        packed = _lib.pack_strings(strings, objects)
-        if self.clean_string and packed[2] != 1:
-            # code points > 0xFF: clean on the host (str.lower() can map into ASCII); cleaning is idempotent,
-            # so the device's clean pass leaves these untouched
-            packed = _lib.pack_strings([_clean_string(s) for s in strings])
-        return _lib.DeviceStrings.upload_packed(ctx, *packed)
+        return upload_strings(strings, self.clean_string, objects)
 
     def _extract_tf_idf(self, from_list, to_list=None, re_train=True, from_objects=None):
         """ reference _tfidf.py:102-118: fit on to_list + from_list (or from_list alone), keep the
